@@ -22,6 +22,9 @@ the other single-GPU BASELINE configs: config 3 at its full size (10 M frames, d
 a 4096-frame subset against the oracle), config 5 (3 biases x 2 mode sets, 1 M frames each), decode, the tonal case
 and the exact-kernels-only rate of the headline.  `config4_share` is the per-GPU share of config 4 (12.5 M frames of
 the mixed corpus): part of the default N = 1 line, and run on every rank when N > 1.
+
+`--dump-outputs DIR` writes a fixed, seeded sample of what the headline's last timed step computed (the same every run
+with the same arguments), so that two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -39,6 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 HBM_PEAK_GBS = 8000.0           # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 BYTES_PER_STEREO_FRAME = 4520
 REFERENCE_NODE12_ONE_CORE = 2150.0   # the reference itself, Node 12, 1 Xeon core, survey container
+DUMP_BYTES = 60 << 20           # --dump-outputs: all ranks together, under 64 MB with the .npy headers
 
 
 def xorshift_jump(seed, steps):
@@ -175,6 +179,24 @@ def node_baseline(frames, threads):
         return {'error': str(e)[:300]}
 
 
+def dump_outputs(out_dir, rows, suffix, budget):
+    """--dump-outputs: `rows` maps a name to a device tensor of the timed path's output, one row per sound unit or frame
+    (the same count for every name).  Writes a fixed, seeded sample of the rows as float32 to out_dir/<name><suffix>.npy
+    and their row numbers to out_dir/index<suffix>.npy (float64), `budget` bytes at most; every row when they fit."""
+    import numpy as np
+    import torch
+    first = next(iter(rows.values()))
+    n = first.shape[0]
+    per_row = 4 * sum(t.shape[1] for t in rows.values()) + 8
+    keep = min(n, budget // per_row)
+    idx = np.sort(np.random.default_rng(20240601).choice(n, keep, replace=False)) if keep < n else np.arange(n)
+    sel = torch.from_numpy(idx).to(first.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'index%s.npy' % suffix), idx.astype(np.float64))
+    for name, t in rows.items():
+        np.save(os.path.join(out_dir, '%s%s.npy' % (name, suffix)), t[sel].cpu().numpy().astype(np.float32))
+
+
 def self_launch(args):
     """--gpus N outside torch.distributed: start the N ranks as fresh processes before any GPU call."""
     s = socket.socket()
@@ -206,7 +228,11 @@ def main():
     ap.add_argument('--config3-frames', type=int, default=10 << 20)
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL); gloo for rehearsals')
     ap.add_argument('--force-device', type=int, default=-1, help='rehearsal only: put every rank on this device')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write a fixed sample of what the last one '
+                    'computed (the headline\'s units, or PCM with --decode) to DIR/<name>.npy as float32, 64 MB at most')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -330,6 +356,11 @@ def main():
         redo_fraction, spec_units, spec_detail = None, 0, None
     else:
         units, elapsed, kernel_ms, redo_fraction, spec_units, spec_detail = encode_run(pcm, frames, c_opts, args.steps, args.warmup)
+    if args.dump_outputs:
+        ctx.synchronize()
+        rows = ({'pcm_ch%d' % c: p.view(-1, 512) for c, p in enumerate(out_pcm)} if args.decode else
+                {'units': units.view(-1, 212)})
+        dump_outputs(args.dump_outputs, rows, '' if world == 1 else '.rank%d' % rank, DUMP_BYTES // world)
 
     line = None
     if rank == 0:

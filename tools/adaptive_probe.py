@@ -2,8 +2,8 @@
  * k_pack<.., SPEC> on exact coefficients (bounds of zero): units packed again in binary64 (c1_ctx_quantization_stats);
  * the speculative transient detector: units rechecked with the reference's arithmetic (c1_ctx_detection_stats).
 And what each path costs when it is forced on / off (C1_SPEC=0 = everything exact), per material.  python tools/adaptive_probe.py"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import carta1_amd as c1
 from carta1_amd import capi

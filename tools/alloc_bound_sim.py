@@ -4,8 +4,8 @@ sound unit allocateBits (bitallocation.js:74-142) really needs when candidates a
 on their total distortion, and how far that bound sits below the totals the heaps produce.  Uses the C oracle for the
 transforms and a Python restatement of distributeBitsRDO / calculateTotalDistortion; asserts bound <= total on every
 candidate it looks at.  Typical output: tonal material 7-8 heaps per unit -> 2, gap 1-4 %."""
-import sys, math, ctypes as C, numpy as np
-sys.path.insert(0, '/root/repo/tests')
+import os, sys, math, ctypes as C, numpy as np
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
 import oracle_lib as O
 L = O.lib()
 SPECS = [8,8,8,8,4,4,4,4,8,8,8,8,6,6,6,6,6,6,6,6,6,6,6,6,7,7,7,7,9,9,9,9,10,10,10,10,12,12,12,12,12,12,12,12,20,20,20,20,20,20,20,20]

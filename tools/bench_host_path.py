@@ -1,5 +1,5 @@
-import time, numpy as np, sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, time, numpy as np, sys
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path[:0] = [R, os.path.join(R, 'tests')]
 import carta1_amd as c1
 ctx = c1.Context(0)
 n = 262144

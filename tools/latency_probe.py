@@ -1,6 +1,6 @@
 """Latency of small streaming calls (c1_enc_stream_push of 1..512 mono frames) by speculation mode: python tools/latency_probe.py"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import carta1_amd as c1
 ctx = c1.Context(0)
