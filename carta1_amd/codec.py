@@ -339,6 +339,52 @@ class Context:
         capi.check(capi.load().c1_mdct_batch(self._h, b.ctypes.data, frames, halo_frames, m.ctypes.data, co.ctypes.data, bw.ctypes.data))
         return co, bw
 
+    # ---- the decoder's pipeline stages (codec/pipeline/decoder.js:52-389, serialization.js:111-176), one channel ------------
+    FIELD_SHAPES = (('nbfu', ()), ('block_modes', (3,)), ('sfi', (52,)), ('wl', (52,)), ('quantized', (512,)))
+
+    def unpack_units(self, units):
+        """deserializeFrame, serialization.js:111-176, over consecutive units of one channel: uint8 [frames, 212] -> dict of
+        int32 arrays nbfu [frames], block_modes [frames, 3], sfi / wl [frames, 52], quantized [frames, 512] (BFU order);
+        entries the reference leaves unset are zeros"""
+        u = np.ascontiguousarray(units, dtype=np.uint8).reshape(-1, capi.UNIT_BYTES)
+        frames = u.shape[0]
+        out = {k: np.zeros((frames,) + shape, dtype=np.int32) for k, shape in self.FIELD_SHAPES}
+        capi.check(capi.load().c1_unpack_units(self._h, u.ctypes.data, frames, *[out[k].ctypes.data for k, _ in self.FIELD_SHAPES]))
+        return out
+
+    def dequantize_frames(self, fields):
+        """dequantizationStage, decoder.js:52-98: a dict of frame fields as unpack_units returns it -> float32 [frames, 512]"""
+        frames = int(np.asarray(fields['nbfu']).size)
+        arrs = []
+        for k, shape in self.FIELD_SHAPES:
+            a = np.ascontiguousarray(fields[k], dtype=np.int32)
+            if a.size != frames * int(np.prod(shape, dtype=np.int64)):
+                raise ValueError('%s must hold %s entries per frame' % (k, shape or 1))
+            arrs.append(a)
+        out = np.zeros((frames, 512), dtype=np.float32)
+        capi.check(capi.load().c1_dequantize_frames(self._h, frames, *[a.ctypes.data for a in arrs], out.ctypes.data))
+        return out
+
+    def imdct(self, coefs, block_modes, halo_frames=0):
+        """imdctStage, decoder.js:116-330: coefs float32 [(halo_frames + frames), 512], block_modes int [(halo_frames + frames), 3]
+        (the first halo_frames rows: the stream's previous frame) -> bands float32 [frames, 512] (low128 | mid128 | high256)"""
+        c = np.ascontiguousarray(coefs, dtype=np.float32).reshape(-1, 512)
+        frames = c.shape[0] - halo_frames
+        m = np.ascontiguousarray(block_modes, dtype=np.int32).reshape(-1)
+        if m.size != 3 * c.shape[0]:
+            raise ValueError('block_modes must hold three entries per frame of coefs')
+        out = np.zeros((max(frames, 0), 512), dtype=np.float32)
+        capi.check(capi.load().c1_imdct_batch(self._h, c.ctypes.data, frames, halo_frames, m.ctypes.data, out.ctypes.data))
+        return out
+
+    def qmf_synthesis(self, bands, halo_frames=0):
+        """qmfSynthesisStage, decoder.js:349-389: bands float32 [(halo_frames + frames), 512] -> PCM float32 [frames, 512]"""
+        b = np.ascontiguousarray(bands, dtype=np.float32).reshape(-1, 512)
+        frames = b.shape[0] - halo_frames
+        out = np.zeros((max(frames, 0), 512), dtype=np.float32)
+        capi.check(capi.load().c1_qmf_synthesis_batch(self._h, b.ctypes.data, frames, halo_frames, out.ctypes.data))
+        return out
+
     def pack_spec_tap_device(self, coefs_ptr, eps_ptr, side_ptr, alloc_ptr, units, units_out_ptr, lists_ptr, all_long=True):
         """Test tap: the speculative quantizer + packer on caller-supplied coefficients, bounds and records (device pointers)."""
         capi.check(capi.load().c1_pack_spec_tap_device(

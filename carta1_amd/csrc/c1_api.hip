@@ -1478,6 +1478,113 @@ int c1_mdct_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_fram
   return C1_OK;
 }
 
+// ---- the decoder's pipeline stages on their own (codec/pipeline/decoder.js:52-389, serialization.js:111-176), host-resident ----
+
+namespace {
+constexpr int64_t kMaxStageFrames = (int64_t)1 << 20;
+}  // namespace
+
+int c1_unpack_units(c1_ctx *ctx, const uint8_t *units, int64_t frames, int32_t *nbfu, int32_t *block_modes, int32_t *sfi,
+                    int32_t *wl, int32_t *quantized) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "unpack: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!units || !nbfu || !block_modes || !sfi || !wl || !quantized) return fail(C1_ERR_ARG, "unpack: NULL argument");
+  DeviceScratch ds;
+  uint8_t *du; int32_t *dn, *dm, *ds_, *dw, *dq;
+  const size_t n = (size_t)frames;
+  if ((rc = ds.alloc(&du, n * C1_UNIT_BYTES)) || (rc = ds.alloc(&dn, n)) || (rc = ds.alloc(&dm, 3 * n)) || (rc = ds.alloc(&ds_, 52 * n)) ||
+      (rc = ds.alloc(&dw, 52 * n)) || (rc = ds.alloc(&dq, 512 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(du, units, n * C1_UNIT_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_unpack_units(du, frames, dn, dm, ds_, dw, dq, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(nbfu, dn, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(block_modes, dm, 3 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(sfi, ds_, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(wl, dw, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(quantized, dq, 512 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_dequantize_frames(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi,
+                         const int32_t *wl, const int32_t *quantized, float *coefs) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "dequantize frames: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!nbfu || !block_modes || !sfi || !wl || !quantized || !coefs) return fail(C1_ERR_ARG, "dequantize frames: NULL argument");
+  // the indices the reference reads (BFUs below nBfu) must name table entries: BFU_START_*, WORD_LENGTH_BITS, SCALE_FACTORS
+  for (int64_t f = 0; f < frames; f++) {
+    const int32_t n = nbfu[f];
+    if (n < 0 || n > 52) return fail(C1_ERR_ARG, "dequantize frames: frame %lld: nBfu %d outside 0..52", (long long)f, n);
+    for (int b = 0; b < n; b++) {
+      const int32_t w = wl[52 * f + b], s = sfi[52 * f + b];
+      if (w < 0 || w > 15) return fail(C1_ERR_ARG, "dequantize frames: frame %lld BFU %d: word length index %d outside 0..15", (long long)f, b, w);
+      if (s < 0 || s > 63) return fail(C1_ERR_ARG, "dequantize frames: frame %lld BFU %d: scale factor index %d outside 0..63", (long long)f, b, s);
+    }
+  }
+  DeviceScratch ds;
+  int32_t *dn, *dm, *ds_, *dw, *dq; float *dc;
+  const size_t n = (size_t)frames;
+  if ((rc = ds.alloc(&dn, n)) || (rc = ds.alloc(&dm, 3 * n)) || (rc = ds.alloc(&ds_, 52 * n)) || (rc = ds.alloc(&dw, 52 * n)) ||
+      (rc = ds.alloc(&dq, 512 * n)) || (rc = ds.alloc(&dc, 512 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(dn, nbfu, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dm, block_modes, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ds_, sfi, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dw, wl, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dq, quantized, 512 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_dequantize_frames(ctx->d_tables, dn, dm, ds_, dw, dq, frames, dc, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(coefs, dc, 512 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_imdct_batch(c1_ctx *ctx, const float *coefs, int64_t frames, int halo_frames, const int32_t *block_modes, float *bands) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (halo_frames < 0 || halo_frames > 1) return fail(C1_ERR_ARG, "imdct: halo_frames must be 0 or 1, got %d", halo_frames);
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "imdct: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!coefs || !block_modes || !bands) return fail(C1_ERR_ARG, "imdct: NULL argument");
+  DeviceScratch ds;
+  float *dc, *db; int32_t *dm;
+  const size_t n = (size_t)frames, all = (size_t)(frames + halo_frames);
+  if ((rc = ds.alloc(&dc, 512 * all)) || (rc = ds.alloc(&dm, 3 * all)) || (rc = ds.alloc(&db, 512 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(dc, coefs, 512 * all * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dm, block_modes, 3 * all * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_imdct_frames(ctx->d_tables, dc, dm, frames, halo_frames, db, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(bands, db, 512 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_qmf_synthesis_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, float *pcm) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (halo_frames < 0 || halo_frames > 1) return fail(C1_ERR_ARG, "qmf synthesis: halo_frames must be 0 or 1, got %d", halo_frames);
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "qmf synthesis: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!bands || !pcm) return fail(C1_ERR_ARG, "qmf synthesis: NULL argument");
+  DeviceScratch ds;
+  float *db, *dp;
+  const size_t n = (size_t)frames, all = (size_t)(frames + halo_frames);
+  if ((rc = ds.alloc(&db, 512 * all)) || (rc = ds.alloc(&dp, 512 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(db, bands, 512 * all * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_qmf_synthesis_frames(ctx->d_tables, db, frames, halo_frames, dp, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(pcm, dp, 512 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 int c1_pack_spec_tap_device(c1_ctx *ctx, const float *coefs, const float *eps, const uint8_t *side, const uint8_t *alloc,
                             int64_t units, int all_long, uint8_t *units_out, uint32_t *lists) {
   CTX_GUARD(ctx);

@@ -186,6 +186,16 @@ void c1k_launch_detect(const C1EncodeLaunch &L, float *bands_ws, double *feat_ws
 // mdctStage + scale factors from stored band samples (k_mdct_bands): bands_ws (units + channels) * 512 floats with slot row 0 =
 // frame -1, modes_ws one byte per unit, lists_ws = {count all-long, count mixed, -, -} then the two unit lists, `units` entries apart
 void c1k_launch_mdct_bands(const C1EncodeLaunch &L, const float *bands_ws, const uint8_t *modes_ws, const uint32_t *lists_ws, hipStream_t stream);
+// the decoder's pipeline stages on their own (c1_k_decode_stages.hip), one channel; device pointers; coefs / modes / bands in
+// point at frame -halo
+void c1k_launch_unpack_units(const uint8_t *units, int64_t frames, int32_t *nbfu, int32_t *modes, int32_t *sfi, int32_t *wl,
+                             int32_t *q, hipStream_t stream);
+void c1k_launch_dequantize_frames(const C1DevTables *tables, const int32_t *nbfu, const int32_t *modes, const int32_t *sfi,
+                                  const int32_t *wl, const int32_t *q, int64_t frames, float *coefs, hipStream_t stream);
+void c1k_launch_imdct_frames(const C1DevTables *tables, const float *coefs, const int32_t *modes, int64_t frames, int halo,
+                             float *bands, hipStream_t stream);
+void c1k_launch_qmf_synthesis_frames(const C1DevTables *tables, const float *bands, int64_t frames, int halo, float *pcm,
+                                     hipStream_t stream);
 // the single-stage functions the reference exports next to encode()/decode() (c1_k_stages.hip); device pointers
 void c1k_launch_quantize_one(const C1DevTables *tables, const float *x, int n, int sfi, int bits, int32_t *out, hipStream_t stream);
 void c1k_launch_dequantize_one(const C1DevTables *tables, const int32_t *q, int n, int sfi, int bits, float *out, hipStream_t stream);

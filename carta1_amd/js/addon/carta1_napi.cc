@@ -629,6 +629,76 @@ napi_value MdctFromBands(napi_env env, napi_callback_info info) { // (ctx, Float
   return arr;
 }
 
+// the decoder's pipeline stages, one channel (c1_unpack_units, c1_dequantize_frames, c1_imdct_batch, c1_qmf_synthesis_batch)
+napi_value UnpackUnits(napi_env env, napi_callback_info info) {   // (ctx, Uint8Array units) -> [nbfu, blockModes, sfi, wl, quantized] Int32Arrays
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  c1_ctx *ctx; void *u; size_t n;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_uint8_array, &u, &n)) return nullptr;
+  if (n % C1_UNIT_BYTES) { napi_throw_type_error(env, nullptr, "unpackUnits: whole units of 212 bytes"); return nullptr; }
+  const size_t frames = n / C1_UNIT_BYTES, per[5] = {1, 3, 52, 52, 512};
+  napi_value arr, out[5];
+  void *p[5];
+  for (int i = 0; i < 5; i++) {
+    napi_value ab;
+    NAPI_OK(napi_create_arraybuffer(env, frames * per[i] * 4 + 4, &p[i], &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, frames * per[i], ab, 0, &out[i]));
+  }
+  const int rc = c1_unpack_units(ctx, static_cast<const uint8_t *>(u), (int64_t)frames, static_cast<int32_t *>(p[0]), static_cast<int32_t *>(p[1]),
+                                 static_cast<int32_t *>(p[2]), static_cast<int32_t *>(p[3]), static_cast<int32_t *>(p[4]));
+  if (rc) return throw_c1(env, rc);
+  NAPI_OK(napi_create_array_with_length(env, 5, &arr));
+  for (int i = 0; i < 5; i++) NAPI_OK(napi_set_element(env, arr, i, out[i]));
+  return arr;
+}
+napi_value DequantizeFrames(napi_env env, napi_callback_info info) {  // (ctx, Int32Array nbfu, blockModes, sfi, wl, quantized) -> Float32Array coefs
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx; void *a[5]; size_t n[5];
+  if (!get_external(env, argv[0], &ctx)) return nullptr;
+  for (int i = 0; i < 5; i++) if (!get_typed(env, argv[1 + i], napi_int32_array, &a[i], &n[i])) return nullptr;
+  const size_t frames = n[0];
+  if (n[1] != 3 * frames || n[2] != 52 * frames || n[3] != 52 * frames || n[4] != 512 * frames) {
+    napi_throw_type_error(env, nullptr, "dequantizeFrames: nBfu, 3 block modes, 52 sfi, 52 wl and 512 mantissas per frame");
+    return nullptr;
+  }
+  float *c;
+  napi_value out = make_f32(env, frames * 512, &c);
+  const int rc = c1_dequantize_frames(ctx, (int64_t)frames, static_cast<const int32_t *>(a[0]), static_cast<const int32_t *>(a[1]),
+                                      static_cast<const int32_t *>(a[2]), static_cast<const int32_t *>(a[3]), static_cast<const int32_t *>(a[4]), c);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+napi_value Imdct(napi_env env, napi_callback_info info) {  // (ctx, Float32Array coefs incl. halo, haloFrames, Int32Array modes incl. halo) -> Float32Array bands
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx; void *d, *m; size_t n, nm; int32_t halo = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &n)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_typed(env, argv[3], napi_int32_array, &m, &nm)) return nullptr;
+  if (n % 512 || halo < 0 || (size_t)halo > n / 512 || nm != 3 * (n / 512)) { napi_throw_type_error(env, nullptr, "imdct: whole frames and three block modes per frame"); return nullptr; }
+  const int64_t frames = (int64_t)(n / 512) - halo;
+  float *b;
+  napi_value out = make_f32(env, (size_t)frames * 512, &b);
+  const int rc = c1_imdct_batch(ctx, static_cast<const float *>(d), frames, halo, static_cast<const int32_t *>(m), b);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+napi_value QmfSynthesis(napi_env env, napi_callback_info info) {  // (ctx, Float32Array bands incl. halo, haloFrames) -> Float32Array pcm
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  c1_ctx *ctx; void *d; size_t n; int32_t halo = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &n)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (n % 512 || halo < 0 || (size_t)halo > n / 512) { napi_throw_type_error(env, nullptr, "qmfSynthesis: whole frames of 512 samples"); return nullptr; }
+  const int64_t frames = (int64_t)(n / 512) - halo;
+  float *p;
+  napi_value out = make_f32(env, (size_t)frames * 512, &p);
+  const int rc = c1_qmf_synthesis_batch(ctx, static_cast<const float *>(d), frames, halo, p);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"abiVersion", nullptr, AbiVersion, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -652,6 +722,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fft", nullptr, Fft, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"qmfAnalysis", nullptr, QmfAnalysis, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"mdctFromBands", nullptr, MdctFromBands, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"unpackUnits", nullptr, UnpackUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"dequantizeFrames", nullptr, DequantizeFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"imdct", nullptr, Imdct, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"qmfSynthesis", nullptr, QmfSynthesis, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

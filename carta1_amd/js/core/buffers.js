@@ -9,5 +9,7 @@ export class BufferPool {
     this.encoderOptionsKey = null
     this.qmfHistory = null // qmfAnalysisStage on its own: the previous frame's PCM (the QMF delay lines are made of it)
     this.mdctPreviousBands = null // mdctStage on its own: the previous frame's band samples (mdctOverlap is made of their tails)
+    this.imdctPrevious = null // imdctStage on its own: the previous frame's coefficients and modes (imdctOverlap is made of them)
+    this.synthesisPreviousBands = null // qmfSynthesisStage on its own: the previous frame's bands (qmfDelays are made of them)
   }
 }

@@ -264,6 +264,37 @@ int c1_qmf_analysis_batch(c1_ctx *ctx, const float *pcm, int64_t frames, int hal
 int c1_mdct_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, const int32_t *block_modes, float *coefs,
                   float *bands_windowed);
 
+/* The decoder's pipeline stages (codec/pipeline/decoder.js:52-389) and deserializeFrame, for `frames` (0 .. 2^20) consecutive
+ * frames of one channel.  Host pointers, synchronous, like the two calls above; the reference's number model (binary64
+ * operations, binary32 at every typed-array store) always: c1_ctx_set_decode_precision does not apply to them.
+ * "Frame fields", int32 arrays per batch: nbfu[frames] (nBfu); block_modes[frames*3] (the three band modes); sfi[frames*52]
+ * and wl[frames*52] (scale-factor and word-length index per BFU); quantized[frames*512] (BFU after BFU, SPECS_PER_BFU[b]
+ * values each: slot order, where a long band's coefficients also sit). */
+/* deserializeFrame, serialization.js:111-176: units = frames*212 bytes -> frame fields.  Entries the reference leaves unset
+ * -- sfi and wl of BFUs at or above nBfu, quantized of those BFUs and of BFUs with word length 0 -- come back as zeros. */
+int c1_unpack_units(c1_ctx *ctx, const uint8_t *units, int64_t frames, int32_t *nbfu, int32_t *block_modes, int32_t *sfi,
+                    int32_t *wl, int32_t *quantized);
+/* dequantizationStage, decoder.js:52-98: frame fields -> coefs = frames*512 floats (as imdctStage receives them).  Any nBfu
+ * 0..52; for the BFUs below it any wl 0..15 (0: the BFU stays zero) and sfi 0..63 (0: zero, quantization.js:66-68), anything
+ * else is C1_ERR_ARG; entries at or above nBfu are not read.  Mantissas are any int32, not clamped:
+ * Float32((q * SCALE_FACTORS[sfi]) / ((1 << (bits - 1)) - 1)).  A band is long only when its mode is exactly 0 (:82); its
+ * BFUs then sit at BFU_START_LONG, else at BFU_START_SHORT. */
+int c1_dequantize_frames(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi,
+                         const int32_t *wl, const int32_t *quantized, float *coefs);
+/* imdctStage, decoder.js:116-330: coefs = (halo_frames + frames) * 512 floats and block_modes = (halo_frames + frames) * 3
+ * (0 long, any other value short), the first halo_frames (0 or 1) being the stream's previous frame -> bands = frames * 512
+ * floats, low128 | mid128 | high256 per frame (the three arrays qmfSynthesisStage receives).  History: imdctOverlap
+ * (buffers.js:63-67, 256 | 256 | 512 floats) carries into the next frame only its last 16 entries per band, which are the
+ * last 16 IMDCT samples of the band (:227-230, :296-300): a function of the previous frame's coefficients and modes alone.
+ * Without a halo the call starts from a fresh BufferPool's zero overlap. */
+int c1_imdct_batch(c1_ctx *ctx, const float *coefs, int64_t frames, int halo_frames, const int32_t *block_modes, float *bands);
+/* qmfSynthesisStage, decoder.js:349-389: bands = (halo_frames + frames) * 512 floats as above, the first halo_frames (0 or 1)
+ * being the previous frame's -> pcm = frames * 512 samples.  History: qmfDelays (buffers.js:29-33) = highBand, the last 39
+ * samples of the previous frame's high band; midBand, the last 46 interleaved (low + mid) / 2, (low - mid) / 2 inputs of
+ * stage 2; lowBand, the last 46 inputs of stage 1, made from the previous frame's low and mid bands (samples 93..127)
+ * and high band.  All are functions of the previous frame's bands alone; without a halo they are a fresh pool's zeros. */
+int c1_qmf_synthesis_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, float *pcm);
+
 /* ---- stage taps for bring-up and stage-level parity tests (device pointers) ---------------- */
 /* bands: frames*channels*512 floats (low128|mid128|high256 per unit index, before windowing);
  * coefs: same shape (MDCT coefficients as quantizationStage receives them);
