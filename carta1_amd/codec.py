@@ -296,14 +296,17 @@ class Context:
 
     # ---- the single-stage functions the reference exports (codec/index.js:30-35,42), host arrays ----------------
     def quantize(self, coefficients, scale_factor_index, bits_per_sample):
-        """quantize, codec/coding/quantization.js:34-56 -> int32 array"""
+        """quantize, codec/coding/quantization.js:34-56 -> int32 array.  Every int32 bits_per_sample has the reference's
+        meaning; scale_factor_index outside 0..63 is C1_ERR_ARG, a non-int32 argument ValueError"""
+        _check_quantize_args(scale_factor_index, bits_per_sample)
         x = np.ascontiguousarray(coefficients, dtype=np.float32)
         out = np.zeros(x.size, dtype=np.int32)
         capi.check(capi.load().c1_quantize(self._h, x.ctypes.data, x.size, int(scale_factor_index), int(bits_per_sample), out.ctypes.data))
         return out
 
     def dequantize(self, quantized, scale_factor_index, bits_per_sample):
-        """dequantize, quantization.js:65-78 -> float32 array"""
+        """dequantize, quantization.js:65-78 -> float32 array; arguments as for quantize"""
+        _check_quantize_args(scale_factor_index, bits_per_sample)
         q = np.ascontiguousarray(quantized, dtype=np.int32)
         out = np.zeros(q.size, dtype=np.float32)
         capi.check(capi.load().c1_dequantize(self._h, q.ctypes.data, q.size, int(scale_factor_index), int(bits_per_sample), out.ctypes.data))
@@ -514,6 +517,13 @@ def pinned_empty(shape, dtype=np.float32):
 
 
 _default_ctx = None
+
+
+def _check_quantize_args(scale_factor_index, bits_per_sample):
+    """quantize / dequantize take int32 arguments; anything else would be truncated silently on its way through ctypes"""
+    for name, v in (('scale_factor_index', scale_factor_index), ('bits_per_sample', bits_per_sample)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not -2**31 <= int(v) < 2**31:
+            raise ValueError('%s must be an int32, got %r' % (name, v))
 
 
 def _ctx(ctx):

@@ -1360,7 +1360,6 @@ int c1_quantize(c1_ctx *ctx, const float *coefficients, int n, int scale_factor_
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!coefficients || !out))) return fail(C1_ERR_ARG, "quantize: bad arguments");
   if (scale_factor_index < 0 || scale_factor_index > 63) return fail(C1_ERR_ARG, "quantize: scaleFactorIndex %d outside SCALE_FACTORS", scale_factor_index);
-  if (bits_per_sample < 0 || bits_per_sample > 32) return fail(C1_ERR_ARG, "quantize: bitsPerSample %d", bits_per_sample);
   if (n == 0) return C1_OK;
   DeviceScratch ds;
   float *dx; int32_t *dq;
@@ -1378,7 +1377,6 @@ int c1_dequantize(c1_ctx *ctx, const int32_t *quantized, int n, int scale_factor
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!quantized || !out))) return fail(C1_ERR_ARG, "dequantize: bad arguments");
   if (scale_factor_index < 0 || scale_factor_index > 63) return fail(C1_ERR_ARG, "dequantize: scaleFactorIndex %d outside SCALE_FACTORS", scale_factor_index);
-  if (bits_per_sample < 0 || bits_per_sample > 32) return fail(C1_ERR_ARG, "dequantize: bitsPerSample %d", bits_per_sample);
   if (n == 0) return C1_OK;
   DeviceScratch ds;
   int32_t *dq; float *dx;

@@ -245,10 +245,13 @@ int c1_aea_header(const char *title, uint32_t unit_count, int channels, uint8_t 
  *      pointers, synchronous; the arithmetic runs on the device in the reference's own number model.  They serve
  *      applications that import these names; the hot path itself never calls them (it quantizes inside the packing kernel
  *      and transforms inside the analysis kernels). ------------------------------------------------------------------- */
-/* quantize, codec/coding/quantization.js:34-56: out[i] = clamp(((x norm) +- 0.5) | 0), norm = ((1 << (bits - 1)) - 1) /
- * SCALE_FACTORS[sfi]; zeros when bits or sfi is 0 */
+/* quantize, codec/coding/quantization.js:34-56: out[i] = ToInt32(clamp(((x norm) +- 0.5) | 0)), norm = range / SCALE_FACTORS[sfi];
+ * zeros when bits or sfi is 0.  range is the reference's (1 << (bits - 1)) - 1: an int32 shift with the count mod 32, the
+ * "- 1" in binary64, so every int bits_per_sample is accepted with the reference's meaning (range 0 at 1 and 33; at 32 it
+ * is -2147483649, the clamps cross and every output is 2147483647).  Deviation: scale_factor_index outside 0..63 is
+ * C1_ERR_ARG, where the reference reads SCALE_FACTORS[sfi] as undefined and produces NaN or 0. */
 int c1_quantize(c1_ctx *ctx, const float *coefficients, int n, int scale_factor_index, int bits_per_sample, int32_t *out);
-/* dequantize, quantization.js:65-78: Float32((q SCALE_FACTORS[sfi]) / ((1 << (bits - 1)) - 1)) */
+/* dequantize, quantization.js:65-78: Float32((q SCALE_FACTORS[sfi]) / range), range and the argument domain as for c1_quantize */
 int c1_dequantize(c1_ctx *ctx, const int32_t *quantized, int n, int scale_factor_index, int bits_per_sample, float *out);
 /* FFT.fft, codec/transforms/fft.js:14-68: in place on real[n], imag[n], n a power of two; w = (cos, sin)(-2 pi / stride) for
  * stride = 2, 4, .., n as the HOST's Math.cos / Math.sin give them (log2(n) pairs; the reference computes them per call, :37-39) */

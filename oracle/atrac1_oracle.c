@@ -512,17 +512,20 @@ static int32_t to_int32(double x) {
 }
 
 /* quantize, quantization.js:34-56 */
+static double quantize_range(int bits) { /* (1 << (bitsPerSample - 1)) - 1: int32 shift, count mod 32, "- 1" in binary64 */
+  return (double)(int32_t)(1u << (((unsigned)bits - 1u) & 31u)) - 1.0;
+}
 void c1o_quantize_bfu(const float *x, int n, int sfi, int bits, int *out) {
   if (bits == 0 || sfi == 0) {
     memset(out, 0, (size_t)n * sizeof(int));
     return;
   }
-  int range = (1 << (bits - 1)) - 1;
-  double norm = (double)range / C1O_SCALE_FACTORS[sfi];
+  double hi = quantize_range(bits), lo = -hi;
+  double norm = hi / C1O_SCALE_FACTORS[sfi];
   for (int i = 0; i < n; i++) {
     double v = (double)x[i] * norm;
-    int32_t y = to_int32(v + (v >= 0 ? 0.5 : -0.5));
-    out[i] = y > range ? range : y < -range ? -range : y;
+    double y = (double)to_int32(v + (v >= 0 ? 0.5 : -0.5));
+    out[i] = to_int32(y > hi ? hi : y < lo ? lo : y); /* the clamps cross at 32 bits (hi < lo); Int32Array store */
   }
 }
 
@@ -532,8 +535,8 @@ void c1o_dequantize_bfu(const int *q, int n, int sfi, int bits, float *out) {
     memset(out, 0, (size_t)n * sizeof(float));
     return;
   }
-  int range = (1 << (bits - 1)) - 1;
-  for (int i = 0; i < n; i++) out[i] = F32(((double)q[i] * C1O_SCALE_FACTORS[sfi]) / (double)range);
+  double range = quantize_range(bits);
+  for (int i = 0; i < n; i++) out[i] = F32(((double)q[i] * C1O_SCALE_FACTORS[sfi]) / range);
 }
 
 /* ---- encode() closure: encoder.js:438-450 (+ quantizationStage :365-418) ------------ */

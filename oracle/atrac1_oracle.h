@@ -81,6 +81,9 @@ void c1o_mdct_frame(c1o_enc_state *s, float bands[512], const int modes[3], floa
 int c1o_find_scale_factor(const float *x, int n);
 void c1o_allocate(const float coefs[512], const int modes[3], const double biased_sf[64],
                   int *nbfu, int wl[52], int sfi[52]);
+/* quantize / dequantize take every int bit count with the reference's meaning: the range (1 << (bits - 1)) - 1 is formed
+ * as an int32 shift with the count mod 32 and "- 1" in binary64 (-2147483649 at 32 bits, 0 at 1 and 33).  sfi must lie in
+ * 0..63; the reference reads undefined beyond SCALE_FACTORS, the oracle does not model that. */
 void c1o_quantize_bfu(const float *x, int n, int sfi, int bits, int *out);
 void c1o_dequantize_bfu(const int *q, int n, int sfi, int bits, float *out);
 

@@ -207,6 +207,28 @@ def test_decode_arbitrary_bytes_matches_oracle(ctx):
         assert np.array_equal(got[c].view(np.uint32), want[c].view(np.uint32))
 
 
+@pytest.mark.parametrize('modes', [(0, 0, 0), (2, 2, 3)])
+def test_decode_of_sfi0_units_with_negative_mantissas_after_silence(ctx, modes):
+    """a unit whose 52 BFUs all have scale factor index 0 but nonzero word lengths and negative mantissas: the reference's
+    dequantize returns a fresh Float32Array (+0) there, where q * step with step 0 would give -0; PCM bit for bit with
+    the oracle, after silent units and before more of them"""
+    silent, _ = O.encode_stream([np.zeros(3 * 512, np.float32)], fixed_modes=modes)
+    f = O.Fields()
+    f.nbfu = 52
+    f.modes[:] = modes
+    f.wl[:] = [1] * 52                                                 # 2-bit words: 16 + 52 * 10 + 512 * 2 bits fit a unit
+    f.sfi[:] = [0] * 52
+    f.q[:] = [-1 - (i & 1) for i in range(512)]                        # -1, -2: every mantissa negative
+    odd = np.zeros(212, dtype=np.uint8)
+    O.lib().c1o_pack_unit(C.byref(f), odd.ctypes.data_as(C.POINTER(C.c_uint8)))
+    back = O.unpack_unit(odd)
+    assert back.nbfu == 52 and list(back.sfi) == [0] * 52 and all(v < 0 for v in back.q)
+    units = np.concatenate([silent, odd[None], odd[None], silent])
+    want, _ = O.decode_stream(units, 1)
+    got = ctx.decode(units, 1)
+    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32))
+
+
 def test_decode_without_the_step_form_of_dequantize():
     """the reciprocal + two-FMA form of dequantize (quantization.js:65-78) that the per-BFU step form shadows with the
     reference's tables: same PCM, bit for bit, on arbitrary units and on an encoded stream"""
