@@ -152,10 +152,12 @@ constexpr int kRunDefault = 64;
 // latency (a 64-frame mono push: 0.41 ms, of which the walk is 0.3) while the rest of the machine idles; the batch is
 // spread over up to 2 048 waves instead, and a run is never shorter than 4 frames (each pays one warm-up frame).
 // A function of the batch alone: every kernel of a call, and the run lists they hand each other, use the same length.
+// A forced run is clamped to at least 4 frames too: the speculative path's deferred-run slots and open-scale-factor
+// masks share one allocation (c1_api.hip, ensure_workspace / bind_defer) sized for at most one slot per 4 units.
 inline int c1k_pick_run(int64_t frames, int channels, int slots) {
   static const int forced = getenv("C1_RUN_FRAMES") ? atoi(getenv("C1_RUN_FRAMES")) : 0;
   (void)slots;
-  if (forced > 0) return forced;
+  if (forced > 0) return forced < 4 ? 4 : forced;
   const int64_t units = frames * channels;
   if (units >= (int64_t)kRunDefault * 2048) return kRunDefault;
   const int run = (int)((units + 2047) / 2048);

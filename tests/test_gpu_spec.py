@@ -42,10 +42,11 @@ def spec_stages(ctx, chans, modes=(0, 0, 0)):
 
 
 def run_length(frames, channels):
-    """c1k_pick_run (c1_internal.h): 64-frame runs, shorter ones for small batches (latency of a streaming push)"""
+    """c1k_pick_run (c1_internal.h): 64-frame runs, shorter ones for small batches (latency of a streaming push); a forced
+    run is never shorter than 4 frames either"""
     import os
     if int(os.environ.get('C1_RUN_FRAMES', '0')) > 0:
-        return int(os.environ['C1_RUN_FRAMES'])
+        return max(4, int(os.environ['C1_RUN_FRAMES']))
     units = frames * channels
     return 64 if units >= 64 * 2048 else max(4, -(-units // 2048))
 
