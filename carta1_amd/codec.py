@@ -342,6 +342,32 @@ class Context:
         capi.check(capi.load().c1_mdct_batch(self._h, b.ctypes.data, frames, halo_frames, m.ctypes.data, co.ctypes.data, bw.ctypes.data))
         return co, bw
 
+    def select_block_modes(self, bands, threshold=1.0, halo_frames=0):
+        """blockSelectorStage's detection branch, encoder.js:111-152: bands float32 [(halo_frames + frames), 512] as qmf_analysis
+        returns them (the first halo_frames rows: the last frame detection ran on) -> int32 [frames, 3], per band 0 or
+        2 | 2 | 3 when its transient score > threshold (options.transientThresholdLow, any float)"""
+        b = np.ascontiguousarray(bands, dtype=np.float32).reshape(-1, 512)
+        frames = b.shape[0] - halo_frames
+        out = np.zeros((max(frames, 0), 3), dtype=np.int32)
+        capi.check(capi.load().c1_select_block_modes(self._h, b.ctypes.data, frames, halo_frames, float(threshold), out.ctypes.data))
+        return out
+
+    def quantize_frames(self, coefs, block_modes, options=None):
+        """quantizationStage, encoder.js:365-418: coefs float32 [frames, 512] as mdct returns them, block_modes int [frames, 3]
+        (0 long, anything else short) -> the dict unpack_units returns (block_modes echoed), so that dequantize_frames takes
+        it as it stands.  options: EncoderOptions; only allocationBias (its biased table, as encode uses it) is read."""
+        c = np.ascontiguousarray(coefs, dtype=np.float32).reshape(-1, 512)
+        frames = c.shape[0]
+        m = np.ascontiguousarray(block_modes, dtype=np.int32).reshape(-1, 3)
+        if m.shape[0] != frames:
+            raise ValueError('block_modes must hold three entries per frame of coefs')
+        opts = (options or EncoderOptions()).to_c()
+        out = {k: np.zeros((frames,) + shape, dtype=np.int32) for k, shape in self.FIELD_SHAPES if k != 'block_modes'}
+        capi.check(capi.load().c1_quantize_frames(self._h, c.ctypes.data, frames, m.ctypes.data, C.byref(opts), out['nbfu'].ctypes.data,
+                                                   out['sfi'].ctypes.data, out['wl'].ctypes.data, out['quantized'].ctypes.data))
+        out['block_modes'] = m.copy()
+        return {k: out[k] for k, _ in self.FIELD_SHAPES}
+
     # ---- the decoder's pipeline stages (codec/pipeline/decoder.js:52-389, serialization.js:111-176), one channel ------------
     FIELD_SHAPES = (('nbfu', ()), ('block_modes', (3,)), ('sfi', (52,)), ('wl', (52,)), ('quantized', (512,)))
 

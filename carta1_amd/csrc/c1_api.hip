@@ -1583,6 +1583,77 @@ int c1_qmf_synthesis_batch(c1_ctx *ctx, const float *bands, int64_t frames, int 
   return C1_OK;
 }
 
+// ---- the encoder's block selection and quantization stages on their own (codec/pipeline/encoder.js:111-152, :365-418) ----
+
+int c1_select_block_modes(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, double threshold, int32_t *block_modes) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (halo_frames < 0 || halo_frames > 1) return fail(C1_ERR_ARG, "select block modes: halo_frames must be 0 or 1, got %d", halo_frames);
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "select block modes: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!bands || !block_modes) return fail(C1_ERR_ARG, "select block modes: NULL argument");
+  DeviceScratch ds;
+  float *db, *dm; int32_t *dmodes;
+  const size_t n = (size_t)frames, all = (size_t)(frames + halo_frames);
+  if ((rc = ds.alloc(&db, 512 * all)) || (rc = ds.alloc(&dm, 256 * all)) || (rc = ds.alloc(&dmodes, 3 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(db, bands, 512 * all * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_block_modes_from_bands(ctx->d_tables, db, frames, halo_frames, threshold, dm, dmodes, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(block_modes, dmodes, 3 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const int32_t *block_modes, const c1_encode_options *opts,
+                       int32_t *nbfu, int32_t *sfi, int32_t *wl, int32_t *quantized) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!opts) return fail(C1_ERR_ARG, "quantize frames: options are NULL");
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "quantize frames: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!coefs || !block_modes || !nbfu || !sfi || !wl || !quantized) return fail(C1_ERR_ARG, "quantize frames: NULL argument");
+  // the stage reads allocationBias alone: the threshold and the fixed modes of `opts` are not looked at
+  c1_encode_options o = *opts;
+  o.transient_threshold = 1.0;
+  o.fixed_block_modes[0] = o.fixed_block_modes[1] = o.fixed_block_modes[2] = -1;
+  if ((rc = upload_opts(ctx, &o))) return rc;
+  DeviceScratch ds;
+  float *dc; int32_t *dmodes, *dn, *ds_, *dw, *dq; uint8_t *dside, *dalloc, *dcand; uint32_t *dwork;
+  const size_t n = (size_t)frames;
+  if ((rc = ds.alloc(&dc, 512 * n)) || (rc = ds.alloc(&dmodes, 3 * n)) || (rc = ds.alloc(&dside, kSideBytes * n)) ||
+      (rc = ds.alloc(&dalloc, kAllocBytes * n)) || (rc = ds.alloc(&dcand, (size_t)kCandidateBytes * n)) ||
+      (rc = ds.alloc(&dwork, 4 + 8 * n)) || (rc = ds.alloc(&dn, n)) || (rc = ds.alloc(&ds_, 52 * n)) || (rc = ds.alloc(&dw, 52 * n)) ||
+      (rc = ds.alloc(&dq, 512 * n))) return rc;
+  HIP_TRY(hipMemcpyAsync(dc, coefs, 512 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dmodes, block_modes, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_stage_scale_factors(ctx->d_tables, dc, dmodes, frames, dside, ctx->stream);
+  // allocateBits as the encoder runs it (c1k_launch_allocate), on per-call scratch: counts, then 7 work-list entries and one
+  // selection-list entry per frame (the layout c1_alloc_bounds_device gives the context's workspace)
+  C1EncodeLaunch L;
+  memset(&L, 0, sizeof L);
+  L.channels = 1;
+  L.frames = frames;
+  L.tables = ctx->d_tables;
+  L.opts = ctx->d_opts;
+  L.side = dside;
+  L.alloc = dalloc;
+  L.cand = dcand;
+  L.work_count = dwork;
+  L.work_list = dwork + 4;
+  L.sel_list = dwork + 4 + 7 * n;
+  c1k_launch_allocate(L, ctx->stream);
+  c1k_launch_stage_fields(ctx->d_tables, dc, dmodes, dside, dalloc, frames, dn, ds_, dw, dq, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(nbfu, dn, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(sfi, ds_, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(wl, dw, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(quantized, dq, 512 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 int c1_pack_spec_tap_device(c1_ctx *ctx, const float *coefs, const float *eps, const uint8_t *side, const uint8_t *alloc,
                             int64_t units, int all_long, uint8_t *units_out, uint32_t *lists) {
   CTX_GUARD(ctx);

@@ -782,4 +782,24 @@ __device__ __forceinline__ void mdct_mixed_r4(const float *stage, float2 *z, flo
   }
 }
 
+// quantizeRange: the reference's (1 << (bitsPerSample - 1)) - 1 -- an int32 shift with the count taken mod 32, then "- 1" in
+// binary64.  Every bit count has a meaning there: 1 and 33 give 0, 32 gives -2147483649 (so quantize's clamps cross and
+// every output is ToInt32(-2147483649) = 2147483647, and dequantize divides by a negative range).
+__device__ __forceinline__ double quantize_range(int bits) {
+  return (double)(int32_t)(1u << (((unsigned)bits - 1u) & 31u)) - 1.0;
+}
+
+// quantize (quantization.js:34-56) of the coefficient *x into *out: 0 when bitsPerSample or scaleFactorIndex is 0 (:38-41), else
+// the clamp in binary64 in the reference's order (y > hi ? hi : y < lo ? lo : y) with ToInt32 applied by the Int32Array store,
+// so +-Inf and NaN give 0.  k_quantize_one and the quantization stage (c1_k_encode_stages.hip) share it; the hot path
+// quantizes inside k_pack.  *x is read only when the BFU codes.
+__device__ __forceinline__ void quantize_into(const C1DevTables *tables, const float *x, int sfi, int bits, int32_t *out) {
+  if (bits == 0 || sfi == 0) { *out = 0; return; }
+  const double hi = quantize_range(bits), lo = -hi;
+  const double norm = hi / tables->scale_factors[sfi & 63];
+  const double v = (double)*x * norm;
+  const double y = (double)to_int32(v + (v >= 0 ? 0.5 : -0.5));
+  *out = to_int32(y > hi ? hi : (y < lo ? lo : y));
+}
+
 }  // namespace

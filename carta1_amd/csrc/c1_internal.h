@@ -198,6 +198,17 @@ void c1k_launch_imdct_frames(const C1DevTables *tables, const float *coefs, cons
                              float *bands, hipStream_t stream);
 void c1k_launch_qmf_synthesis_frames(const C1DevTables *tables, const float *bands, int64_t frames, int halo, float *pcm,
                                      hipStream_t stream);
+// the encoder's block selection and quantization stages on their own (c1_k_encode_stages.hip), one channel; device pointers.
+// bands point at frame -halo; mags: (halo + frames) * 256 floats of scratch; modes: frames * 3 int32
+void c1k_launch_block_modes_from_bands(const C1DevTables *tables, const float *bands, int64_t frames, int halo, double threshold,
+                                       float *mags, int32_t *modes, hipStream_t stream);
+// findScaleFactor per BFU -> side records (kSideBytes per frame) for c1k_launch_allocate
+void c1k_launch_stage_scale_factors(const C1DevTables *tables, const float *coefs, const int32_t *modes, int64_t frames, uint8_t *side,
+                                    hipStream_t stream);
+// allocation + side records -> frame fields (nbfu[frames], sfi / wl [frames * 52], q [frames * 512])
+void c1k_launch_stage_fields(const C1DevTables *tables, const float *coefs, const int32_t *modes, const uint8_t *side,
+                             const uint8_t *alloc, int64_t frames, int32_t *nbfu, int32_t *sfi, int32_t *wl, int32_t *q,
+                             hipStream_t stream);
 // the single-stage functions the reference exports next to encode()/decode() (c1_k_stages.hip); device pointers
 void c1k_launch_quantize_one(const C1DevTables *tables, const float *x, int n, int sfi, int bits, int32_t *out, hipStream_t stream);
 void c1k_launch_dequantize_one(const C1DevTables *tables, const int32_t *q, int n, int sfi, int bits, float *out, hipStream_t stream);

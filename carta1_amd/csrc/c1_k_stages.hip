@@ -8,24 +8,11 @@
 
 namespace {
 
-// quantizeRange: the reference's (1 << (bitsPerSample - 1)) - 1 -- an int32 shift with the count taken mod 32, then "- 1" in
-// binary64.  Every bit count has a meaning there: 1 and 33 give 0, 32 gives -2147483649 (so quantize's clamps cross and
-// every output is ToInt32(-2147483649) = 2147483647, and dequantize divides by a negative range).
-__device__ __forceinline__ double quantize_range(int bits) {
-  return (double)(int32_t)(1u << (((unsigned)bits - 1u) & 31u)) - 1.0;
-}
-
-// quantization.js:34-56: the clamp in binary64 in the reference's order (y > hi ? hi : y < lo ? lo : y), the Int32Array store
-// applies ToInt32 to the clamped value
+// quantization.js:34-56 (quantize_into, c1_device.h)
 __global__ void k_quantize_one(const C1DevTables *tables, const float *__restrict__ x, int n, int sfi, int bits, int32_t *__restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (bits == 0 || sfi == 0) { out[i] = 0; return; }
-  const double hi = quantize_range(bits), lo = -hi;
-  const double norm = hi / tables->scale_factors[sfi & 63];
-  const double v = (double)x[i] * norm;
-  const double y = (double)to_int32(v + (v >= 0 ? 0.5 : -0.5));
-  out[i] = to_int32(y > hi ? hi : (y < lo ? lo : y));
+  quantize_into(tables, x + i, sfi, bits, out + i);
 }
 
 // quantization.js:65-78

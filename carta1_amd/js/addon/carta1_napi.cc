@@ -651,6 +651,49 @@ napi_value UnpackUnits(napi_env env, napi_callback_info info) {   // (ctx, Uint8
   for (int i = 0; i < 5; i++) NAPI_OK(napi_set_element(env, arr, i, out[i]));
   return arr;
 }
+napi_value SelectBlockModes(napi_env env, napi_callback_info info) {  // (ctx, Float32Array bands incl. halo, haloFrames, threshold) -> Int32Array modes
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx; void *d; size_t n; int32_t halo = 0; double threshold = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &n)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  NAPI_OK(napi_get_value_double(env, argv[3], &threshold));
+  if (n % 512 || halo < 0 || halo > 1 || (size_t)halo > n / 512) { napi_throw_type_error(env, nullptr, "selectBlockModes: whole frames of 512 band samples, halo 0 or 1"); return nullptr; }
+  const int64_t frames = (int64_t)(n / 512) - halo;
+  napi_value ab, out;
+  void *m;
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)frames * 3 * 4 + 4, &m, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)frames * 3, ab, 0, &out));
+  const int rc = c1_select_block_modes(ctx, static_cast<const float *>(d), frames, halo, threshold, static_cast<int32_t *>(m));
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+napi_value QuantizeFrames(napi_env env, napi_callback_info info) {  // (ctx, Float32Array coefs, Int32Array modes, Float64Array(68) options) -> {nbfu, sfi, wl, quantized}
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx; void *c, *m; size_t n, nm;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &c, &n) ||
+      !get_typed(env, argv[2], napi_int32_array, &m, &nm)) return nullptr;
+  c1_encode_options o;
+  if (!get_options(env, argv[3], &o)) return nullptr;
+  if (n % 512 || nm != 3 * (n / 512)) { napi_throw_type_error(env, nullptr, "quantizeFrames: whole frames of 512 coefficients and three block modes per frame"); return nullptr; }
+  const size_t frames = n / 512, per[4] = {1, 52, 52, 512};
+  static const char *const names[4] = {"nbfu", "sfi", "wl", "quantized"};
+  napi_value obj, out[4];
+  void *p[4];
+  for (int i = 0; i < 4; i++) {
+    napi_value ab;
+    NAPI_OK(napi_create_arraybuffer(env, frames * per[i] * 4 + 4, &p[i], &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, frames * per[i], ab, 0, &out[i]));
+  }
+  const int rc = c1_quantize_frames(ctx, static_cast<const float *>(c), (int64_t)frames, static_cast<const int32_t *>(m), &o,
+                                    static_cast<int32_t *>(p[0]), static_cast<int32_t *>(p[1]), static_cast<int32_t *>(p[2]),
+                                    static_cast<int32_t *>(p[3]));
+  if (rc) return throw_c1(env, rc);
+  NAPI_OK(napi_create_object(env, &obj));
+  for (int i = 0; i < 4; i++) NAPI_OK(napi_set_named_property(env, obj, names[i], out[i]));
+  return obj;
+}
 napi_value DequantizeFrames(napi_env env, napi_callback_info info) {  // (ctx, Int32Array nbfu, blockModes, sfi, wl, quantized) -> Float32Array coefs
   napi_value argv[6];
   if (!get_args(env, info, 6, argv)) return nullptr;
@@ -722,6 +765,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fft", nullptr, Fft, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"qmfAnalysis", nullptr, QmfAnalysis, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"mdctFromBands", nullptr, MdctFromBands, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"selectBlockModes", nullptr, SelectBlockModes, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"quantizeFrames", nullptr, QuantizeFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"unpackUnits", nullptr, UnpackUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"dequantizeFrames", nullptr, DequantizeFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"imdct", nullptr, Imdct, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,6 +8,7 @@ export class BufferPool {
     this.decoderStream = null // c1_dec_stream
     this.encoderOptionsKey = null
     this.qmfHistory = null // qmfAnalysisStage on its own: the previous frame's PCM (the QMF delay lines are made of it)
+    this.transientBands = null // blockSelectorStage on its own: the bands of the last frame detection ran on (its magnitudes are transientDetection)
     this.mdctPreviousBands = null // mdctStage on its own: the previous frame's band samples (mdctOverlap is made of their tails)
     this.imdctPrevious = null // imdctStage on its own: the previous frame's coefficients and modes (imdctOverlap is made of them)
     this.synthesisPreviousBands = null // qmfSynthesisStage on its own: the previous frame's bands (qmfDelays are made of them)

@@ -5,7 +5,7 @@
 // same fields object: { nBfu, scaleFactorIndices, wordLengthIndices, quantizedCoefficients, blockModes }.
 import { EncoderOptions } from '../core/options.js'
 import { BufferPool } from '../core/buffers.js'
-import { SAMPLES_PER_FRAME } from '../core/constants.js'
+import { SAMPLES_PER_FRAME, SCALE_FACTORS, SPECS_PER_BFU } from '../core/constants.js'
 import { deserializeFrame } from '../io/serialization.js'
 import { native, context } from '../native.js'
 import { throwError } from '../utils.js'
@@ -69,5 +69,58 @@ export function mdctStage(stageContext) {
     // the reference windows the band arrays it was given in place and hands the same arrays on (encoder.js:244,292,314)
     bands[0].set(windowed.subarray(0, 128)); bands[1].set(windowed.subarray(128, 256)); bands[2].set(windowed.subarray(256, 512))
     return { bands, coefficients, blockModes, originalFrame }
+  }
+}
+
+// blockSelectorStage(context) and quantizationStage(context): the other two stages encode() composes (codec/pipeline/encoder.js:111,
+// :365), with the reference's call and return shapes, so that pipe(context, qmfAnalysisStage, blockSelectorStage, mdctStage,
+// quantizationStage) is encode() again.  The detection history the reference keeps -- transientDetection, performFFT's
+// magnitudes of the last frame detection ran on -- is a function of that frame's bands: the pool keeps a copy of them and the
+// device rebuilds the magnitudes (include/carta1_hip.h, c1_select_block_modes).
+export function blockSelectorStage(stageContext) {
+  const bufferPool = (stageContext && stageContext.bufferPool) || throwError('blockSelectorStage: bufferPool is required')
+  const options = (stageContext && stageContext.options) || throwError('blockSelectorStage: options is required')
+  return (input) => {
+    const { bands } = input
+    if (options.fixedBlockModes) return { bands, blockModes: options.fixedBlockModes }   // the history stays as it is (:130-132)
+    const prev = bufferPool.transientBands
+    const all = new Float32Array((prev ? 2 : 1) * 512)
+    const at = prev ? 512 : 0
+    if (prev) all.set(prev, 0)
+    all.set(bands[0], at); all.set(bands[1], at + 128); all.set(bands[2], at + 256)
+    const modes = native().selectBlockModes(context(), all, prev ? 1 : 0, options.transientThresholdLow)
+    // a copy: mdctStage windows the band arrays in place right after this stage
+    bufferPool.transientBands = all.slice(at, at + 512)
+    return { bands, blockModes: Array.from(modes) }
+  }
+}
+
+// allocationBias's table (bitallocation.js:46-61) in the packed options the addon reads; threshold and modes are not read
+function quantizationOptions(options) {
+  if (typeof options.toNative === 'function') return options.toNative()
+  const out = new Float64Array(68)
+  const bias = options.allocationBias === undefined ? 1 : options.allocationBias
+  for (let i = 0; i < 64; i++) out[i] = bias === 1 ? SCALE_FACTORS[i] : Math.pow(SCALE_FACTORS[i], bias)
+  out[64] = 1
+  out[65] = out[66] = out[67] = -1
+  return out
+}
+
+export function quantizationStage(stageContext) {
+  const options = (stageContext && stageContext.options) || throwError('quantizationStage: options is required')
+  return (input) => {
+    const { coefficients, blockModes } = input
+    const coefs = coefficients instanceof Float32Array ? coefficients : Float32Array.from(coefficients)
+    const f = native().quantizeFrames(context(), coefs, Int32Array.from(blockModes), quantizationOptions(options))
+    const nBfu = f.nbfu[0]
+    const quantizedCoefficients = []
+    for (let b = 0, at = 0; b < nBfu; at += SPECS_PER_BFU[b], b++) quantizedCoefficients.push(f.quantized.slice(at, at + SPECS_PER_BFU[b]))
+    return {
+      nBfu,
+      scaleFactorIndices: f.sfi.slice(0, nBfu),
+      wordLengthIndices: f.wl.slice(0, nBfu),
+      quantizedCoefficients,
+      blockModes,
+    }
   }
 }

@@ -298,6 +298,27 @@ int c1_imdct_batch(c1_ctx *ctx, const float *coefs, int64_t frames, int halo_fra
  * and high band.  All are functions of the previous frame's bands alone; without a halo they are a fresh pool's zeros. */
 int c1_qmf_synthesis_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, float *pcm);
 
+/* The encoder's two middle-to-last pipeline stages (codec/pipeline/encoder.js:111-152, :365-418), which with
+ * c1_qmf_analysis_batch (qmfAnalysisStage) and c1_mdct_batch (mdctStage) make up encode() (:438-450).  For `frames` (0 .. 2^20)
+ * consecutive frames of one channel; host pointers, synchronous; the reference's number model always.  Both return C1_ERR_ARG
+ * for a bad halo, a NULL pointer or NULL opts; frames == 0 writes nothing. */
+/* blockSelectorStage, encoder.js:111-152 (detection branch).  bands = (halo_frames + frames) * 512 floats, low128 | mid128 |
+ * high256 as qmfAnalysisStage returns them (unwindowed); halo_frames 0 or 1: the bands whose magnitudes are the pool's
+ * transientDetection (the last frame detection ran on), none = a fresh pool's zero magnitudes.  threshold =
+ * options.transientThresholdLow, any double (NaN: nothing is transient).  block_modes = frames * 3 int32: per band 0, or
+ * 2 | 2 | 3 when its score > threshold (:143). */
+int c1_select_block_modes(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, double threshold,
+                          int32_t *block_modes);
+/* quantizationStage, encoder.js:365-418.  coefs = frames * 512 floats as mdctStage returns them, any bit pattern;
+ * block_modes = frames * 3, any int32 (0 long, anything else short); opts->biased_scale_factors = allocationBias's table
+ * (threshold and fixed modes are not read).  Out: frame fields as c1_unpack_units writes them -- nbfu, sfi and wl of the
+ * BFUs below nBfu (sfi as findScaleFactor gave it, also where wl is 0), quantized; zeros at and above nBfu and where wl is 0.
+ * findScaleFactor's maximum skips NaN (signalling or quiet), so +-Inf gives 63 and -0 and denormals give 0; quantize gives 0
+ * for +-Inf and NaN.  allocateBits' fallback (:132-139, no finite total) gives nBfu 20 with every index 0.  The bit
+ * allocation runs on scratch of the call, not on the context's encode workspace. */
+int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const int32_t *block_modes,
+                       const c1_encode_options *opts, int32_t *nbfu, int32_t *sfi, int32_t *wl, int32_t *quantized);
+
 /* ---- stage taps for bring-up and stage-level parity tests (device pointers) ---------------- */
 /* bands: frames*channels*512 floats (low128|mid128|high256 per unit index, before windowing);
  * coefs: same shape (MDCT coefficients as quantizationStage receives them);
