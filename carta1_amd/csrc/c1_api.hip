@@ -323,7 +323,9 @@ int build_table_fields(const c1_encode_options &o, C1DevEncOpts *d) {
       d->rank[s * 16 + wl] = (uint16_t)(1 + (it - uniq.begin()));
     }
   // Is the order of the ranks the order of an integer form?  (bias 1: priority = 2^(s/3-21) * {0.875 | 2^-(wl+2)}
-  // -> 2s-1 for wl = 0 and 2s - 6wl - 12 for wl >= 1.)  Search small coefficients; ties must match too.
+  // -> 2s-1 for wl = 0 and 2s - 6wl - 12 for wl >= 1, i.e. A = 2, B = 6, C = 5 in the form below: the wl = 0 term
+  // sits above the wl = 1 term of the same sfi, so C is searched on both sides of zero.)  Search small coefficients;
+  // ties must match too.
   d->rank_affine = 0;
   {
     std::vector<int> order;                       // (s, wl) pairs sorted by rank
@@ -332,7 +334,7 @@ int build_table_fields(const c1_encode_options &o, C1DevEncOpts *d) {
     std::sort(order.begin(), order.end(), [&](int x, int y) { return d->rank[x] < d->rank[y]; });
     for (int A = 1; A <= 12 && !d->rank_affine; A++)
       for (int B = 1; B <= 36 && !d->rank_affine; B++)
-        for (int C = -2 * B; C <= 0 && !d->rank_affine; C++) {
+        for (int C = -2 * B; C <= 2 * B && !d->rank_affine; C++) {
           auto key = [&](int idx) { const int s = idx >> 4, wl = idx & 15; return wl == 0 ? A * s + C : A * s - B * wl - B; };
           bool ok = true;
           int lo = key(order[0]), hi = lo;
@@ -934,6 +936,16 @@ int c1_table_fast_paths(int *scale_factor_bits, int *dequant_reciprocal) {
   build_device_tables(t, d.get());
   if (scale_factor_bits) *scale_factor_bits = d->sf_fast;
   if (dequant_reciprocal) *dequant_reciprocal = d->dq_fast + d->dq_step;
+  return C1_OK;
+}
+
+int c1_alloc_rank_form(const c1_encode_options *opts, int *affine, int *coef) {
+  if (!opts) return fail(C1_ERR_ARG, "opts is NULL");
+  std::unique_ptr<C1DevEncOpts> d(new C1DevEncOpts);
+  const int rc = build_table_fields(*opts, d.get());
+  if (rc) return rc;
+  if (affine) *affine = d->rank_affine;
+  if (coef) { coef[0] = d->rank_a; coef[1] = d->rank_b; coef[2] = d->rank_c; coef[3] = d->rank_off; }
   return C1_OK;
 }
 

@@ -97,6 +97,10 @@ int c1_default_encode_options(c1_encode_options *out);
  *                     2 = moreover, after the store to the Float32 array, equal to q * RN(SF * RN(1 / range)) for every
  *                     (word length, scale factor, q): one product per BFU and one per coefficient */
 int c1_table_fast_paths(int *scale_factor_bits, int *dequant_reciprocal);
+/* Diagnostics (host only): how the bit allocation will order heap priorities for opts' biased table.  affine = 1: by
+ * the integer form A*sfi + C (word length 0) / A*sfi - B*(wl + 1) (wl >= 1) plus an offset, coef = {A, B, C, offset};
+ * affine = 0: by the table of ranks of the Float32 priorities (coef zero).  Fails as encoding would on a bad table. */
+int c1_alloc_rank_form(const c1_encode_options *opts, int *affine, int *coef);
 
 /* ---- contexts ------------------------------------------------------------------------- */
 int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stream */, c1_ctx **out);

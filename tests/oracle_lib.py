@@ -127,13 +127,14 @@ def biased_table(bias):
     return out
 
 
-def make_options(fixed_modes=None, bias=1.0, threshold=1.0):
+def make_options(fixed_modes=None, bias=1.0, threshold=1.0, biased=None):
+    """biased: an explicit allocationBias table (64 doubles) in place of biased_table(bias)"""
     o = Options()
     fm = fixed_modes if fixed_modes is not None else (-1, -1, -1)
     for i in range(3):
         o.fixed_modes[i] = int(fm[i])
     o.threshold = float(threshold)
-    b = biased_table(bias)
+    b = biased_table(bias) if biased is None else biased
     for i in range(64):
         o.biased_sf[i] = b[i]
     return o
@@ -176,14 +177,14 @@ def gen_pinkT(seed, n):
     return out
 
 
-def encode_stream(channels, fixed_modes=None, bias=1.0, threshold=1.0, states=None):
+def encode_stream(channels, fixed_modes=None, bias=1.0, threshold=1.0, states=None, biased=None):
     """channels: list of float32 arrays of equal length (a multiple of 512).  Returns units
     uint8 [frames*nch, 212] interleaved L,R and the final states."""
     nch = len(channels)
     chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
     frames = len(chans[0]) // 512
     assert all(len(c) == frames * 512 for c in chans)
-    o = make_options(fixed_modes, bias, threshold)
+    o = make_options(fixed_modes, bias, threshold, biased)
     st = states if states is not None else (EncState * nch)()
     units = np.zeros((frames * nch, 212), dtype=np.uint8)
     ptrs = (C.POINTER(C.c_float) * nch)(*[_fp(c) for c in chans])

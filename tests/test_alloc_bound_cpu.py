@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import option_domain_lib as OD
 
 SPECS = [8, 8, 8, 8, 4, 4, 4, 4, 8, 8, 8, 8, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 7, 7, 7, 7, 9, 9, 9, 9, 10, 10, 10, 10,
          12, 12, 12, 12, 12, 12, 12, 12, 20, 20, 20, 20, 20, 20, 20, 20]
@@ -39,7 +40,8 @@ def _sift(hi, hp, i, n):                                  # siftDown, bitallocat
     hi[i], hp[i] = iv, pv
 
 
-def distribute(n, rem, bsf, sfi):                         # distributeBitsRDO, :203-281
+def distribute(n, rem, bsf, sfi, ties=None):             # distributeBitsRDO, :203-281
+    """ties: a one-element list, if given, counts the spending steps whose root priority equals a child's"""
     wl, hi, hp = [0] * n, [], []
     for b in range(n):
         if sfi[b]:
@@ -55,6 +57,8 @@ def distribute(n, rem, bsf, sfi):                         # distributeBitsRDO, :
         if hs > 0:
             _sift(hi, hp, 0, hs)
     while rem > 0 and hs > 0:
+        if ties is not None:
+            ties[0] += (hs > 1 and hp[1] == hp[0]) or (hs > 2 and hp[2] == hp[0])
         b = hi[0]
         cur = wl[b]
         cost = DB[cur] * SPECS[b]
@@ -137,12 +141,12 @@ def families(rng, per):
     return out
 
 
-@pytest.mark.parametrize('bias', [1.0, 2.0, 0.5])
+@pytest.mark.parametrize('bias', [1.0, 2.0, 0.5] + [float(b) for b in OD.fixture()['biases'] if float(b) not in (1.0, 2.0, 0.5)])
 def test_bound_never_exceeds_the_total_and_pruning_keeps_the_winner(bias):
     L = O.lib()
     L.c1o_scale_factors.restype = C.POINTER(C.c_double)
     SF = np.ctypeslib.as_array(L.c1o_scale_factors(), shape=(64,)).copy()
-    bsf = np.array(O.biased_table(bias), dtype=np.float64)
+    bsf = OD.biased(bias)                                 # the reference's own table
     rng = np.random.RandomState(int(100 * bias))
     heaps_all = heaps_pruned = 0
     for sfi in families(rng, 6):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import option_domain_lib as OD
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +48,8 @@ def _families(rng, units):
     return np.concatenate(out).astype(np.uint8)
 
 
-@pytest.mark.parametrize('bias', [0.5, 1.0, 2.0, 1.37])
+@pytest.mark.parametrize('bias', [0.5, 1.0, 2.0, 1.37] + [float(b) for b in OD.fixture()['biases']
+                                                         if float(b) not in (0.5, 1.0, 2.0, 1.37)])
 def test_bounds_hold_and_the_pruned_choice_is_the_brute_force_minimum(ctx, bias):
     import torch
     import carta1_amd as c1
@@ -57,7 +59,7 @@ def test_bounds_hold_and_the_pruned_choice_is_the_brute_force_minimum(ctx, bias)
     side[:, :52] = _families(rng, units)
     d_side = torch.from_numpy(side).cuda()
     d_out = torch.zeros((units, 16), dtype=torch.float64, device='cuda')
-    opts = c1.EncoderOptions({'allocationBias': bias, 'fixedBlockModes': [0, 0, 0]}, biased_table=O.biased_table(bias))
+    opts = c1.EncoderOptions({'allocationBias': bias, 'fixedBlockModes': [0, 0, 0]}, biased_table=OD.biased(bias))
     ctx.alloc_bounds_device(d_side.data_ptr(), units, d_out.data_ptr(), opts)
     ctx.synchronize()
     out = d_out.cpu().numpy()

@@ -12,6 +12,7 @@ import pytest
 
 import encoder_stages_golden as EG
 import oracle_lib as O
+import option_domain_lib as OD
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -226,11 +227,11 @@ def _oracle_fields(coefs, modes, biased):
     return {'nbfu': nbfu, 'block_modes': modes, 'sfi': sfi, 'wl': wl, 'quantized': q}
 
 
-@pytest.mark.parametrize('bias', [0.5, 1.0, 2.0])
+@pytest.mark.parametrize('bias', [0.5, 1.0, 2.0] + [float(b) for b in OD.fixture()['biases'] if float(b) not in (0.5, 1.0, 2.0)])
 def test_random_coefficients_against_oracle(ctx, bias):
-    frames = 40_000                                             # 120 k frames over the three biases
+    frames = 40_000                                             # 440 k frames over the eleven biases
     coefs, modes = _coef_mixture(frames, int(bias * 10))
-    biased = CASES['coefs_b%g' % bias]['biased']
+    biased = CASES['coefs_b%g' % bias]['biased'] if bias in (0.5, 1.0, 2.0) else OD.biased(bias)
     got = ctx.quantize_frames(coefs, modes, options(bias, biased))
     assert_fields(got, _oracle_fields(coefs, modes, biased), 'bias %g' % bias)
 
