@@ -368,6 +368,21 @@ class Context:
         out['block_modes'] = m.copy()
         return {k: out[k] for k, _ in self.FIELD_SHAPES}
 
+    def pack_units(self, fields):
+        """serializeFrame, serialization.js:41-98, over consecutive frames of one channel: a dict of frame fields as
+        unpack_units and quantize_frames return it (FIELD_SHAPES) -> uint8 [frames, 212].  nbfu must be 0..52; every other
+        value is any int32 and takes the reference's meaning (include/carta1_hip.h, c1_pack_units)."""
+        frames = int(np.asarray(fields['nbfu']).size)
+        arrs = []
+        for k, shape in self.FIELD_SHAPES:
+            a = np.ascontiguousarray(fields[k], dtype=np.int32)
+            if a.size != frames * int(np.prod(shape, dtype=np.int64)):
+                raise ValueError('%s must hold %s entries per frame' % (k, shape or 1))
+            arrs.append(a)
+        out = np.zeros((frames, 212), dtype=np.uint8)
+        capi.check(capi.load().c1_pack_units(self._h, frames, *[a.ctypes.data for a in arrs], out.ctypes.data))
+        return out
+
     # ---- the decoder's pipeline stages (codec/pipeline/decoder.js:52-389, serialization.js:111-176), one channel ------------
     FIELD_SHAPES = (('nbfu', ()), ('block_modes', (3,)), ('sfi', (52,)), ('wl', (52,)), ('quantized', (512,)))
 

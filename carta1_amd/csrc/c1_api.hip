@@ -361,8 +361,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units"};
 
 }  // namespace
 
@@ -423,8 +423,8 @@ struct c1_ctx {
   bool profiling = false;
   std::vector<Timing> timings;
   std::vector<hipEvent_t> event_pool;
-  double ms[K_KINDS] = {0, 0, 0, 0, 0};
-  int launches[K_KINDS] = {0, 0, 0, 0, 0};
+  double ms[K_KINDS] = {};
+  int launches[K_KINDS] = {};
   // scratch for host-resident calls
   void *d_io = nullptr;
   size_t d_io_bytes = 0;
@@ -1595,7 +1595,8 @@ int c1_qmf_synthesis_batch(c1_ctx *ctx, const float *bands, int64_t frames, int 
   return C1_OK;
 }
 
-// ---- the encoder's block selection and quantization stages on their own (codec/pipeline/encoder.js:111-152, :365-418) ----
+// ---- the encoder's block selection, quantization and serialization stages on their own (encoder.js:111-152, :365-418,
+// serialization.js:41-98) ----
 
 int c1_select_block_modes(c1_ctx *ctx, const float *bands, int64_t frames, int halo_frames, double threshold, int32_t *block_modes) {
   CTX_GUARD(ctx);
@@ -1662,6 +1663,35 @@ int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const in
   HIP_TRY(hipMemcpyAsync(sfi, ds_, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(wl, dw, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(quantized, dq, 512 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_pack_units(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi, const int32_t *wl,
+                  const int32_t *quantized, uint8_t *units) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "pack units: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!nbfu || !block_modes || !sfi || !wl || !quantized || !units) return fail(C1_ERR_ARG, "pack units: NULL argument");
+  // the field layout holds 52 BFUs; every other value takes the reference's meaning (include/carta1_hip.h)
+  for (int64_t f = 0; f < frames; f++)
+    if (nbfu[f] < 0 || nbfu[f] > 52) return fail(C1_ERR_ARG, "pack units: frame %lld: nBfu %d outside 0..52", (long long)f, nbfu[f]);
+  DeviceScratch ds;
+  int32_t *dn, *dm, *ds_, *dw, *dq; uint8_t *du;
+  const size_t n = (size_t)frames;
+  if ((rc = ds.alloc(&dn, n)) || (rc = ds.alloc(&dm, 3 * n)) || (rc = ds.alloc(&ds_, 52 * n)) || (rc = ds.alloc(&dw, 52 * n)) ||
+      (rc = ds.alloc(&dq, 512 * n)) || (rc = ds.alloc(&du, n * C1_UNIT_BYTES))) return rc;
+  HIP_TRY(hipMemcpyAsync(dn, nbfu, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dm, block_modes, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ds_, sfi, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dw, wl, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dq, quantized, 512 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  { ScopedTiming t(ctx, K_PACK_UNITS); c1k_launch_pack_units(dn, dm, ds_, dw, dq, frames, du, ctx->stream); }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(units, du, n * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }

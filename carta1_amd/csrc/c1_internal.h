@@ -209,6 +209,9 @@ void c1k_launch_stage_scale_factors(const C1DevTables *tables, const float *coef
 void c1k_launch_stage_fields(const C1DevTables *tables, const float *coefs, const int32_t *modes, const uint8_t *side,
                              const uint8_t *alloc, int64_t frames, int32_t *nbfu, int32_t *sfi, int32_t *wl, int32_t *q,
                              hipStream_t stream);
+// frame fields (as above) -> units = frames * 212 bytes, serializeFrame (serialization.js:41-98); nbfu must be 0..52
+void c1k_launch_pack_units(const int32_t *nbfu, const int32_t *modes, const int32_t *sfi, const int32_t *wl, const int32_t *q,
+                           int64_t frames, uint8_t *units, hipStream_t stream);
 // the single-stage functions the reference exports next to encode()/decode() (c1_k_stages.hip); device pointers
 void c1k_launch_quantize_one(const C1DevTables *tables, const float *x, int n, int sfi, int bits, int32_t *out, hipStream_t stream);
 void c1k_launch_dequantize_one(const C1DevTables *tables, const int32_t *q, int n, int sfi, int bits, float *out, hipStream_t stream);

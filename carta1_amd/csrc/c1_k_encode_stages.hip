@@ -1,9 +1,10 @@
 // c1_k_encode_stages.hip -- the encoder's middle and last pipeline stages on their own (codec/pipeline/encoder.js exports them
-// next to encode()): blockSelectorStage's detection branch (encoder.js:111-152) from stored bands, and quantizationStage
-// (:365-418) from stored coefficients, batched over consecutive frames of one channel in the reference's number model.  The
-// transient FFT, the feature sums and the decision are the exact detector's own device code (c1_detect_core.h); the bit
-// allocation is the encoder's k_alloc_* chain (c1_k_allocate.hip, launched by the host); quantize is k_quantize_one's
-// (quantize_into, c1_device.h).  The hot path never calls these kernels: c1_encode_* runs its own fused analysis.
+// next to encode()): blockSelectorStage's detection branch (encoder.js:111-152) from stored bands, quantizationStage
+// (:365-418) from stored coefficients, and serializeFrame (io/serialization.js:41-98) from frame fields, batched over
+// consecutive frames of one channel in the reference's number model.  The transient FFT, the feature sums and the decision
+// are the exact detector's own device code (c1_detect_core.h); the bit allocation is the encoder's k_alloc_* chain
+// (c1_k_allocate.hip, launched by the host); quantize is k_quantize_one's (quantize_into, c1_device.h).  The hot path never
+// calls these kernels: c1_encode_* runs its own fused analysis and packs in k_pack.
 #include "c1_detect_core.h"
 
 namespace {
@@ -135,8 +136,73 @@ __global__ __launch_bounds__(C1_WAVE) void k_stage_fields(const C1DevTables *tab
   }
 }
 
+// ---- serializeFrame ---------------------------------------------------------------------------------------------------
+// serializeFrame (serialization.js:41-98): the mirror of k_unpack_units, one wave per unit.  The unit is 53 big-endian
+// words in LDS; every field lands on bits no other field uses, so OR-ing a field into the (at most two) words it touches
+// is its insert, and the bits of a field past the 1 696th are dropped as packBits drops them (bitstream.js:15-38).
+// Fields are taken as any int32: the header in wrapping uint32 arithmetic, wl & 15, sfi & 63, q & mask, and no mantissas
+// for a BFU whose wl is outside 1..15 (WORD_LENGTH_BITS[wl] is 0 or undefined there).  nbfu is 0..52 (checked by the host).
+__device__ __forceinline__ void or_bits_be(uint32_t *words, int pos, int nbits, uint32_t v) {
+  const int w = pos >> 5, o = pos & 31;
+  if (w >= 53) return;
+  const uint64_t two = (uint64_t)v << (64 - o - nbits);      // o + nbits <= 47: the field sits in the top 47 bits
+  __hip_atomic_fetch_or(&words[w], (uint32_t)(two >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  const uint32_t lo = (uint32_t)two;
+  if (lo != 0u && w + 1 < 53) __hip_atomic_fetch_or(&words[w + 1], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+__global__ __launch_bounds__(C1_WAVE) void k_pack_units(const int32_t *__restrict__ nbfu, const int32_t *__restrict__ modes,
+                                                       const int32_t *__restrict__ sfi, const int32_t *__restrict__ wl,
+                                                       const int32_t *__restrict__ q, int64_t frames, uint8_t *__restrict__ units) {
+  __shared__ uint32_t words[53];
+  __shared__ uint32_t desc[52];           // per BFU: bits(5) | mantissa bit offset << 5
+  const int lane = threadIdx.x;
+  const int64_t f = blockIdx.x;
+  if (f >= frames) return;
+  if (lane < 53) words[lane] = 0u;
+  const int n = nbfu[f];
+  wave_fence();
+  if (lane == 0) {
+    // BFU_AMOUNTS.indexOf(nBfu): -1 sets bits 5..15; 2 - mode wraps, and the shifted fields overlap when a mode is out of range
+    const int idx = n == 20 ? 0 : ((n >= 28 && (n & 3) == 0) ? (n - 24) >> 2 : -1);
+    const uint32_t header = ((2u - (uint32_t)modes[3 * f]) << 14) | ((2u - (uint32_t)modes[3 * f + 1]) << 12) |
+                            ((3u - (uint32_t)modes[3 * f + 2]) << 10) | ((uint32_t)idx << 5);
+    words[0] = header << 16;
+  }
+  int w = 0, s = 0;
+  if (lane < n) {
+    w = wl[f * 52 + lane];
+    s = sfi[f * 52 + lane];
+  }
+  const int bits = lane < n && w >= 1 && w <= 15 ? w + 1 : 0;
+  const int mybits = lane < 52 ? bits * (int)kSpecs[lane] : 0;
+  const int scan = wave_inclusive_scan(mybits);
+  if (lane < 52) desc[lane] = (uint32_t)bits | ((uint32_t)(16 + 10 * n + scan - mybits) << 5);
+  wave_fence();
+  if (lane < n) {
+    or_bits_be(words, 16 + 4 * lane, 4, (uint32_t)w & 15u);
+    or_bits_be(words, 16 + 4 * n + 6 * lane, 6, (uint32_t)s & 63u);
+  }
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    const int slot = 8 * lane + m, b = bfu_of_slot(slot);
+    const uint32_t d = desc[b];
+    const int fb = (int)(d & 31u);
+    if (fb != 0) or_bits_be(words, (int)(d >> 5) + (slot - (int)kBfuFirst[b]) * fb, fb, (uint32_t)q[f * 512 + slot] & ((1u << fb) - 1u));
+  }
+  wave_fence();
+  if (lane < 53) {
+    const uint32_t v = lane == 52 ? words[52] & 0xff000000u : words[lane];   // bytes 209..211 are zeroed (:92-94)
+    reinterpret_cast<uint32_t *>(units + f * C1_UNIT_BYTES)[lane] = __builtin_bswap32(v);
+  }
+}
+
 }  // namespace
 
+void c1k_launch_pack_units(const int32_t *nbfu, const int32_t *modes, const int32_t *sfi, const int32_t *wl, const int32_t *q,
+                           int64_t frames, uint8_t *units, hipStream_t stream) {
+  hipLaunchKernelGGL(k_pack_units, dim3((unsigned)frames), dim3(C1_WAVE), 0, stream, nbfu, modes, sfi, wl, q, frames, units);
+}
 void c1k_launch_block_modes_from_bands(const C1DevTables *tables, const float *bands, int64_t frames, int halo, double threshold,
                                        float *mags, int32_t *modes, hipStream_t stream) {
   hipLaunchKernelGGL(k_stage_mags, dim3((unsigned)(frames + halo)), dim3(C1_WAVE), 0, stream, tables, bands, frames + halo, mags);

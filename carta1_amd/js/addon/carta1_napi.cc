@@ -694,6 +694,27 @@ napi_value QuantizeFrames(napi_env env, napi_callback_info info) {  // (ctx, Flo
   for (int i = 0; i < 4; i++) NAPI_OK(napi_set_named_property(env, obj, names[i], out[i]));
   return obj;
 }
+napi_value PackUnits(napi_env env, napi_callback_info info) {  // (ctx, Int32Array nbfu, blockModes, sfi, wl, quantized) -> Uint8Array units
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx; void *a[5]; size_t n[5];
+  if (!get_external(env, argv[0], &ctx)) return nullptr;
+  for (int i = 0; i < 5; i++) if (!get_typed(env, argv[1 + i], napi_int32_array, &a[i], &n[i])) return nullptr;
+  const size_t frames = n[0];
+  if (n[1] != 3 * frames || n[2] != 52 * frames || n[3] != 52 * frames || n[4] != 512 * frames) {
+    napi_throw_type_error(env, nullptr, "packUnits: nBfu, 3 block modes, 52 sfi, 52 wl and 512 mantissas per frame");
+    return nullptr;
+  }
+  napi_value ab, out;
+  void *u;
+  NAPI_OK(napi_create_arraybuffer(env, frames * C1_UNIT_BYTES + 4, &u, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_uint8_array, frames * C1_UNIT_BYTES, ab, 0, &out));
+  const int rc = c1_pack_units(ctx, (int64_t)frames, static_cast<const int32_t *>(a[0]), static_cast<const int32_t *>(a[1]),
+                               static_cast<const int32_t *>(a[2]), static_cast<const int32_t *>(a[3]), static_cast<const int32_t *>(a[4]),
+                               static_cast<uint8_t *>(u));
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 napi_value DequantizeFrames(napi_env env, napi_callback_info info) {  // (ctx, Int32Array nbfu, blockModes, sfi, wl, quantized) -> Float32Array coefs
   napi_value argv[6];
   if (!get_args(env, info, 6, argv)) return nullptr;
@@ -769,6 +790,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"quantizeFrames", nullptr, QuantizeFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"unpackUnits", nullptr, UnpackUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"dequantizeFrames", nullptr, DequantizeFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"packUnits", nullptr, PackUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"imdct", nullptr, Imdct, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"qmfSynthesis", nullptr, QmfSynthesis, nullptr, nullptr, nullptr, napi_default, nullptr},
   };

@@ -7,6 +7,7 @@ import {
   AEA_TITLE_OFFSET, AEA_TITLE_SIZE, AEA_FRAME_COUNT_OFFSET, AEA_CHANNEL_COUNT_OFFSET,
 } from '../core/constants.js'
 import { BitWriter, BitReader } from './bitstream.js'
+import { native, context } from '../native.js'
 
 export function serializeFrame(frameData) {
   const unit = new Uint8Array(SOUND_UNIT_SIZE)
@@ -28,6 +29,49 @@ export function serializeFrame(frameData) {
   }
   unit[SOUND_UNIT_SIZE - 3] = unit[SOUND_UNIT_SIZE - 2] = unit[SOUND_UNIT_SIZE - 1] = 0
   return unit
+}
+
+// serializeFrames(frameDataList): serializeFrame (codec/io/serialization.js:41-98) of every frameData, such as
+// quantizationStage returns, in one device call (c1_pack_units) -> one Uint8Array of n * 212 bytes, unit after unit.
+// Bit-exact to the reference for every int32 field value, non-canonical ones included (the header's wrapping arithmetic,
+// nBfu outside BFU_AMOUNTS, wl & 15 and sfi & 63, q & mask, truncation at the unit's end; include/carta1_hip.h).
+// RangeError for an nBfu outside 0..52, a value the reference reads that is not an int32, and -- the one deviation --
+// a quantizedCoefficients[b] whose length is not SPECS_PER_BFU[b] where b < nBfu and WORD_LENGTH_BITS[wl] > 0: the
+// reference writes arrays of any length, and the device reads exactly SPECS_PER_BFU[b] mantissas per BFU.
+const isInt32 = (v) => typeof v === 'number' && (v | 0) === v
+
+export function serializeFrames(frameDataList) {
+  const n = frameDataList.length
+  const nbfu = new Int32Array(n), modes = new Int32Array(3 * n), sfi = new Int32Array(52 * n), wl = new Int32Array(52 * n)
+  const q = new Int32Array(512 * n)
+  for (let f = 0; f < n; f++) {
+    const fd = frameDataList[f]
+    const k = fd.nBfu
+    if (!isInt32(k) || k < 0 || k > 52) throw new RangeError(`serializeFrames: frame ${f}: nBfu ${k} is not an integer 0..52`)
+    nbfu[f] = k
+    for (let i = 0; i < 3; i++) {
+      const m = fd.blockModes[i]
+      if (!isInt32(m)) throw new RangeError(`serializeFrames: frame ${f}: block mode ${i} (${m}) is not an int32`)
+      modes[3 * f + i] = m
+    }
+    for (let b = 0, at = 512 * f; b < k; at += SPECS_PER_BFU[b], b++) {
+      const w = fd.wordLengthIndices[b], s = fd.scaleFactorIndices[b]
+      if (!isInt32(w) || !isInt32(s)) throw new RangeError(`serializeFrames: frame ${f} BFU ${b}: word length ${w} or scale factor ${s} is not an int32`)
+      wl[52 * f + b] = w
+      sfi[52 * f + b] = s
+      if (w < 1 || w > 15) continue                       // WORD_LENGTH_BITS[w] is 0 or undefined: no mantissas
+      const c = fd.quantizedCoefficients[b]
+      if (!c || c.length !== SPECS_PER_BFU[b]) {
+        throw new RangeError(`serializeFrames: frame ${f} BFU ${b}: ${c ? c.length : 'no'} mantissas, not ${SPECS_PER_BFU[b]}`)
+      }
+      for (let j = 0; j < c.length; j++) {
+        if (!isInt32(c[j])) throw new RangeError(`serializeFrames: frame ${f} BFU ${b}: mantissa ${j} (${c[j]}) is not an int32`)
+        q[at + j] = c[j]
+      }
+    }
+  }
+  if (n === 0) return new Uint8Array(0)
+  return native().packUnits(context(), nbfu, modes, sfi, wl, q)
 }
 
 export function deserializeFrame(buffer) {

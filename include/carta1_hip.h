@@ -107,8 +107,8 @@ int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stre
 int c1_ctx_destroy(c1_ctx *ctx);
 int c1_ctx_synchronize(c1_ctx *ctx);
 /* milliseconds the device spent in the named kernel during the most recent *_device call on this
- * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), from HIP events on the context's
- * stream; c1_ctx_set_profiling(ctx, 1) must have been set before the call */
+ * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), or in the most recent c1_pack_units call
+ * ("pack_units"), from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1) must have been set before the call */
 int c1_ctx_set_profiling(c1_ctx *ctx, int enabled);
 int c1_ctx_kernel_ms(c1_ctx *ctx, const char *name, double *ms, int *launches);
 
@@ -322,6 +322,21 @@ int c1_select_block_modes(c1_ctx *ctx, const float *bands, int64_t frames, int h
  * allocation runs on scratch of the call, not on the context's encode workspace. */
 int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const int32_t *block_modes,
                        const c1_encode_options *opts, int32_t *nbfu, int32_t *sfi, int32_t *wl, int32_t *quantized);
+/* serializeFrame, codec/io/serialization.js:41-98, the inverse of c1_unpack_units: frame fields in the layout c1_unpack_units
+ * writes and c1_quantize_frames returns -> units = frames*212 bytes.  frames 0 .. 2^20 of one channel; host pointers,
+ * synchronous; frames == 0 writes nothing.  C1_ERR_ARG for a NULL pointer, frames out of range, or an nbfu outside 0..52
+ * (the layout holds 52 BFUs).  Every other value is any int32 and takes the reference's meaning:
+ *   header: ((2 - m0) << 14) | ((2 - m1) << 12) | ((3 - m2) << 10) | (idx << 5) in wrapping uint32 arithmetic, truncated
+ *     to 16 bits, big-endian; idx = the position of nbfu in BFU_AMOUNTS, or -1, which sets bits 5..15.  Out-of-range
+ *     modes make the fields overlap (nbfu 19, modes 0,0,0: 0xffe0; nbfu 20, modes 1,-2,7: 0xf000).
+ *   from bit 16: nbfu 4-bit fields wl & 15, then nbfu 6-bit fields sfi & 63.
+ *   mantissas: for b < nbfu in BFU order, SPECS_PER_BFU[b] fields of WORD_LENGTH_BITS[wl] = wl + 1 bits, value q & mask,
+ *     when wl is 1..15.  A wl outside 0..15 still writes its 4 bits wl & 15 but no mantissas (WORD_LENGTH_BITS[wl] is
+ *     undefined there).
+ *   truncation: bits past bit 1696 are dropped, also the tail of a field that straddles it (packBits stops at the end of
+ *     the buffer, bitstream.js:15-38); then bytes 209..211 are zeroed.  Bits after the end of the stream are zero. */
+int c1_pack_units(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi,
+                  const int32_t *wl, const int32_t *quantized, uint8_t *units);
 
 /* ---- stage taps for bring-up and stage-level parity tests (device pointers) ---------------- */
 /* bands: frames*channels*512 floats (low128|mid128|high256 per unit index, before windowing);
