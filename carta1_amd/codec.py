@@ -77,11 +77,17 @@ class EncoderOptions:
         the package carries the tables V8 produced for the biases 0, 0.25, 0.5, 1, 1.5, 2, 3.3 and 5
         (carta1_amd/biased_tables.json, generated from the golden vectors).  Any other bias falls back to libm's pow,
         whose last bit may differ from V8's ("parity unpinned" for those) -- pass biased_table to pin it; the JavaScript
-        host always uses its own engine's Math.pow."""
+        host always uses its own engine's Math.pow.  Bias 1 is SCALE_FACTORS itself (bitallocation.js:51-53): the table
+        installed with c1_set_tables at the time to_c() runs, which c1_default_encode_options copies.  A context keeps the
+        tables it was created with (its quantization norms, window, transforms), so for a context created before a later
+        c1_set_tables, pass biased_table= its own SCALE_FACTORS (c1_get_default_tables, or the table installed then);
+        otherwise its allocation would weigh with the newer engine's table."""
         o = capi.EncodeOptions()
         capi.check(capi.load().c1_default_encode_options(C.byref(o)))
         bias = float(self.values['allocationBias'])
-        table = self.biased_table if self.biased_table is not None else packaged_biased_table(bias)
+        table = self.biased_table
+        if table is None and bias != 1.0:
+            table = packaged_biased_table(bias)
         if table is not None:
             for i in range(64):
                 o.biased_scale_factors[i] = float(table[i])

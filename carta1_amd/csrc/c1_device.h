@@ -196,8 +196,9 @@ __device__ __forceinline__ int wave_inclusive_scan(int x) {
 
 __device__ __forceinline__ int bitrev(int k, int log2n) { return (int)(__brev((unsigned)k) >> (32 - log2n)); }
 
-// findScaleFactor on binary32 bit patterns: with SF[3q] = 2^(q-21) and the two in-between fraction
-// patterns m1 < m2 shared by every octave, the index is 3(e+21) + [frac > 0] + [frac > m1] + [frac > m2]
+// findScaleFactor (bitallocation.js:290-299) = ceil(3 (log2 m + 21)) on binary32 bit patterns: its boundaries 2^(i/3-21) are
+// 2^(q-21) at i = 3q and two in-between fraction patterns m1 < m2 shared by every octave (C1DevTables::sf_m1 / sf_m2), so
+// the index is 3(e+21) + [frac > 0] + [frac > m1] + [frac > m2]; the installed SCALE_FACTORS play no part
 __device__ __forceinline__ int scale_factor_index_fast(float maxabs, uint32_t m1, uint32_t m2) {
   const uint32_t u = __float_as_uint(maxabs);
   const int e = (int)(u >> 23) - 127;
@@ -205,22 +206,6 @@ __device__ __forceinline__ int scale_factor_index_fast(float maxabs, uint32_t m1
   int r = 3 * (e + 21) + (frac > 0u ? 1 : 0) + (frac > m1 ? 1 : 0) + (frac > m2 ? 1 : 0);
   r = r > 63 ? 63 : r;
   return (e < -21) ? 0 : r;     // also zero, denormals and anything below 2^-21
-}
-
-// smallest i with m <= SCALE_FACTORS[i], clamped to [0,63]  == findScaleFactor, bitallocation.js:290-299
-__device__ __forceinline__ int scale_factor_index(float maxabs, TablesPtr T) {
-  if (!(maxabs > 0.0f)) return 0;
-  const double m = (double)maxabs;
-  if (m > 1.0) return 63;                        // SCALE_FACTORS[63] = 2^0
-  int e = (int)((__float_as_uint(maxabs) >> 23) & 0xff) - 127;  // floor(log2 m) for normal m
-  if (e < -21) return 0;                         // also covers denormals (field 0 -> e = -127)
-  int i = 3 * (e + 21);                          // SCALE_FACTORS[i] = 2^e <= m
-  // m in [2^e, 2^(e+1)): answer is i, i+1, i+2 or i+3
-  int r = i;
-  if (m > T->scale_factors[i]) r = i + 1;
-  if (i + 1 <= 63 && m > T->scale_factors[i + 1 > 63 ? 63 : i + 1]) r = i + 2;
-  if (i + 2 <= 63 && m > T->scale_factors[i + 2 > 63 ? 63 : i + 2]) r = i + 3;
-  return r > 63 ? 63 : r;
 }
 
 // =====================================================================================================
@@ -264,7 +249,7 @@ __device__ __forceinline__ void sf_long(const float *coef, uint8_t *sfi_out, con
   // the neighbour lane's maximum: a DPP quad permutation [1,0,3,2], not an LDS-crossbar shuffle
   const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mx), 0xB1, 0xf, 0xf, false));
   mx = fmaxf(mx, g.wide ? other : 0.0f);
-  const int sfi = T->sf_fast ? scale_factor_index_fast(mx, T->sf_m1, T->sf_m2) : scale_factor_index(mx, T);
+  const int sfi = scale_factor_index_fast(mx, T->sf_m1, T->sf_m2);
   if (g.store) sfi_out[g.b] = (uint8_t)sfi;
 }
 

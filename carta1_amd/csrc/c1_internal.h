@@ -23,8 +23,11 @@ struct C1DevTables {
   double scale_factors[64];
   double norm[64 * 16];      // quantRange(wl)/SCALE_FACTORS[sfi]   quantization.js:42-44
   double log1p10;
-  // fraction bits (23) of floor_f32(2^(1/3)) and floor_f32(2^(2/3)) when every octave of scale_factors
-  // shares them (always true for the reference's table); sf_fast = 0 selects the table compare
+  // findScaleFactor is ceil(3 (log2 m + 21)) (bitallocation.js:290-299): its boundaries are the powers 2^(i/3-21), not the
+  // installed table.  sf_m1 / sf_m2 are the fraction bits (23) of floor_f32(2^(1/3)) and floor_f32(2^(2/3)) of those
+  // boundaries (constants: the kernels always read the index off the bit pattern).  sf_fast = 1 when the installed
+  // scale_factors share one such pattern in every octave, with exact powers of two at i % 3 == 0: a structural check the
+  // speculative paths require (spec_ok), reported by c1_table_fast_paths
   uint32_t sf_m1, sf_m2;
   int32_t sf_fast;
   // dequantization (q * SF) / range as q0 = a*y, r = fma(-q0, range, a), fma(r, y, q0) with y = RN(1/range)

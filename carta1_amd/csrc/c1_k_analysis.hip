@@ -239,7 +239,7 @@ __global__ __launch_bounds__(C1_WAVE, ALL_LONG ? 4 : 3) void k_analysis_fast(C1E
         float mx = sf_scan_long_groups(grp[0], grp[1], grp[2]);
         const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mx), 0xB1, 0xf, 0xf, false));
         mx = fmaxf(mx, ((sw >> 19) & 1u) ? other : 0.0f);
-        const int sfi = T->sf_fast ? scale_factor_index_fast(mx, T->sf_m1, T->sf_m2) : scale_factor_index(mx, T);
+        const int sfi = scale_factor_index_fast(mx, T->sf_m1, T->sf_m2);
         if ((sw >> 20) & 1u) S.sfi[(sw >> 13) & 63u] = (uint8_t)sfi;
       }
       {

@@ -664,7 +664,7 @@ __global__ __launch_bounds__(C1_WAVE * (LONG ? kMdctWavesLong : 1), LONG ? 4 : 3
         float mx = sf_scan_long_groups(grp[0], grp[1], grp[2]);
         const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mx), 0xB1, 0xf, 0xf, false));
         mx = fmaxf(mx, ((sw >> 19) & 1u) ? other : 0.0f);
-        const int sfi = T->sf_fast ? scale_factor_index_fast(mx, T->sf_m1, T->sf_m2) : scale_factor_index(mx, T);
+        const int sfi = scale_factor_index_fast(mx, T->sf_m1, T->sf_m2);
         if ((sw >> 20) & 1u) S.sfi[(sw >> 13) & 63u] = (uint8_t)sfi;
       }
       if (lane >= 60) reinterpret_cast<uint32_t *>(S.sfi)[13 + (lane - 60) % 3] = 0;   // modes byte (all long) and padding
@@ -674,7 +674,7 @@ __global__ __launch_bounds__(C1_WAVE * (LONG ? kMdctWavesLong : 1), LONG ? 4 : 3
         const int n = my_size;
         float mx = 0.0f;
         for (int j = 0; j < n; j++) mx = fmaxf(mx, fabsf(coef[start + j]));
-        S.sfi[lane] = (uint8_t)(T->sf_fast ? scale_factor_index_fast(mx, T->sf_m1, T->sf_m2) : scale_factor_index(mx, T));
+        S.sfi[lane] = (uint8_t)scale_factor_index_fast(mx, T->sf_m1, T->sf_m2);
       } else {
         S.sfi[lane] = lane == 52 ? (uint8_t)mode_byte : 0;
       }

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(C1_WAVE) void k_stage_scale_factors(const C1DevTabl
       if (a <= 0x7f800000u && a > mx) mx = a;                 // not NaN, and a > maxAmplitude
     }
     const float m = __uint_as_float(mx);
-    sfi = T->sf_fast ? scale_factor_index_fast(m, T->sf_m1, T->sf_m2) : scale_factor_index(m, T);
+    sfi = scale_factor_index_fast(m, T->sf_m1, T->sf_m2);
   }
   side[f * kSideBytes + lane] = (uint8_t)sfi;                 // lanes 52..63: the rest of the record, zeros
 }

@@ -89,13 +89,16 @@ int c1_set_tables(const c1_tables *tables);      /* NULL restores defaults; appl
 /* fills biased_scale_factors for allocationBias == 1 (exact copy, bitallocation.js:51-52) and sets
  * threshold 1.0 / detection on: the EncoderOptions defaults (options.js:17-23) */
 int c1_default_encode_options(c1_encode_options *out);
-/* Diagnostics (host only, no device needed): which table-dependent shortcuts the kernels will take with the
- * tables currently installed.  Both are verified on the host against the plain formulation for the whole input
- * domain when tables are installed, and the kernels fall back to it when a check fails:
- *  scale_factor_bits  findScaleFactor (bitallocation.js:290-299) from the binary32 bit pattern
+/* Diagnostics (host only, no device needed): two properties of the tables currently installed.
+ *  scale_factor_bits  1 when SCALE_FACTORS has the structure of 2^(i/3-21) in binary32 (exact powers of two at i % 3 == 0,
+ *                     one pair of fraction patterns shared by every octave); the speculative paths require it.  It does
+ *                     not change findScaleFactor (bitallocation.js:290-299), which is ceil(3 (log2 m + 21)) whatever the
+ *                     table: the kernels always read it off the binary32 bit pattern against those fixed boundaries.
  *  dequant_reciprocal dequantize's (q * SF) / range (quantization.js:65-78): 1 = as multiply + two FMAs with RN(1 / range);
  *                     2 = moreover, after the store to the Float32 array, equal to q * RN(SF * RN(1 / range)) for every
- *                     (word length, scale factor, q): one product per BFU and one per coefficient */
+ *                     (word length, scale factor, q): one product per BFU and one per coefficient.  Both are verified on
+ *                     the host against the division for the whole input domain when tables are installed; the kernels
+ *                     fall back to it when a check fails */
 int c1_table_fast_paths(int *scale_factor_bits, int *dequant_reciprocal);
 /* Diagnostics (host only): how the bit allocation will order heap priorities for opts' biased table.  affine = 1: by
  * the integer form A*sfi + C (word length 0) / A*sfi - B*(wl + 1) (wl >= 1) plus an offset, coef = {A, B, C, offset};

@@ -12,6 +12,33 @@
 #include <string.h>
 
 #include "c1o_tables.inc"
+
+/* The tables in use: the defaults above, or another engine's installed with c1o_set_tables (945 doubles in the order of
+ * c1_tables: SCALE_FACTORS, WINDOW_SHORT, the six MDCT sinCosTables, the eight FFT (cos, sin) pairs, log1p(10)).
+ * findScaleFactor keeps C1O_SCALE_FACTORS: the reference computes ceil(3 (log2 m + 21)) and never reads the table there;
+ * comparing against the default table is that function (tests/golden/find_scale_factor.json).  Not thread safe. */
+#define C1O_TABLE_DOUBLES 945
+static double tab_custom[C1O_TABLE_DOUBLES];
+static const double *SF = C1O_SCALE_FACTORS, *WIN = C1O_WINDOW_SHORT, *FWD64 = C1O_MDCT_FWD64, *FWD256 = C1O_MDCT_FWD256,
+                    *FWD512 = C1O_MDCT_FWD512, *INV64 = C1O_MDCT_INV64, *INV256 = C1O_MDCT_INV256,
+                    *INV512 = C1O_MDCT_INV512, *FFTW = C1O_FFT_W, *LOG1P10 = &C1O_LOG1P_10;
+
+void c1o_reset_tables(void) {
+  SF = C1O_SCALE_FACTORS; WIN = C1O_WINDOW_SHORT;
+  FWD64 = C1O_MDCT_FWD64; FWD256 = C1O_MDCT_FWD256; FWD512 = C1O_MDCT_FWD512;
+  INV64 = C1O_MDCT_INV64; INV256 = C1O_MDCT_INV256; INV512 = C1O_MDCT_INV512;
+  FFTW = C1O_FFT_W; LOG1P10 = &C1O_LOG1P_10;
+}
+
+void c1o_set_tables(const double *t) {
+  if (!t) { c1o_reset_tables(); return; }
+  memcpy(tab_custom, t, sizeof tab_custom);
+  const double *p = tab_custom;
+  SF = p; p += 64; WIN = p; p += 32;
+  FWD64 = p; p += 32; FWD256 = p; p += 128; FWD512 = p; p += 256;
+  INV64 = p; p += 32; INV256 = p; p += 128; INV512 = p; p += 256;
+  FFTW = p; p += 16; LOG1P10 = p;
+}
 #include "c1o_fdlibm.h"
 
 #define F32(x) ((float)(x))
@@ -58,11 +85,11 @@ static void init_tables(void) {
   tables_ready = 1;
 }
 
-const double *c1o_scale_factors(void) { return C1O_SCALE_FACTORS; }
+const double *c1o_scale_factors(void) { return SF; }
 
 /* buildBiasedScaleFactorTable: codec/coding/bitallocation.js:46-61 */
 void c1o_default_biased_sf(double bias, double out[64]) {
-  for (int i = 0; i < 64; i++) out[i] = (bias == 1.0) ? C1O_SCALE_FACTORS[i] : pow(C1O_SCALE_FACTORS[i], bias);
+  for (int i = 0; i < 64; i++) out[i] = (bias == 1.0) ? SF[i] : pow(SF[i], bias);
 }
 
 void c1o_enc_state_init(c1o_enc_state *s) { memset(s, 0, sizeof *s); }
@@ -139,7 +166,7 @@ static void fft_inplace(float *re, float *im, int size) {
   int stage = 0;
   for (int stride = 2; stride <= size; stride <<= 1, stage++) { /* fft.js:35-66 */
     int half = stride >> 1;
-    double wr = C1O_FFT_W[2 * stage], wi = C1O_FFT_W[2 * stage + 1]; /* cos/sin(-2*pi/stride) */
+    double wr = FFTW[2 * stage], wi = FFTW[2 * stage + 1]; /* cos/sin(-2*pi/stride) */
     for (int start = 0; start < size; start += stride) {
       double tr = 1, ti = 0;
       for (int k = 0; k < half; k++) {
@@ -162,9 +189,9 @@ static void fft_inplace(float *re, float *im, int size) {
 /* ---- MDCT / IMDCT: codec/transforms/mdct.js ---------------------------------------- */
 
 static const double *mdct_table(int size, int inverse) {
-  if (size == 64) return inverse ? C1O_MDCT_INV64 : C1O_MDCT_FWD64;
-  if (size == 256) return inverse ? C1O_MDCT_INV256 : C1O_MDCT_FWD256;
-  return inverse ? C1O_MDCT_INV512 : C1O_MDCT_FWD512;
+  if (size == 64) return inverse ? INV64 : FWD64;
+  if (size == 256) return inverse ? INV256 : FWD256;
+  return inverse ? INV512 : FWD512;
 }
 
 /* MDCT.transform, mdct.js:54-122: size samples in, size/2 coefficients out */
@@ -302,7 +329,7 @@ double c1o_transient_score(const float *cur, const float *prev, int n) {
   double e_change = db > 0 ? db : 0;
   /* calculateTransientScore :197-226 */
   double flat_c = sqrt(flat_change);
-  double hf_c = c1o_fd_log1p(hf_change * 10) / C1O_LOG1P_10;
+  double hf_c = c1o_fd_log1p(hf_change * 10) / *LOG1P10;
   double e_c = e_change / 30 < 1 ? e_change / 30 : 1;
   return (flux + flat_c + hf_c + e_c) / 4;
 }
@@ -338,8 +365,8 @@ static void tail_window(float *samples, float *overlap, int block) {
   int t0 = block - 32;
   for (int i = 0; i < 32; i++) {
     double v = samples[t0 + i];
-    overlap[i] = F32(C1O_WINDOW_SHORT[i] * v);
-    samples[t0 + i] = F32(v * C1O_WINDOW_SHORT[31 - i]);
+    overlap[i] = F32(WIN[i] * v);
+    samples[t0 + i] = F32(v * WIN[31 - i]);
   }
 }
 
@@ -521,7 +548,7 @@ void c1o_quantize_bfu(const float *x, int n, int sfi, int bits, int *out) {
     return;
   }
   double hi = quantize_range(bits), lo = -hi;
-  double norm = hi / C1O_SCALE_FACTORS[sfi];
+  double norm = hi / SF[sfi];
   for (int i = 0; i < n; i++) {
     double v = (double)x[i] * norm;
     double y = (double)to_int32(v + (v >= 0 ? 0.5 : -0.5));
@@ -536,7 +563,7 @@ void c1o_dequantize_bfu(const int *q, int n, int sfi, int bits, float *out) {
     return;
   }
   double range = quantize_range(bits);
-  for (int i = 0; i < n; i++) out[i] = F32(((double)q[i] * C1O_SCALE_FACTORS[sfi]) / range);
+  for (int i = 0; i < n; i++) out[i] = F32(((double)q[i] * SF[sfi]) / range);
 }
 
 /* ---- encode() closure: encoder.js:438-450 (+ quantizationStage :365-418) ------------ */
@@ -625,7 +652,7 @@ void c1o_unpack_unit(const uint8_t unit[212], c1o_fields *f) {
 /* overlapAdd, mdct.js:230-245, with size 16 and the 32-entry sine window */
 static void overlap_add16(const float *prev, const float *curr, float *out) {
   for (int i = 0; i < 16; i++) {
-    double w1 = C1O_WINDOW_SHORT[i], w2 = C1O_WINDOW_SHORT[31 - i];
+    double w1 = WIN[i], w2 = WIN[31 - i];
     double p = prev[i], c = curr[15 - i];
     out[i] = F32(p * w2 - c * w1);
     out[31 - i] = F32(p * w1 + c * w2);

@@ -63,6 +63,11 @@ typedef struct c1o_fields {
   int q[C1O_FRAME];      /* mantissas, BFU after BFU, SPECS_PER_BFU[b] each */
 } c1o_fields;
 
+/* install another engine's tables: 945 doubles laid out as c1_tables (include/carta1_hip.h); NULL or c1o_reset_tables()
+ * restores the defaults.  Quantize, dequantize, the MDCTs, the FFT, the window and the transient score then read them;
+ * findScaleFactor stays on the reference's log2 boundaries.  Process-wide, not thread safe. */
+void c1o_set_tables(const double *tables);
+void c1o_reset_tables(void);
 void c1o_default_biased_sf(double bias, double out[64]); /* bias==1 exact copy; else libm pow (unpinned vs V8 for general bias) */
 const double *c1o_scale_factors(void);
 

@@ -52,6 +52,9 @@ def lib():
         _lib = C.CDLL(build())
         fp = C.POINTER(C.c_float)
         ip = C.POINTER(C.c_int)
+        _lib.c1o_set_tables.argtypes = [C.POINTER(C.c_double)]
+        _lib.c1o_set_tables.restype = None
+        _lib.c1o_reset_tables.restype = None
         _lib.c1o_default_biased_sf.argtypes = [C.c_double, C.POINTER(C.c_double)]
         _lib.c1o_scale_factors.restype = C.POINTER(C.c_double)
         _lib.c1o_qmf_analysis_frame.argtypes = [C.POINTER(EncState), fp, fp]
@@ -138,6 +141,20 @@ def make_options(fixed_modes=None, bias=1.0, threshold=1.0, biased=None):
     for i in range(64):
         o.biased_sf[i] = b[i]
     return o
+
+
+TABLE_DOUBLES = 945     # c1_tables: 64 + 32 + 32 + 128 + 256 + 32 + 128 + 256 + 16 + 1
+
+
+def set_tables(tables):
+    """install another engine's tables (945 doubles in c1_tables order) for every later oracle call; None restores the
+    defaults.  findScaleFactor keeps the reference's log2 boundaries."""
+    if tables is None:
+        lib().c1o_reset_tables()
+        return
+    t = np.ascontiguousarray(tables, dtype=np.float64)
+    assert t.shape == (TABLE_DOUBLES,)
+    lib().c1o_set_tables(t.ctypes.data_as(C.POINTER(C.c_double)))
 
 
 def pcm_from_int(raw, bits, channels):

@@ -148,8 +148,9 @@ def test_sound_unit_fields_round_trip_and_match_reference():
 
 
 def test_table_dependent_shortcuts_are_verified_for_the_default_tables():
-    """The kernels read findScaleFactor off the binary32 bit pattern and dequantize with a reciprocal + two FMAs
-    only when the host has checked those forms over their whole input domain for the installed tables."""
+    """scale_factor_bits reports whether the installed SCALE_FACTORS have the structure of 2^(i/3-21) (the speculative
+    paths require it; findScaleFactor itself never reads the table), and the kernels dequantize with a reciprocal + two
+    FMAs only when the host has checked that form over its whole input domain for the installed tables."""
     from carta1_amd import capi
     lib = capi.load()
     a, b = C.c_int(-1), C.c_int(-1)
@@ -157,7 +158,7 @@ def test_table_dependent_shortcuts_are_verified_for_the_default_tables():
     assert (a.value, b.value) == (1, 2)
     t = capi.Tables()
     assert lib.c1_get_default_tables(C.byref(t)) == 0
-    t.scale_factors[10] *= 1.0000001            # no longer 2^(i/3 - 21): the bit-pattern form must be refused
+    t.scale_factors[10] *= 1.0000001            # no longer 2^(i/3 - 21): the structure check must fail
     try:
         assert lib.c1_set_tables(C.byref(t)) == 0
         assert lib.c1_table_fast_paths(C.byref(a), C.byref(b)) == 0
