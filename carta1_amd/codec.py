@@ -216,6 +216,13 @@ class Context:
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
                                                 capi.ptr_array(pcm_ptrs)))
 
+    def decode_fields_device(self, field_ptrs, channels, frames, pcm_ptrs, halo_frames=0):
+        """c1_decode_fields_device: field_ptrs = device pointers (nbfu, block_modes, sfi, wl, quantized) of frame 0, the halo's
+        fields (halo_frames 0 or 1) just before them; unit index frame * channels + channel.  Fields outside the domain of
+        include/carta1_hip.h are not checked here."""
+        capi.check(capi.load().c1_decode_fields_device(self._h, channels, frames, halo_frames,
+                                                       *[C.c_void_p(int(p)) for p in field_ptrs], capi.ptr_array(pcm_ptrs)))
+
     def generate_device(self, signal, seed, frames, pcm_ptr):
         capi.check(capi.load().c1_generate_device(self._h, signal, seed, frames, C.c_void_p(pcm_ptr)))
 
@@ -402,6 +409,22 @@ class Context:
         capi.check(capi.load().c1_unpack_units(self._h, u.ctypes.data, frames, *[out[k].ctypes.data for k, _ in self.FIELD_SHAPES]))
         return out
 
+    def decode_fields(self, fields, channels=1, halo_frames=0):
+        """decode() over frame fields (c1_decode_fields_batch): a dict as unpack_units / quantize_frames return it, with
+        (halo_frames + frames) * channels units in the order frame * channels + channel (the first halo_frames frames: the
+        stream's previous frame) -> a list of float32 arrays of frames * 512 samples, one per channel, as decode returns"""
+        arrs = _field_arrays(fields)
+        units = arrs[0].size
+        if units % channels:
+            raise ValueError('the fields must hold whole frames of %d channel(s)' % channels)
+        frames = units // channels - halo_frames
+        outs = [np.zeros(max(frames, 0) * 512, dtype=np.float32) for _ in range(channels)]
+        capi.check(capi.load().c1_decode_fields_batch(self._h, channels, frames, halo_frames,
+                                                      *[a.ctypes.data + 4 * halo_frames * channels * int(np.prod(shape, dtype=np.int64))
+                                                        for a, (_, shape) in zip(arrs, self.FIELD_SHAPES)],
+                                                      capi.ptr_array([o.ctypes.data for o in outs])))
+        return outs
+
     def dequantize_frames(self, fields):
         """dequantizationStage, decoder.js:52-98: a dict of frame fields as unpack_units returns it -> float32 [frames, 512]"""
         frames = int(np.asarray(fields['nbfu']).size)
@@ -520,6 +543,18 @@ class DecoderStream:
                                                   capi.ptr_array([o.ctypes.data for o in outs])))
         return outs
 
+    def push_fields(self, fields):
+        """frame fields (the dict unpack_units returns, unit index frame * channels + channel) continuing the same stream as
+        push: any interleaving of the two decodes as one call over all frames would"""
+        arrs = _field_arrays(fields)
+        frames = arrs[0].size // self.channels
+        if arrs[0].size != frames * self.channels:
+            raise ValueError('the fields must hold whole frames of %d channel(s)' % self.channels)
+        outs = [np.zeros(frames * 512, dtype=np.float32) for _ in range(self.channels)]
+        capi.check(capi.load().c1_dec_stream_push_fields(self._h, frames, *[a.ctypes.data for a in arrs],
+                                                         capi.ptr_array([o.ctypes.data for o in outs])))
+        return outs
+
     def close(self):
         if self._h:
             capi.load().c1_dec_stream_destroy(self._h)
@@ -564,6 +599,18 @@ def pinned_empty(shape, dtype=np.float32):
 
 
 _default_ctx = None
+
+
+def _field_arrays(fields):
+    """the five frame-field arrays of `fields` (Context.FIELD_SHAPES order) as contiguous int32, sizes checked"""
+    units = int(np.asarray(fields['nbfu']).size)
+    arrs = []
+    for k, shape in Context.FIELD_SHAPES:
+        a = np.ascontiguousarray(fields[k], dtype=np.int32)
+        if a.size != units * int(np.prod(shape, dtype=np.int64)):
+            raise ValueError('%s must hold %s entries per frame' % (k, shape or 1))
+        arrs.append(a)
+    return arrs
 
 
 def _check_quantize_args(scale_factor_index, bits_per_sample):

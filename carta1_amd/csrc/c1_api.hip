@@ -364,8 +364,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields"};
 
 }  // namespace
 
@@ -1495,6 +1495,38 @@ int c1_mdct_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_fram
 
 namespace {
 constexpr int64_t kMaxStageFrames = (int64_t)1 << 20;
+
+// The indices the reference reads (BFUs below nBfu) must name table entries: BFU_START_*, WORD_LENGTH_BITS, SCALE_FACTORS.
+// units = frames * channels frame fields, unit u = frame (first_frame + u / channels) of channel u % channels.
+int check_field_domain(const char *what, int64_t units, int channels, int64_t first_frame, const int32_t *nbfu, const int32_t *sfi,
+                       const int32_t *wl) {
+  auto where = [&](int64_t u) {
+    char at[64];
+    if (channels == 1) snprintf(at, sizeof at, "frame %lld", (long long)(first_frame + u));
+    else snprintf(at, sizeof at, "frame %lld channel %d", (long long)(first_frame + u / channels), (int)(u % channels));
+    return std::string(at);
+  };
+  for (int64_t u = 0; u < units; u++) {
+    const int32_t n = nbfu[u];
+    if (n < 0 || n > 52) return fail(C1_ERR_ARG, "%s: %s: nBfu %d outside 0..52", what, where(u).c_str(), n);
+    for (int b = 0; b < n; b++) {
+      const int32_t w = wl[52 * u + b], s = sfi[52 * u + b];
+      if (w < 0 || w > 15) return fail(C1_ERR_ARG, "%s: %s BFU %d: word length index %d outside 0..15", what, where(u).c_str(), b, w);
+      if (s < 0 || s > 63) return fail(C1_ERR_ARG, "%s: %s BFU %d: scale factor index %d outside 0..63", what, where(u).c_str(), b, s);
+    }
+  }
+  return C1_OK;
+}
+
+// the five field arrays of `units` frame fields packed in one allocation, in this order (one copy moves them all; q stays
+// 16-byte aligned: it starts 432 * units bytes in)
+constexpr int64_t kFieldInts = 1 + 3 + 52 + 52 + 512;
+C1FieldPtrs field_layout(const int32_t *base, int64_t units) {
+  return C1FieldPtrs{base, base + units, base + 4 * units, base + 56 * units, base + 108 * units};
+}
+C1FieldPtrs field_unit(const C1FieldPtrs &p, int64_t u) {
+  return C1FieldPtrs{p.nbfu + u, p.modes + 3 * u, p.sfi + 52 * u, p.wl + 52 * u, p.q + 512 * u};
+}
 }  // namespace
 
 int c1_unpack_units(c1_ctx *ctx, const uint8_t *units, int64_t frames, int32_t *nbfu, int32_t *block_modes, int32_t *sfi,
@@ -1530,16 +1562,7 @@ int c1_dequantize_frames(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const
   if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "dequantize frames: frames must be 0 .. 2^20, got %lld", (long long)frames);
   if (frames == 0) return C1_OK;
   if (!nbfu || !block_modes || !sfi || !wl || !quantized || !coefs) return fail(C1_ERR_ARG, "dequantize frames: NULL argument");
-  // the indices the reference reads (BFUs below nBfu) must name table entries: BFU_START_*, WORD_LENGTH_BITS, SCALE_FACTORS
-  for (int64_t f = 0; f < frames; f++) {
-    const int32_t n = nbfu[f];
-    if (n < 0 || n > 52) return fail(C1_ERR_ARG, "dequantize frames: frame %lld: nBfu %d outside 0..52", (long long)f, n);
-    for (int b = 0; b < n; b++) {
-      const int32_t w = wl[52 * f + b], s = sfi[52 * f + b];
-      if (w < 0 || w > 15) return fail(C1_ERR_ARG, "dequantize frames: frame %lld BFU %d: word length index %d outside 0..15", (long long)f, b, w);
-      if (s < 0 || s > 63) return fail(C1_ERR_ARG, "dequantize frames: frame %lld BFU %d: scale factor index %d outside 0..63", (long long)f, b, s);
-    }
-  }
+  if ((rc = check_field_domain("dequantize frames", frames, 1, 0, nbfu, sfi, wl))) return rc;
   DeviceScratch ds;
   int32_t *dn, *dm, *ds_, *dw, *dq; float *dc;
   const size_t n = (size_t)frames;
@@ -1971,6 +1994,83 @@ int c1_decode_batch(c1_ctx *ctx, const uint8_t *units, int channels, int64_t fra
   return C1_OK;
 }
 
+// ---- decode from frame fields (k_decode_fields) -------------------------------------------------------------------------
+namespace {
+int launch_decode_fields(c1_ctx *ctx, const C1FieldPtrs &cur, const C1FieldPtrs &prev, int channels, int64_t frames, int halo_frames,
+                         float *const *pcm) {
+  C1DecodeFieldsLaunch L;
+  memset(&L, 0, sizeof L);
+  L.cur = cur;
+  L.prev = halo_frames ? prev : cur;
+  L.channels = channels;
+  L.frames = frames;
+  L.halo_frames = halo_frames;
+  L.tables = ctx->d_tables;
+  for (int c = 0; c < channels; c++) L.pcm[c] = pcm[c];
+  { ScopedTiming t(ctx, K_DECODE_FIELDS); c1k_launch_decode_fields(L, ctx->stream); }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+}  // namespace
+
+int c1_decode_fields_device(c1_ctx *ctx, int channels, int64_t frames, int halo_frames, const int32_t *nbfu,
+                            const int32_t *block_modes, const int32_t *sfi, const int32_t *wl, const int32_t *quantized,
+                            float *const *pcm) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "decode fields: frames must be 0 .. 2^27, got %lld", (long long)frames);
+  if (halo_frames < 0 || halo_frames > 1) return fail(C1_ERR_ARG, "decode fields: halo_frames must be 0 or 1, got %d", halo_frames);
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if (frames == 0) return C1_OK;
+  if (!nbfu || !block_modes || !sfi || !wl || !quantized || !pcm) return fail(C1_ERR_ARG, "decode fields: NULL argument");
+  if ((uintptr_t)quantized & 15) return fail(C1_ERR_ARG, "decode fields: quantized must be 16-byte aligned on the device");
+  if (((uintptr_t)nbfu | (uintptr_t)block_modes | (uintptr_t)sfi | (uintptr_t)wl) & 3)
+    return fail(C1_ERR_ARG, "decode fields: field arrays must be 4-byte aligned on the device");
+  for (int c = 0; c < channels; c++) {
+    if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if ((uintptr_t)pcm[c] & 15) return fail(C1_ERR_ARG, "pcm[%d] must be 16-byte aligned on the device", c);
+  }
+  const C1FieldPtrs cur{nbfu, block_modes, sfi, wl, quantized};
+  const C1FieldPtrs prev = halo_frames ? field_unit(cur, -(int64_t)channels) : cur;
+  return launch_decode_fields(ctx, cur, prev, channels, frames, halo_frames, pcm);
+}
+
+int c1_decode_fields_batch(c1_ctx *ctx, int channels, int64_t frames, int halo_frames, const int32_t *nbfu,
+                           const int32_t *block_modes, const int32_t *sfi, const int32_t *wl, const int32_t *quantized,
+                           float *const *pcm) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (halo_frames < 0 || halo_frames > 1) return fail(C1_ERR_ARG, "decode fields: halo_frames must be 0 or 1, got %d", halo_frames);
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "decode fields: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!nbfu || !block_modes || !sfi || !wl || !quantized || !pcm) return fail(C1_ERR_ARG, "decode fields: NULL argument");
+  for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  const int64_t h = (int64_t)halo_frames * channels, units = frames * channels + h;
+  nbfu -= h; block_modes -= 3 * h; sfi -= 52 * h; wl -= 52 * h; quantized -= 512 * h;      // the halo's fields first
+  if ((rc = check_field_domain("decode fields", units, channels, -halo_frames, nbfu, sfi, wl))) return rc;
+  DeviceScratch ds;
+  int32_t *d; float *dp;
+  const size_t per = (size_t)frames * 512;
+  if ((rc = ds.alloc(&d, (size_t)(kFieldInts * units))) || (rc = ds.alloc(&dp, per * channels))) return rc;
+  const C1FieldPtrs all = field_layout(d, units);
+  HIP_TRY(hipMemcpyAsync((void *)all.nbfu, nbfu, (size_t)units * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync((void *)all.modes, block_modes, 3 * (size_t)units * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync((void *)all.sfi, sfi, 52 * (size_t)units * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync((void *)all.wl, wl, 52 * (size_t)units * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync((void *)all.q, quantized, 512 * (size_t)units * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) dptr[c] = dp + per * c;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if ((rc = launch_decode_fields(ctx, field_unit(all, h), all, channels, frames, halo_frames, dptr))) return rc;
+  for (int c = 0; c < channels; c++) HIP_TRY(hipMemcpyAsync(pcm[c], dptr[c], per * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 // ---- one batch over several devices ------------------------------------------------------------------------------------
 namespace {
 // Contexts for the *_multi entry points: one per shard for the duration of a call, checked out of a process-wide pool and
@@ -2296,15 +2396,78 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   return C1_OK;
 }
 
+// The decoded state after a frame is a function of that frame alone, so the stream keeps its previous frame: as a unit after a
+// unit push (d_prev, k_decode's halo), as fields after a field push.  Fields live in two buffers used in turn (d_fields), so
+// that a push reads its halo from the previous push's buffer while it writes its own; after a unit push the fields of d_prev
+// are made by k_unpack_units when a field push needs them (d_prev_fields).
 struct c1_dec_stream {
   c1_ctx *ctx;
   int channels;
   bool have_prev = false;
+  bool prev_is_unit = false;   // the previous push was units: d_prev holds the previous frame
   uint8_t *d_prev = nullptr;   // channels units of the previous frame
   uint8_t *d_units = nullptr;
   float *d_pcm = nullptr;
   int64_t cap_frames = 0;
+  C1FieldPtrs prev_fields = {nullptr, nullptr, nullptr, nullptr, nullptr};   // channels units; nbfu NULL: not made yet
+  int32_t *d_fields[2] = {nullptr, nullptr};   // kFieldInts per unit, field_layout over the push's units
+  int64_t fields_cap[2] = {0, 0};              // units
+  int fields_next = 0;
+  int32_t *d_prev_fields = nullptr;            // channels units, field_layout
+  int32_t *h_stage = nullptr;                  // page-locked staging of a field push (one host-to-device copy)
+  int64_t stage_cap = 0;                       // units
 };
+
+namespace {
+int dec_stream_reserve(c1_dec_stream *s, int64_t frames) {
+  const size_t ub = (size_t)s->channels * C1_UNIT_BYTES;
+  if (frames > s->cap_frames) {
+    if (s->d_units) { hipFree(s->d_units); hipFree(s->d_pcm); }
+    s->d_units = nullptr; s->d_pcm = nullptr; s->cap_frames = 0;
+    HIP_TRY(hipMalloc(&s->d_units, ub * (frames + 1)));
+    HIP_TRY(hipMalloc(&s->d_pcm, (size_t)s->channels * frames * 512 * sizeof(float)));
+    s->cap_frames = frames;
+  }
+  return C1_OK;
+}
+// the fields buffer of this push (units = frames * channels), never the one the previous push left its last frame in
+int dec_stream_fields(c1_dec_stream *s, int64_t units, int32_t **out) {
+  const int p = s->fields_next;
+  if (units > s->fields_cap[p]) {
+    if (s->d_fields[p]) hipFree(s->d_fields[p]);
+    s->d_fields[p] = nullptr; s->fields_cap[p] = 0;
+    HIP_TRY(hipMalloc(&s->d_fields[p], (size_t)(kFieldInts * units) * sizeof(int32_t)));
+    s->fields_cap[p] = units;
+  }
+  *out = s->d_fields[p];
+  return C1_OK;
+}
+// decode `frames` frames whose fields are at `cur` (layout over frames * channels units) from the stream's history, then make
+// the last of them the history; downloads the PCM and synchronises
+int dec_stream_decode_fields(c1_dec_stream *s, const C1FieldPtrs &cur, int64_t frames, float *const *pcm) {
+  c1_ctx *ctx = s->ctx;
+  int rc;
+  if (s->have_prev && !s->prev_fields.nbfu) {      // the previous frame as fields: unpack the unit the last push ended with
+    if (!s->d_prev_fields) HIP_TRY(hipMalloc(&s->d_prev_fields, (size_t)(kFieldInts * s->channels) * sizeof(int32_t)));
+    const C1FieldPtrs pf = field_layout(s->d_prev_fields, s->channels);
+    c1k_launch_unpack_units(s->d_prev, s->channels, (int32_t *)pf.nbfu, (int32_t *)pf.modes, (int32_t *)pf.sfi, (int32_t *)pf.wl,
+                            (int32_t *)pf.q, ctx->stream);
+    s->prev_fields = pf;
+  }
+  float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < s->channels; c++) dptr[c] = s->d_pcm + (size_t)c * s->cap_frames * 512;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if ((rc = launch_decode_fields(ctx, cur, s->prev_fields, s->channels, frames, s->have_prev ? 1 : 0, dptr))) return rc;
+  s->prev_fields = field_unit(cur, (frames - 1) * s->channels);
+  s->fields_next ^= 1;
+  s->have_prev = true;
+  s->prev_is_unit = false;
+  for (int c = 0; c < s->channels; c++)
+    HIP_TRY(hipMemcpyAsync(pcm[c], dptr[c], (size_t)frames * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+}  // namespace
 
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out) {
   CTX_GUARD(ctx);
@@ -2329,13 +2492,23 @@ int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units, int64_t frames, f
   if (frames < 0) return fail(C1_ERR_ARG, "frames must be >= 0");
   if (frames == 0) return C1_OK;
   if (!units || !pcm) return fail(C1_ERR_ARG, "units or pcm is NULL");
+  for (int c = 0; c < s->channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
   const size_t ub = (size_t)s->channels * C1_UNIT_BYTES;
-  if (frames > s->cap_frames) {
-    if (s->d_units) { hipFree(s->d_units); hipFree(s->d_pcm); }
-    s->d_units = nullptr; s->d_pcm = nullptr; s->cap_frames = 0;
-    HIP_TRY(hipMalloc(&s->d_units, ub * (frames + 1)));
-    HIP_TRY(hipMalloc(&s->d_pcm, (size_t)s->channels * frames * 512 * sizeof(float)));
-    s->cap_frames = frames;
+  if ((rc = dec_stream_reserve(s, frames))) return rc;
+  if (s->have_prev && !s->prev_is_unit) {
+    // the previous frame is held as fields, which a unit cannot stand in for: unpack this push's units and decode them
+    // from fields too (k_unpack_units + k_decode_fields decode any unit exactly as k_decode does)
+    const int64_t units_n = frames * s->channels;
+    int32_t *d;
+    if ((rc = dec_stream_fields(s, units_n, &d))) return rc;
+    const C1FieldPtrs cur = field_layout(d, units_n);
+    HIP_TRY(hipMemcpyAsync(s->d_units + ub, units, ub * frames, hipMemcpyHostToDevice, ctx->stream));
+    c1k_launch_unpack_units(s->d_units + ub, units_n, (int32_t *)cur.nbfu, (int32_t *)cur.modes, (int32_t *)cur.sfi, (int32_t *)cur.wl,
+                            (int32_t *)cur.q, ctx->stream);
+    HIP_TRY(hipMemcpyAsync(s->d_prev, s->d_units + ub * frames, ub, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = dec_stream_decode_fields(s, cur, frames, pcm))) return rc;
+    s->prev_is_unit = true;                        // d_prev and prev_fields both hold the last frame now: either kind may follow
+    return C1_OK;
   }
   if (s->have_prev) HIP_TRY(hipMemcpyAsync(s->d_units, s->d_prev, ub, hipMemcpyDeviceToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(s->d_units + ub, units, ub * frames, hipMemcpyHostToDevice, ctx->stream));
@@ -2344,12 +2517,45 @@ int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units, int64_t frames, f
   if ((rc = c1_decode_device(ctx, s->d_units + ub, s->channels, frames, s->have_prev ? 1 : 0, dptr))) return rc;
   HIP_TRY(hipMemcpyAsync(s->d_prev, s->d_units + ub * frames, ub, hipMemcpyDeviceToDevice, ctx->stream));
   s->have_prev = true;
-  for (int c = 0; c < s->channels; c++) {
-    if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  s->prev_is_unit = true;
+  s->prev_fields.nbfu = nullptr;
+  for (int c = 0; c < s->channels; c++)
     HIP_TRY(hipMemcpyAsync(pcm[c], dptr[c], (size_t)frames * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
+}
+
+int c1_dec_stream_push_fields(c1_dec_stream *s, int64_t frames, const int32_t *nbfu, const int32_t *block_modes,
+                              const int32_t *sfi, const int32_t *wl, const int32_t *quantized, float *const *pcm) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (frames < 0 || frames > kMaxStageFrames) return fail(C1_ERR_ARG, "decode fields: frames must be 0 .. 2^20, got %lld", (long long)frames);
+  if (frames == 0) return C1_OK;
+  if (!nbfu || !block_modes || !sfi || !wl || !quantized || !pcm) return fail(C1_ERR_ARG, "decode fields: NULL argument");
+  for (int c = 0; c < s->channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  const int64_t units_n = frames * s->channels;
+  if ((rc = check_field_domain("decode fields", units_n, s->channels, 0, nbfu, sfi, wl))) return rc;
+  if ((rc = dec_stream_reserve(s, frames))) return rc;
+  if (units_n > s->stage_cap) {
+    if (s->h_stage) hipHostFree(s->h_stage);
+    s->h_stage = nullptr; s->stage_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)&s->h_stage, (size_t)(kFieldInts * units_n) * sizeof(int32_t), hipHostMallocDefault));
+    s->stage_cap = units_n;
+  }
+  int32_t *d;
+  if ((rc = dec_stream_fields(s, units_n, &d))) return rc;
+  // one copy: the five arrays staged in the device buffer's layout (the last push's copy has completed: pushes synchronise)
+  const C1FieldPtrs st = field_layout(s->h_stage, units_n);
+  memcpy((void *)st.nbfu, nbfu, (size_t)units_n * sizeof(int32_t));
+  memcpy((void *)st.modes, block_modes, 3 * (size_t)units_n * sizeof(int32_t));
+  memcpy((void *)st.sfi, sfi, 52 * (size_t)units_n * sizeof(int32_t));
+  memcpy((void *)st.wl, wl, 52 * (size_t)units_n * sizeof(int32_t));
+  memcpy((void *)st.q, quantized, 512 * (size_t)units_n * sizeof(int32_t));
+  HIP_TRY(hipMemcpyAsync(d, s->h_stage, (size_t)(kFieldInts * units_n) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  return dec_stream_decode_fields(s, field_layout(d, units_n), frames, pcm);
 }
 
 int c1_dec_stream_destroy(c1_dec_stream *s) {
@@ -2359,6 +2565,9 @@ int c1_dec_stream_destroy(c1_dec_stream *s) {
   if (s->d_prev) hipFree(s->d_prev);
   if (s->d_units) hipFree(s->d_units);
   if (s->d_pcm) hipFree(s->d_pcm);
+  for (int p = 0; p < 2; p++) if (s->d_fields[p]) hipFree(s->d_fields[p]);
+  if (s->d_prev_fields) hipFree(s->d_prev_fields);
+  if (s->h_stage) hipHostFree(s->h_stage);
   delete s;
   return C1_OK;
 }

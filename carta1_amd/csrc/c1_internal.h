@@ -145,6 +145,21 @@ struct C1DecodeLaunch {
   int run_frames;        // consecutive units of one channel a wave decodes (set by the launcher)
 };
 
+// frame fields in the layout c1_unpack_units writes: unit u at nbfu[u], modes[3u], sfi[52u], wl[52u], q[512u] (q 16-byte aligned)
+struct C1FieldPtrs {
+  const int32_t *nbfu, *modes, *sfi, *wl, *q;
+};
+struct C1DecodeFieldsLaunch {
+  C1FieldPtrs cur;       // frame f >= 0 of channel c: unit f * channels + c
+  C1FieldPtrs prev;      // halo_frames 1: the frame before frame 0, unit c (need not precede `cur` in memory)
+  int channels;
+  int64_t frames;
+  int halo_frames;
+  const C1DevTables *tables;
+  float *pcm[C1_MAX_CHANNELS];
+  int run_frames;        // consecutive frames of one channel a wave decodes (set by the launcher)
+};
+
 // Run length of the frame-walking kernels: consecutive frames of one channel a wave walks, carrying the filter state
 // (one extra warm-up frame per run).  Measured on MI355X (1 M stereo frames, A/B in one session): 64-frame runs beat
 // runs sized to fill the wave slots exactly once (205 frames: every wave then finishes at the same moment, and the
@@ -235,6 +250,10 @@ void c1k_launch_defer_compact(const C1EncodeLaunch &L, uint32_t *list, uint32_t 
 // open_masks -> a dense list of units (counts[0] = entries), for the exact pre-pass of the units with an open scale factor
 void c1k_launch_open_compact(const C1EncodeLaunch &L, uint32_t *list, uint32_t *count, hipStream_t stream);
 void c1k_launch_decode(const C1DecodeLaunch &L, bool binary32, hipStream_t stream);   // binary32: opt-in, PCM within rounding noise of the reference
+// the decode() closure from frame fields (c1_k_decode_fields.hip), the reference's number model always.  Any int32 field value
+// is memory-safe (nbfu clamped to 0..52, wl & 15, sfi & 63 on the read path); the output is the reference's for nbfu 0..52 and,
+// below nbfu, wl 0..15 and sfi 0..63
+void c1k_launch_decode_fields(const C1DecodeFieldsLaunch &L, hipStream_t stream);
 // kind_mask: bit k = fill the 512-frame segments with (segment & 3) == k (15 = all)
 void c1k_launch_generate_white(const uint32_t *frame_states, int64_t frames, float *pcm, int kind_mask, double amp, hipStream_t stream);
 void c1k_launch_generate_pink(const uint32_t *segment_states, int64_t frames, float *pcm, int kind_mask, hipStream_t stream);

@@ -552,6 +552,69 @@ napi_value DecStreamPush(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return arr;
 }
+// frame fields (Int32Array nbfu, blockModes, sfi, wl, quantized; unit index frame * channels + channel) of whole frames:
+// the frame count, or -1 after throwing
+int64_t get_fields(napi_env env, const napi_value *argv, int32_t channels, int32_t halo, const int32_t **f, const char *what) {
+  void *a[5];
+  size_t n[5];
+  for (int i = 0; i < 5; i++) if (!get_typed(env, argv[i], napi_int32_array, &a[i], &n[i])) return -1;
+  const size_t units = n[0];
+  if (channels < 1 || channels > 2 || units % (size_t)channels || n[1] != 3 * units || n[2] != 52 * units || n[3] != 52 * units ||
+      n[4] != 512 * units || halo < 0 || (size_t)halo * channels > units) {
+    std::string msg = std::string(what) + ": nBfu, 3 block modes, 52 sfi, 52 wl and 512 mantissas per frame and channel";
+    napi_throw_type_error(env, nullptr, msg.c_str());
+    return -1;
+  }
+  static const size_t per[5] = {1, 3, 52, 52, 512};
+  for (int i = 0; i < 5; i++) f[i] = static_cast<const int32_t *>(a[i]) + per[i] * (size_t)halo * channels;
+  return (int64_t)(units / channels) - halo;
+}
+napi_value pcm_array(napi_env env, int32_t channels, int64_t frames, float **p) {
+  napi_value arr;
+  if (napi_create_array_with_length(env, channels, &arr) != napi_ok) return nullptr;
+  for (int c = 0; c < channels; c++) {
+    napi_value ta = make_f32(env, (size_t)frames * 512, &p[c]);
+    if (!ta || napi_set_element(env, arr, c, ta) != napi_ok) return nullptr;
+  }
+  return arr;
+}
+// (ctx, Int32Array nbfu, blockModes, sfi, wl, quantized, channels, haloFrames) -> [Float32Array pcm per channel]
+napi_value DecodeFieldsBatch(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  c1_ctx *ctx;
+  int32_t channels = 1, halo = 0;
+  if (!get_external(env, argv[0], &ctx)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[6], &channels));
+  NAPI_OK(napi_get_value_int32(env, argv[7], &halo));
+  const int32_t *f[5];
+  const int64_t frames = get_fields(env, argv + 1, channels, halo, f, "decodeFieldsBatch");
+  if (frames < 0) return nullptr;
+  float *p[2] = {nullptr, nullptr};
+  napi_value arr = pcm_array(env, channels, frames, p);
+  if (!arr) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_decode_fields_batch(ctx, channels, frames, halo, f[0], f[1], f[2], f[3], f[4], p);
+  if (rc) return throw_c1(env, rc);
+  return arr;
+}
+// (stream, Int32Array nbfu, blockModes, sfi, wl, quantized, channels) -> [Float32Array pcm per channel]
+napi_value DecStreamPushFields(napi_env env, napi_callback_info info) {
+  napi_value argv[7];
+  if (!get_args(env, info, 7, argv)) return nullptr;
+  c1_dec_stream *s;
+  int32_t channels = 1;
+  if (!get_external(env, argv[0], &s)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[6], &channels));
+  const int32_t *f[5];
+  const int64_t frames = get_fields(env, argv + 1, channels, 0, f, "decStreamPushFields");
+  if (frames < 0) return nullptr;
+  float *p[2] = {nullptr, nullptr};
+  napi_value arr = pcm_array(env, channels, frames, p);
+  if (!arr) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_dec_stream_push_fields(s, frames, f[0], f[1], f[2], f[3], f[4], p);
+  if (rc) return throw_c1(env, rc);
+  return arr;
+}
 
 // ---- the single-stage functions of the reference's export surface (codec/index.js:30-35,42) ---------------------------
 napi_value Quantize(napi_env env, napi_callback_info info) {      // (ctx, Float32Array, sfi, bits) -> Int32Array
@@ -781,6 +844,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamCreate", nullptr, DecStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamPush", nullptr, DecStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decStreamPushFields", nullptr, DecStreamPushFields, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decodeFieldsBatch", nullptr, DecodeFieldsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"quantize", nullptr, Quantize, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"dequantize", nullptr, Dequantize, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fft", nullptr, Fft, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -1,24 +1,21 @@
 // decode(bufferPool) -> frame closure (codec/pipeline/decoder.js:408-411): dequantization, IMDCT with
 // overlap-add and QMF synthesis run as one HIP kernel; decoder state lives in the pool's native stream.
 import { BufferPool } from '../core/buffers.js'
-import { SOUND_UNIT_SIZE, SPECS_PER_BFU } from '../core/constants.js'
-import { serializeFrame } from '../io/serialization.js'
+import { SPECS_PER_BFU } from '../core/constants.js'
 import { native, context } from '../native.js'
 import { throwError } from '../utils.js'
 
+// A sound unit (Uint8Array) is decoded from its bytes; a frameData object from its fields as they stand, without
+// serializeFrame, so that fields no unit can carry (an nBfu outside BFU_AMOUNTS, a band mode of 1, mantissas beyond their word
+// length) decode as the reference decodes them.  Both kinds continue the same native stream.
 export function decode(bufferPool = new BufferPool()) {
   if (!bufferPool) throwError('imdctStage: bufferPool is required')
   return (frameData) => {
     const addon = native()
     if (!bufferPool.decoderStream) bufferPool.decoderStream = addon.decStreamCreate(context(), 1)
-    let unit
-    if (frameData instanceof Uint8Array) unit = frameData
-    else if (!frameData.nBfu) {
-      // the reference's padding frame (processor.js:300-308): no BFUs -> all-zero spectrum
-      unit = new Uint8Array(SOUND_UNIT_SIZE)
-      unit[0] = 0xac
-    } else unit = serializeFrame(frameData)
-    return addon.decStreamPush(bufferPool.decoderStream, unit, 1)[0]
+    if (frameData instanceof Uint8Array) return addon.decStreamPush(bufferPool.decoderStream, frameData, 1)[0]
+    const f = frameFields(frameData)
+    return addon.decStreamPushFields(bufferPool.decoderStream, f.nbfu, f.modes, f.sfi, f.wl, f.q, 1)[0]
   }
 }
 
@@ -29,19 +26,28 @@ export function decode(bufferPool = new BufferPool()) {
 // (include/carta1_hip.h states those histories): bit-identical to carrying the reference's buffers along.
 const isLong = (mode) => (mode === 0 ? 0 : 1)            // a band is long only when its mode is exactly 0 (decoder.js:82)
 
+// frameData -> the native frame fields (Int32Array nbfu[1], modes[3], sfi[52], wl[52], q[512]): what the reference's
+// dequantizationStage reads of it (decoder.js:63-95) and nothing else -- BFUs at or above nBfu and the mantissas of BFUs with
+// word length 0 stay zero.  Indices the device cannot name are left for the native call to reject.
+function frameFields(frameData) {
+  const { nBfu, scaleFactorIndices, wordLengthIndices, quantizedCoefficients, blockModes } = frameData
+  const sfi = new Int32Array(52), wl = new Int32Array(52), q = new Int32Array(512)
+  for (let b = 0, at = 0; b < 52; at += SPECS_PER_BFU[b], b++) {
+    if (!(b < nBfu)) continue
+    sfi[b] = scaleFactorIndices[b]
+    wl[b] = wordLengthIndices[b]
+    if (wl[b] === 0) continue
+    const src = quantizedCoefficients[b], n = Math.min(src.length, SPECS_PER_BFU[b])
+    for (let i = 0; i < n; i++) q[at + i] = src[i]               // ToInt32 on the store, as Int32Array.from converts
+  }
+  return { nbfu: Int32Array.of(nBfu), modes: Int32Array.from(blockModes, isLong), sfi, wl, q }
+}
+
 export function dequantizationStage() {
   return (frameData) => {
-    const { nBfu, scaleFactorIndices, wordLengthIndices, quantizedCoefficients, blockModes } = frameData
-    const sfi = new Int32Array(52), wl = new Int32Array(52), q = new Int32Array(512)
-    for (let b = 0, at = 0; b < 52; at += SPECS_PER_BFU[b], b++) {
-      if (b >= nBfu) continue
-      sfi[b] = scaleFactorIndices[b]
-      wl[b] = wordLengthIndices[b]
-      if (wl[b] !== 0) q.set(Int32Array.from(quantizedCoefficients[b].slice(0, SPECS_PER_BFU[b])), at)
-    }
-    const modes = Int32Array.from(blockModes, isLong)
-    const coefficients = native().dequantizeFrames(context(), Int32Array.of(nBfu), modes, sfi, wl, q)
-    return { coefficients, blockModes }
+    const f = frameFields(frameData)
+    const coefficients = native().dequantizeFrames(context(), f.nbfu, f.modes, f.sfi, f.wl, f.q)
+    return { coefficients, blockModes: frameData.blockModes }
   }
 }
 

@@ -110,8 +110,10 @@ int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stre
 int c1_ctx_destroy(c1_ctx *ctx);
 int c1_ctx_synchronize(c1_ctx *ctx);
 /* milliseconds the device spent in the named kernel during the most recent *_device call on this
- * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), or in the most recent c1_pack_units call
- * ("pack_units"), from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1) must have been set before the call */
+ * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), in the most recent c1_pack_units call
+ * ("pack_units"), or in the most recent decode from frame fields -- c1_decode_fields_*, c1_dec_stream_push_fields or a
+ * unit push that follows one ("decode_fields") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
+ * must have been set before the call */
 int c1_ctx_set_profiling(c1_ctx *ctx, int enabled);
 int c1_ctx_kernel_ms(c1_ctx *ctx, const char *name, double *ms, int *launches);
 
@@ -213,6 +215,12 @@ int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
 int c1_dec_stream_destroy(c1_dec_stream *s);
+/* decode() over frame fields (below, c1_decode_fields_*) on the same stream: one frame per channel, unit index = frame *
+ * channels + channel in every array.  Continues the stream c1_dec_stream_push decodes: any interleaving of unit pushes and
+ * field pushes decodes exactly as one call over the concatenated frames would (the decoded state after a frame is a function
+ * of that frame alone).  The domain is validated as c1_decode_fields_batch validates it; frames 0 .. 2^20 per call. */
+int c1_dec_stream_push_fields(c1_dec_stream *s, int64_t frames, const int32_t *nbfu, const int32_t *block_modes,
+                              const int32_t *sfi, const int32_t *wl, const int32_t *quantized, float *const *pcm /* host */);
 
 /* ---- device-resident synthetic input for measurement ------------- */
 enum { C1_SIGNAL_WHITE = 0, C1_SIGNAL_PINK_BURSTS = 1, C1_SIGNAL_MIXED = 2, C1_SIGNAL_PARTIALS = 3 };
@@ -340,6 +348,31 @@ int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const in
  *     the buffer, bitstream.js:15-38); then bytes 209..211 are zeroed.  Bits after the end of the stream are zero. */
 int c1_pack_units(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi,
                   const int32_t *wl, const int32_t *quantized, uint8_t *units);
+
+/* The decode() frame closure (codec/pipeline/decoder.js:408-411: dequantizationStage, imdctStage, qmfSynthesisStage) over frame
+ * fields in the layout c1_unpack_units writes, in one device launch: what the reference's decode() computes for a frameData
+ * object, also for fields serializeFrame would not carry (an nBfu outside BFU_AMOUNTS, band modes other than 0 and the
+ * short codes, mantissas beyond their word length).  channels 1 or 2; unit index = frame * channels + channel in every array
+ * (the interleave of c1_unpack_units over stereo units).  halo_frames 0 or 1: one frame of fields per channel precedes each
+ * pointer, the stream's previous frame, whose fields rebuild imdctOverlap and qmfDelays; without one the state is a fresh
+ * BufferPool's zeros.  pcm[c] = frames * 512 samples.
+ * Number model: the reference's always (binary64 operations, binary32 at every typed-array store); c1_ctx_set_decode_precision
+ * does not apply.  Dequantization is Float32((q * SCALE_FACTORS[sfi]) / ((1 << (bits - 1)) - 1)) for any int32 q, with the
+ * semantics of c1_dequantize_frames: entries at or above nBfu are never read, nor are the mantissas of BFUs with word length 0,
+ * and a band is long only when its mode is exactly 0.
+ * Domain: nbfu 0..52; below nbfu, wl 0..15 and sfi 0..63; block modes and mantissas any int32. */
+/* device pointers, asynchronous on the context's stream; frames 0 .. 2^27 per channel; quantized 16-byte aligned, pcm[c]
+ * 16-byte aligned.  Fields outside the domain are not checked here: the output is then unspecified, but every read stays in
+ * bounds for any int32 value (nbfu is clamped to 0..52, wl & 15 and sfi & 63 are what is read). */
+int c1_decode_fields_device(c1_ctx *ctx, int channels, int64_t frames, int halo_frames, const int32_t *nbfu,
+                            const int32_t *block_modes, const int32_t *sfi, const int32_t *wl, const int32_t *quantized,
+                            float *const *pcm);
+/* host pointers, synchronous; frames 0 .. 2^20 per channel.  Validates the domain over the halo and the frames first:
+ * C1_ERR_ARG naming the frame (-1 for the halo; and the channel when channels is 2) and the BFU, worded as
+ * c1_dequantize_frames words it; also for a bad halo, a NULL pointer or frames out of range. */
+int c1_decode_fields_batch(c1_ctx *ctx, int channels, int64_t frames, int halo_frames, const int32_t *nbfu,
+                           const int32_t *block_modes, const int32_t *sfi, const int32_t *wl, const int32_t *quantized,
+                           float *const *pcm);
 
 /* ---- stage taps for bring-up and stage-level parity tests (device pointers) ---------------- */
 /* bands: frames*channels*512 floats (low128|mid128|high256 per unit index, before windowing);
