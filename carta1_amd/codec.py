@@ -523,6 +523,12 @@ class EncoderStream:
                                                   units.ctypes.data))
         return units
 
+    def set_options(self, options):
+        """The options of every channel from the next push on, as the reference's encode() reads them on every call; the
+        stream goes on (include/carta1_hip.h, c1_enc_stream_set_options).  Invalid options raise and change nothing."""
+        opts = options.to_c()
+        capi.check(capi.load().c1_enc_stream_set_options(self._h, C.byref(opts)))
+
     def close(self):
         if self._h:
             capi.load().c1_enc_stream_destroy(self._h)

@@ -2323,6 +2323,29 @@ int c1_decode_wav16_batch(c1_ctx *ctx, const uint8_t *units, int channels, int64
 }
 
 // ---- stateful streams -------------------------------------------------------------------------------
+// What an encode() closure keeps besides the PCM is its detection history (bufferPool.transientDetection, encoder.js:142):
+// the magnitudes of the last frame detection ran on, a function of that frame's bands.  A push with halo = 2 rebuilds them
+// from the previous frame, which is right whenever that frame was detected.  After fixed modes it was not: the history is
+// then a fresh pool's zeros (detection never ran) or the bands of the last detected frame, kept here since the switch to
+// fixed modes, and the first frame of the next push under detection is encoded by the stage kernels against them.
+enum EncHistory { HIST_PREV = 0, HIST_ZEROS = 1, HIST_STORED = 2 };
+
+// scratch of the switch frame, one allocation carved per stream on first use; channels-interleaved where several
+struct EncSwitchScratch {
+  float *bands;      // 2 frames x channels x 512: the bands of t-1 and t (t-1's alone at a detection -> fixed switch)
+  float *coefs;      // 2 frames x channels x 512, and side / alloc: the encode taps behind `bands`
+  uint8_t *side, *alloc;
+  float *rows;       // 2 x 512: [halo, t] for the block selection, then [t-1, t] for the MDCT
+  float *mags;       // 2 x 256
+  int32_t *modes;    // channels x 3
+  uint8_t *mode_byte;
+  uint32_t *lists;   // 4 + 2
+  float *coef1;      // one frame: coefficients, side, allocation, candidates, work lists, fields
+  uint8_t *side1, *alloc1, *cand1;
+  uint32_t *work1;
+  int32_t *nbfu, *sfi, *wl, *q;
+};
+
 struct c1_enc_stream {
   c1_ctx *ctx;
   int channels;
@@ -2331,7 +2354,107 @@ struct c1_enc_stream {
   float *d_buf = nullptr;
   uint8_t *d_units = nullptr;
   int64_t cap_frames = 0;
+  int64_t pushed = 0;              // frames per channel encoded so far
+  EncHistory hist = HIST_PREV;     // where the detection history of the next frame lives (same for every channel)
+  float *d_stored = nullptr;       // channels x 512: the bands of the last detected frame (HIST_STORED), from d_sw's block
+  void *d_sw_block = nullptr;
+  EncSwitchScratch sw;
 };
+
+namespace {
+bool opts_detect(const c1_encode_options &o) { return o.fixed_block_modes[0] < 0; }
+
+int enc_stream_scratch(c1_enc_stream *s) {
+  if (s->d_sw_block) return C1_OK;
+  const size_t C = (size_t)s->channels;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
+  const size_t o_stored = take(C * 512 * 4), o_bands = take(2 * C * 512 * 4), o_coefs = take(2 * C * 512 * 4),
+               o_side = take(2 * C * kSideBytes), o_alloc = take(2 * C * kAllocBytes), o_rows = take(2 * 512 * 4),
+               o_mags = take(2 * 256 * 4), o_modes = take(C * 3 * 4), o_mb = take(1), o_lists = take(6 * 4), o_c1 = take(512 * 4),
+               o_s1 = take(kSideBytes), o_a1 = take(kAllocBytes), o_k1 = take(kCandidateBytes), o_w1 = take((4 + 8) * 4),
+               o_n = take(4), o_sfi = take(52 * 4), o_wl = take(52 * 4), o_q = take(512 * 4);
+  void *block = nullptr;
+  HIP_TRY(hipMalloc(&block, at));
+  char *b = static_cast<char *>(block);
+  s->d_sw_block = block;
+  s->d_stored = reinterpret_cast<float *>(b + o_stored);
+  EncSwitchScratch &w = s->sw;
+  w.bands = reinterpret_cast<float *>(b + o_bands);
+  w.coefs = reinterpret_cast<float *>(b + o_coefs);
+  w.side = reinterpret_cast<uint8_t *>(b + o_side);
+  w.alloc = reinterpret_cast<uint8_t *>(b + o_alloc);
+  w.rows = reinterpret_cast<float *>(b + o_rows);
+  w.mags = reinterpret_cast<float *>(b + o_mags);
+  w.modes = reinterpret_cast<int32_t *>(b + o_modes);
+  w.mode_byte = reinterpret_cast<uint8_t *>(b + o_mb);
+  w.lists = reinterpret_cast<uint32_t *>(b + o_lists);
+  w.coef1 = reinterpret_cast<float *>(b + o_c1);
+  w.side1 = reinterpret_cast<uint8_t *>(b + o_s1);
+  w.alloc1 = reinterpret_cast<uint8_t *>(b + o_a1);
+  w.cand1 = reinterpret_cast<uint8_t *>(b + o_k1);
+  w.work1 = reinterpret_cast<uint32_t *>(b + o_w1);
+  w.nbfu = reinterpret_cast<int32_t *>(b + o_n);
+  w.sfi = reinterpret_cast<int32_t *>(b + o_sfi);
+  w.wl = reinterpret_cast<int32_t *>(b + o_wl);
+  w.q = reinterpret_cast<int32_t *>(b + o_q);
+  return C1_OK;
+}
+
+// QMF analysis of `frames` frames of every channel (pcm[c] at the first, `halo` frames of PCM before it) into s->sw.bands,
+// channels interleaved: the encoder's own bands tap (c1_qmf_analysis_batch's path), run with the stream's detection options
+// so that the options on the device stay as they are.  Device pointers, ordered on the context's stream.
+int enc_stream_bands(c1_enc_stream *s, const float *const *pcm, int64_t frames, int halo) {
+  return encode_device_impl(s->ctx, pcm, s->channels, frames, halo, &s->opts, nullptr, s->sw.bands, s->sw.coefs, s->sw.side,
+                            s->sw.alloc);
+}
+
+// The first frame t of a push under detection while the history is not the previous frame's: pcm[c] points at frame t with two
+// frames of history before it.  The reference's stages on the device, channel by channel: bands of t-1 and t (halo 1),
+// blockSelectorStage against the stored bands or a fresh pool's zeros, mdctStage with t-1's bands as the overlap,
+// quantizationStage, serializeFrame -> units[c * 212].
+int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *units) {
+  c1_ctx *ctx = s->ctx;
+  EncSwitchScratch &w = s->sw;
+  const int C = s->channels;
+  const float *prev[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < C; c++) prev[c] = pcm[c] - 512;
+  int rc = enc_stream_bands(s, prev, 2, 1);            // also puts s->opts on the device, which the allocation reads
+  if (rc) return rc;
+  for (int c = 0; c < C; c++) {
+    const float *bands_prev = w.bands + (size_t)c * 512, *bands_t = w.bands + (size_t)(C + c) * 512;
+    int32_t *modes = w.modes + 3 * c;
+    const int halo = s->hist == HIST_STORED ? 1 : 0;
+    if (halo) HIP_TRY(hipMemcpyAsync(w.rows, s->d_stored + (size_t)c * 512, 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(w.rows + 512 * halo, bands_t, 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    c1k_launch_block_modes_from_bands(ctx->d_tables, w.rows, 1, halo, s->opts.transient_threshold, w.mags, modes, ctx->stream);
+    HIP_TRY(hipMemcpyAsync(w.rows, bands_prev, 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(w.rows + 512, bands_t, 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    c1k_launch_stage_mode_lists(modes, 1, w.mode_byte, w.lists, ctx->stream);
+    C1EncodeLaunch L;
+    memset(&L, 0, sizeof L);
+    L.channels = 1;
+    L.frames = 1;
+    L.halo_frames = 1;
+    L.tables = ctx->d_tables;
+    L.opts = ctx->d_opts;
+    L.coefs = w.coef1;
+    L.side = w.side1;
+    c1k_launch_mdct_bands(L, w.rows, w.mode_byte, w.lists, ctx->stream);
+    c1k_launch_stage_scale_factors(ctx->d_tables, w.coef1, modes, 1, w.side1, ctx->stream);
+    L.alloc = w.alloc1;
+    L.cand = w.cand1;
+    L.work_count = w.work1;
+    L.work_list = w.work1 + 4;
+    L.sel_list = w.work1 + 4 + 7;
+    c1k_launch_allocate(L, ctx->stream);
+    c1k_launch_stage_fields(ctx->d_tables, w.coef1, modes, w.side1, w.alloc1, 1, w.nbfu, w.sfi, w.wl, w.q, ctx->stream);
+    c1k_launch_pack_units(w.nbfu, modes, w.sfi, w.wl, w.q, 1, units + (size_t)c * C1_UNIT_BYTES, ctx->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return C1_OK;
+}
+}  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
   CTX_GUARD(ctx);
@@ -2343,11 +2466,39 @@ int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opt
   if ((rc = build_encode_opts(*opts, &probe))) return rc;
   c1_enc_stream *s = new c1_enc_stream();
   s->ctx = ctx; s->channels = channels; s->opts = *opts; s->d_hist = nullptr;
+  s->hist = opts_detect(*opts) ? HIST_PREV : HIST_ZEROS;
   const size_t hb = (size_t)channels * 1024 * sizeof(float);
   hipError_t e = hipMalloc(&s->d_hist, hb);
   if (e == hipSuccess) e = hipMemsetAsync(s->d_hist, 0, hb, ctx->stream);   // zero history == stream start
   if (e != hipSuccess) { delete s; return fail(C1_ERR_HIP, "enc stream alloc: %s", hipGetErrorString(e)); }
   *out = s;
+  return C1_OK;
+}
+
+int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!opts) return fail(C1_ERR_ARG, "opts is NULL");
+  C1DevEncOpts probe;
+  if ((rc = build_encode_opts(*opts, &probe))) return rc;
+  if (opts_detect(s->opts) && !opts_detect(*opts) && s->hist == HIST_PREV) {
+    if (s->pushed > 0) {
+      // detection -> fixed modes: the history freezes at the last pushed frame's magnitudes; keep that frame's bands
+      if ((rc = enc_stream_scratch(s))) return rc;
+      const float *last[C1_MAX_CHANNELS] = {nullptr, nullptr};
+      for (int c = 0; c < s->channels; c++) last[c] = s->d_hist + 1024 * c + 512;
+      if ((rc = enc_stream_bands(s, last, 1, 1))) return rc;
+      HIP_TRY(hipMemcpyAsync(s->d_stored, s->sw.bands, (size_t)s->channels * 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      s->hist = HIST_STORED;
+    } else {
+      s->hist = HIST_ZEROS;
+    }
+  }
+  s->opts = *opts;
   return C1_OK;
 }
 
@@ -2360,6 +2511,11 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   if (frames < 0) return fail(C1_ERR_ARG, "frames must be >= 0");
   if (frames == 0) return C1_OK;
   if (!pcm || !units) return fail(C1_ERR_ARG, "pcm or units is NULL");
+  for (int c = 0; c < s->channels; c++)
+    if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  const bool detect = opts_detect(s->opts);
+  const bool switch_frame = detect && s->hist != HIST_PREV && s->pushed > 0;
+  if (switch_frame && (rc = enc_stream_scratch(s))) return rc;
   if (frames > s->cap_frames) {
     if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); }
     s->d_buf = nullptr; s->d_units = nullptr; s->cap_frames = 0;
@@ -2370,18 +2526,29 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   const size_t stride = (size_t)(s->cap_frames + 2) * 512;
   const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
   for (int c = 0; c < s->channels; c++) {
-    if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
     float *d = s->d_buf + stride * c;
     HIP_TRY(hipMemcpyAsync(d, s->d_hist + 1024 * c, 1024 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d + 1024, pcm[c], (size_t)frames * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     dptr[c] = d + 1024;
   }
-  if ((rc = encode_device_joined(ctx, dptr, s->channels, frames, 2, &s->opts, s->d_units))) return rc;
+  if (switch_frame) {
+    if ((rc = enc_stream_switch_frame(s, dptr, s->d_units))) return rc;
+    if (frames > 1) {
+      const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
+      for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + 512;
+      if ((rc = encode_device_joined(ctx, rest, s->channels, frames - 1, 2, &s->opts, s->d_units + (size_t)s->channels * C1_UNIT_BYTES)))
+        return rc;
+    }
+  } else if ((rc = encode_device_joined(ctx, dptr, s->channels, frames, 2, &s->opts, s->d_units))) {
+    return rc;
+  }
   for (int c = 0; c < s->channels; c++)   // new history = the last two frames of [history | pushed]
     HIP_TRY(hipMemcpyAsync(s->d_hist + 1024 * c, s->d_buf + stride * c + (size_t)frames * 512, 1024 * sizeof(float),
                            hipMemcpyDeviceToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(units, s->d_units, (size_t)s->channels * frames * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  s->pushed += frames;
+  if (detect) s->hist = HIST_PREV;
   return C1_OK;
 }
 
@@ -2392,6 +2559,7 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (s->d_hist) hipFree(s->d_hist);
   if (s->d_buf) hipFree(s->d_buf);
   if (s->d_units) hipFree(s->d_units);
+  if (s->d_sw_block) hipFree(s->d_sw_block);
   delete s;
   return C1_OK;
 }

@@ -220,6 +220,8 @@ void c1k_launch_qmf_synthesis_frames(const C1DevTables *tables, const float *ban
 // bands point at frame -halo; mags: (halo + frames) * 256 floats of scratch; modes: frames * 3 int32
 void c1k_launch_block_modes_from_bands(const C1DevTables *tables, const float *bands, int64_t frames, int halo, double threshold,
                                        float *mags, int32_t *modes, hipStream_t stream);
+// block modes (frames * 3 int32) -> k_mdct_bands' mode bytes (frames) and frame lists (4 + 2 * frames uint32); for a few frames
+void c1k_launch_stage_mode_lists(const int32_t *modes, int64_t frames, uint8_t *mode_bytes, uint32_t *lists, hipStream_t stream);
 // findScaleFactor per BFU -> side records (kSideBytes per frame) for c1k_launch_allocate
 void c1k_launch_stage_scale_factors(const C1DevTables *tables, const float *coefs, const int32_t *modes, int64_t frames, uint8_t *side,
                                     hipStream_t stream);

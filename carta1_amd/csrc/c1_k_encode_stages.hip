@@ -136,6 +136,26 @@ __global__ __launch_bounds__(C1_WAVE) void k_stage_fields(const C1DevTables *tab
   }
 }
 
+// ---- block modes -> the MDCT's inputs ----------------------------------------------------------------------------------
+// k_mdct_bands reads a mode byte per unit (2 bits per band: 2, 2, 3 for a short band, as c1_mdct_batch packs them) and two
+// frame lists, long units (every band mode 0) and the others, with their counts in lists[0] and lists[1].  The stream's
+// option-switch frame has its modes on the device only (k_stage_decide): one lane walks its few frames in order.
+__global__ void k_stage_mode_lists(const int32_t *__restrict__ modes, int64_t frames, uint8_t *__restrict__ mode_bytes,
+                                   uint32_t *__restrict__ lists) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t n_long = 0u, n_short = 0u;
+  for (int64_t f = 0; f < frames; f++) {
+    const int m0 = modes[3 * f] ? 2 : 0, m1 = modes[3 * f + 1] ? 2 : 0, m2 = modes[3 * f + 2] ? 3 : 0;
+    const uint8_t b = (uint8_t)(m0 | (m1 << 2) | (m2 << 4));
+    mode_bytes[f] = b;
+    if (b == 0) lists[4 + n_long++] = (uint32_t)f;
+    else lists[4 + frames + n_short++] = (uint32_t)f;
+  }
+  lists[0] = n_long;
+  lists[1] = n_short;
+  lists[2] = lists[3] = 0u;
+}
+
 // ---- serializeFrame ---------------------------------------------------------------------------------------------------
 // serializeFrame (serialization.js:41-98): the mirror of k_unpack_units, one wave per unit.  The unit is 53 big-endian
 // words in LDS; every field lands on bits no other field uses, so OR-ing a field into the (at most two) words it touches
@@ -218,4 +238,7 @@ void c1k_launch_stage_fields(const C1DevTables *tables, const float *coefs, cons
                              hipStream_t stream) {
   hipLaunchKernelGGL(k_stage_fields, dim3((unsigned)frames), dim3(C1_WAVE), 0, stream, tables, coefs, modes, side, alloc, frames,
                      nbfu, sfi, wl, q);
+}
+void c1k_launch_stage_mode_lists(const int32_t *modes, int64_t frames, uint8_t *mode_bytes, uint32_t *lists, hipStream_t stream) {
+  hipLaunchKernelGGL(k_stage_mode_lists, dim3(1), dim3(C1_WAVE), 0, stream, modes, frames, mode_bytes, lists);
 }

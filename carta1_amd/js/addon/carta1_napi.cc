@@ -514,6 +514,17 @@ napi_value EncStreamPush(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encStreamSetOptions(stream, packedOptions): the options of the next push on (c1_enc_stream_set_options)
+napi_value EncStreamSetOptions(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  c1_enc_stream *s;
+  c1_encode_options o;
+  if (!get_external(env, argv[0], &s) || !get_options(env, argv[1], &o)) return nullptr;
+  const int rc = c1_enc_stream_set_options(s, &o);
+  if (rc) return throw_c1(env, rc);
+  return nullptr;
+}
 napi_value DecStreamCreate(napi_env env, napi_callback_info info) {
   napi_value argv[2];
   if (!get_args(env, info, 2, argv)) return nullptr;
@@ -842,6 +853,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"decodeBatchAsync", nullptr, DecodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamCreate", nullptr, DecStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamPush", nullptr, DecStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamPushFields", nullptr, DecStreamPushFields, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -111,7 +111,8 @@ export class AudioProcessor {
   // Streams of frames in, frame fields out: one closure per channel, as processor.js:69-136.
   // options.batchFrames (default 1 = a result after every frame, like the reference): with N > 1 the frames are
   // collected and handed to the device N at a time (one native stream for all channels); same fields, N times fewer
-  // device round trips.
+  // device round trips.  The encoder options are read as each frame is collected, as the reference's closures read them
+  // per frame: the frames collected under other options are pushed first, and the stream goes on under the new ones.
   static async *encodeStream(audioFrames, options = {}) {
     const { channelCount = 1, onProgress, encoderOptions, batchFrames = 1 } = options
     if (channelCount !== 1 && channelCount !== 2) throw new Error(`Unsupported channel count: ${channelCount}`)
@@ -119,21 +120,25 @@ export class AudioProcessor {
     let frameIndex = 0
     if (batchFrames > 1) {
       const addon = native()
-      const stream = addon.encStreamCreate(context(), channelCount, opts.toNative())
+      const first = opts.toNative()
+      let key = first.join(',')
+      const stream = addon.encStreamCreate(context(), channelCount, first)
       let pending = 0
       let buffers = null
+      const modes = []   // options.fixedBlockModes as each pending frame was collected
       const flush = function* () {
         const units = addon.encStreamPush(stream, buffers.map((b) => b.subarray(0, pending * SAMPLES_PER_FRAME)))
-        for (let f = 0; f < pending; f++) {
+        const frameModes = modes.splice(0, pending)
+        pending = 0
+        for (let f = 0; f < frameModes.length; f++) {
           for (let c = 0; c < channelCount; c++) {
             const at = (f * channelCount + c) * SOUND_UNIT_SIZE
             const fields = deserializeFrame(units.subarray(at, at + SOUND_UNIT_SIZE))
-            if (opts.fixedBlockModes) fields.blockModes = opts.fixedBlockModes
+            if (frameModes[f]) fields.blockModes = frameModes[f]
             yield fields
           }
           if (onProgress) onProgress(frameIndex++)
         }
-        pending = 0
       }
       for await (const frame of audioFrames) {
         const parts = channelCount === 1 ? [frame] : frame
@@ -142,8 +147,16 @@ export class AudioProcessor {
           if (!(parts[c] instanceof Float32Array) || parts[c].length !== SAMPLES_PER_FRAME) {
             throw new Error(`encode: expected a Float32Array of ${SAMPLES_PER_FRAME} samples`)
           }
-          buffers[c].set(parts[c], pending * SAMPLES_PER_FRAME)
         }
+        const now = opts.toNative()
+        const nowKey = now.join(',')
+        if (nowKey !== key) {
+          if (pending) yield* flush()
+          addon.encStreamSetOptions(stream, now)
+          key = nowKey
+        }
+        modes.push(opts.fixedBlockModes)
+        for (let c = 0; c < channelCount; c++) buffers[c].set(parts[c], pending * SAMPLES_PER_FRAME)
         if (++pending === batchFrames) yield* flush()
       }
       if (pending) yield* flush()

@@ -18,14 +18,15 @@ export function encode(options = new EncoderOptions(), bufferPool = new BufferPo
       throwError(`encode: expected a Float32Array of ${SAMPLES_PER_FRAME} samples`)
     }
     const addon = native()
-    // options are read per call, as the reference's stages do (encoder.js:131,381)
+    // options are read per call, as the reference's stages do (encoder.js:131,381); a change goes on with the same stream
+    // from the next frame, detection history included (include/carta1_hip.h, c1_enc_stream_set_options)
     const packed = options.toNative()
     const key = packed.join(',')
-    if (!bufferPool.encoderStream || bufferPool.encoderOptionsKey !== key) {
-      if (bufferPool.encoderStream && bufferPool.encoderOptionsKey !== key) {
-        throwError('encode: options changed on a live stream; use a new BufferPool')
-      }
+    if (!bufferPool.encoderStream) {
       bufferPool.encoderStream = addon.encStreamCreate(context(), 1, packed)
+      bufferPool.encoderOptionsKey = key
+    } else if (bufferPool.encoderOptionsKey !== key) {
+      addon.encStreamSetOptions(bufferPool.encoderStream, packed)
       bufferPool.encoderOptionsKey = key
     }
     const unit = addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])

@@ -211,6 +211,18 @@ int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opt
 int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
                        uint8_t *units /* host, frames*channels*212 */);
 int c1_enc_stream_destroy(c1_enc_stream *s);
+/* The options of every channel from the next push on, as the reference's encode() reads its EncoderOptions on every call
+ * (encoder.js:131-140, :393): validated as c1_enc_stream_create validates them; an invalid call leaves the stream as it was.
+ * The stream goes on bit for bit as the reference's closure does under the same option changes.  What it carries across a
+ * change is the PCM history (QMF delays and the MDCT overlap are functions of it, whatever the block modes) and the detection
+ * history, which only detection writes: under fixed modes it stays at the magnitudes of the last frame detection ran on, or at
+ * a fresh pool's zeros when there was none.  So a switch from detection to fixed modes keeps the bands of the last pushed frame
+ * on the device, and the first frame pushed after a switch back to detection is encoded by the stage kernels
+ * (c1_select_block_modes against those bands or zeros, then c1_mdct_batch, c1_quantize_frames, c1_pack_units); the rest of
+ * that push, and every other push, takes the usual path.  One nuance on that first frame: for non-finite bands the stage
+ * selector follows the reference's Math.max / Math.min, where the encoder's detector clamps, so there it follows the
+ * reference.  Setting the options a stream already has changes nothing. */
+int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
