@@ -292,7 +292,8 @@ class Context:
         return float(out[0]), float(out[1])
 
     def libm_device(self, fn, in_ptr, out_ptr, n):
-        """Math.log / exp / log1p / log10 (fn 0..3) as the detector's kernels evaluate them, on n device doubles."""
+        """Math.log / exp / log1p / log10 (fn 0..3) as the detector's kernels evaluate them, and Math.log2 (fn 4) as
+        find_scale_factor does, on n device doubles."""
         capi.check(capi.load().c1_libm_device(self._h, fn, C.c_void_p(in_ptr), C.c_void_p(out_ptr), n))
 
     def alloc_bounds_device(self, side_ptr, units, out_ptr, options=None):
@@ -332,6 +333,108 @@ class Context:
             raise ValueError('fft works in place on two contiguous float32 arrays of equal length')
         w = np.ascontiguousarray(w, dtype=np.float64)
         capi.check(capi.load().c1_fft(self._h, real.ctypes.data, imag.ctypes.data, real.size, w.ctypes.data))
+
+    # ---- the decision functions of codec/analysis/transient.js and codec/coding/bitallocation.js, batched over independent
+    # problems of any shape (include/carta1_hip.h, c1_perform_fft .. c1_allocate_bits).  Values are read as float64.
+
+    def perform_fft(self, samples, fft_size, w=None):
+        """performFFT, transient.js:17-35, per problem: samples = a sequence of 1-D arrays (any lengths) or a 2-D array ->
+        float32 [problems, fft_size // 2] magnitudes.  fft_size: a power of two 1 .. 2^22.  w: (cos, sin)(-2 pi / stride) for
+        stride = 2 .. fft_size, log2(fft_size) pairs as the reference's engine computes them; default this process's math.cos /
+        math.sin, which may differ from V8's in the last bit"""
+        if not isinstance(fft_size, int) or fft_size < 1 or fft_size & (fft_size - 1) or fft_size > 1 << 22:
+            raise ValueError('perform_fft: fftSize must be a power of two 1 .. 2^22, got %r' % (fft_size,))
+        stages = fft_size.bit_length() - 1
+        if w is None:
+            w = [f(-2 * math.pi / (2 << s)) for s in range(stages) for f in (math.cos, math.sin)]
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.size != 2 * stages:
+            raise ValueError('perform_fft: w must hold log2(fftSize) pairs')
+        rows = list(samples)
+        out = np.zeros((len(rows), fft_size // 2), dtype=np.float32)
+        step = max(1, (1 << 22) // fft_size)                  # problems per call: re / im scratch of 32 MiB
+        for a in range(0, len(rows), step):
+            vals, off = _ragged(rows[a:a + step])
+            capi.check(capi.load().c1_perform_fft(self._h, vals.ctypes.data, off.ctypes.data, off.size - 1, fft_size, w.ctypes.data,
+                                                  out[a:a + step].ctypes.data))
+        return out
+
+    def detect_transient(self, current, previous, threshold):
+        """detectTransient, transient.js:44-226, per problem: current / previous = sequences of 1-D arrays of any lengths
+        (previous[p] None: a falsy prevCoeffs, never transient); threshold a float or one per problem -> (bool [problems],
+        float64 scores [problems], NaN where previous is None)"""
+        cur = list(current)
+        prev = list(previous)
+        if len(prev) != len(cur):
+            raise ValueError('detect_transient: one previous frame (or None) per current frame')
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float64), (len(cur),)))
+        has = np.array([q is not None for q in prev], dtype=np.uint8)
+        cv, co = _ragged(cur)
+        pv, po = _ragged([q if q is not None else () for q in prev])
+        flag = np.zeros(len(cur), dtype=np.uint8)
+        score = np.zeros(len(cur), dtype=np.float64)
+        capi.check(capi.load().c1_detect_transients(self._h, cv.ctypes.data, co.ctypes.data, pv.ctypes.data, po.ctypes.data,
+                                                    has.ctypes.data, thr.ctypes.data, len(cur), flag.ctypes.data, score.ctypes.data))
+        return flag.astype(bool), score
+
+    def find_scale_factor(self, values, lengths=None):
+        """findScaleFactor, bitallocation.js:290-299, per problem: values = a sequence of 1-D arrays; lengths = `length` per
+        problem (default each array's own; past the end reads undefined, <= 0 gives 0) -> int32 [problems]"""
+        rows = list(values)
+        vals, off = _ragged(rows)
+        n = np.diff(off) if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
+        if n.size != len(rows):
+            raise ValueError('find_scale_factor: one length per problem')
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        out = np.zeros(len(rows), dtype=np.int32)
+        capi.check(capi.load().c1_find_scale_factors(self._h, vals.ctypes.data, off.ctypes.data, n.ctypes.data, len(rows), out.ctypes.data))
+        return out
+
+    def allocate_bits(self, bfu_data, bfu_sizes, max_bfu_count, allocation_bias=1.0, biased_table=None):
+        """allocateBits, bitallocation.js:74-142, per problem.  bfu_data: a float array [problems, 52, L] (every BFU L values)
+        or a sequence (per problem) of sequences of 1-D arrays (BFU i's values, any length); bfu_sizes int [problems, 52]
+        (bfuSizes[i] | 0); max_bfu_count 0..52, an int or one per problem.  The table is pow(SCALE_FACTORS, allocation_bias)
+        as EncoderOptions.to_c() builds it (allocation_bias 0 .. 5), or biased_table (64 doubles, any values).  -> dict: bfu_count int32 [problems], allocation
+        int32 [problems, 52] (the first bfu_count entries are the reference's array), scale_factor_indices int32
+        [problems, 52] (the first max_bfu_count entries, or 52 zeros on the fallback), fallback bool [problems]"""
+        sizes = np.ascontiguousarray(bfu_sizes, dtype=np.int32).reshape(-1, 52)
+        n = sizes.shape[0]
+        mb = np.ascontiguousarray(np.broadcast_to(np.asarray(max_bfu_count, dtype=np.int32), (n,)))
+        if isinstance(bfu_data, np.ndarray):
+            d = np.ascontiguousarray(bfu_data, dtype=np.float64).reshape(n, 52, -1)
+            per = d.shape[2]
+            data = d.reshape(-1)
+            offs = (np.arange(n * 52, dtype=np.int64) * per).reshape(n, 52)
+            lens = np.full((n, 52), per, dtype=np.int32)
+        else:
+            rows = list(bfu_data)
+            if len(rows) != n:
+                raise ValueError('allocate_bits: one BFU list per problem')
+            flat = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1) for r in rows for b in list(r)[:52]]
+            data = np.concatenate(flat) if flat else np.zeros(0)
+            offs = np.zeros((n, 52), dtype=np.int64)
+            lens = np.zeros((n, 52), dtype=np.int32)
+            pos = k = 0
+            for p, r in enumerate(rows):
+                for i in range(min(len(r), 52)):
+                    offs[p, i], lens[p, i] = pos, flat[k].size
+                    pos += flat[k].size
+                    k += 1
+        table = biased_table
+        if table is None:
+            o = EncoderOptions({'allocationBias': allocation_bias}).to_c()
+            table = [o.biased_scale_factors[i] for i in range(64)]
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.size != 64:
+            raise ValueError('allocate_bits: the biased table holds 64 entries')
+        res = {'bfu_count': np.zeros(n, dtype=np.int32), 'allocation': np.zeros((n, 52), dtype=np.int32),
+               'scale_factor_indices': np.zeros((n, 52), dtype=np.int32), 'fallback': np.zeros(n, dtype=np.uint8)}
+        capi.check(capi.load().c1_allocate_bits(self._h, data.ctypes.data, data.size, offs.ctypes.data, lens.ctypes.data,
+                                                sizes.ctypes.data, mb.ctypes.data, n, table.ctypes.data, res['bfu_count'].ctypes.data,
+                                                res['allocation'].ctypes.data, res['scale_factor_indices'].ctypes.data,
+                                                res['fallback'].ctypes.data))
+        res['fallback'] = res['fallback'].astype(bool)
+        return res
 
     def qmf_analysis(self, pcm, halo_frames=0):
         """qmfAnalysisStage, codec/pipeline/encoder.js:57-96: pcm = (halo_frames + frames) * 512 samples of one channel
@@ -617,6 +720,16 @@ def _field_arrays(fields):
             raise ValueError('%s must hold %s entries per frame' % (k, shape or 1))
         arrs.append(a)
     return arrs
+
+
+def _ragged(rows):
+    """a sequence of 1-D arrays -> (float64 values, int64 offsets[len + 1]) as the batched decision entries take them"""
+    arrs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1) for r in rows]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    if arrs:
+        off[1:] = np.cumsum([a.size for a in arrs])
+    vals = np.concatenate(arrs) if arrs and off[-1] else np.zeros(1)
+    return np.ascontiguousarray(vals), off
 
 
 def _check_quantize_args(scale_factor_index, bits_per_sample):

@@ -1333,8 +1333,9 @@ int c1_libm_device(c1_ctx *ctx, int fn, const double *in, double *out, int64_t n
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx);
   if (rc) return rc;
-  if (fn < 0 || fn > 3 || n < 0 || (n > 0 && (!in || !out))) return fail(C1_ERR_ARG, "bad fn / n / NULL argument");
-  c1k_launch_libm(fn, in, out, n, ctx->stream);
+  if (fn < 0 || fn > 4 || n < 0 || (n > 0 && (!in || !out))) return fail(C1_ERR_ARG, "bad fn / n / NULL argument");
+  if (fn == 4) c1k_launch_js_log2(in, out, n, ctx->stream);
+  else c1k_launch_libm(fn, in, out, n, ctx->stream);
   HIP_TRY(hipGetLastError());
   return C1_OK;
 }
@@ -1718,6 +1719,154 @@ int c1_pack_units(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_
   { ScopedTiming t(ctx, K_PACK_UNITS); c1k_launch_pack_units(dn, dm, ds_, dw, dq, frames, du, ctx->stream); }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(units, du, n * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// ---- the decision functions of analysis/transient.js and coding/bitallocation.js over batches of problems ----
+namespace {
+constexpr int64_t kMaxDecisionProblems = (int64_t)1 << 20;
+constexpr int64_t kMaxDecisionValues = (int64_t)1 << 28;      // doubles of input per call (2 GiB)
+
+// offsets[0..problems]: non-decreasing from 0; *total = offsets[problems]
+int check_csr(const char *what, const int64_t *offsets, int64_t problems, int64_t *total) {
+  if (offsets[0] != 0) return fail(C1_ERR_ARG, "%s: offsets[0] must be 0", what);
+  for (int64_t p = 0; p < problems; p++)
+    if (offsets[p + 1] < offsets[p]) return fail(C1_ERR_ARG, "%s: offsets decrease at problem %lld", what, (long long)p);
+  if (offsets[problems] > kMaxDecisionValues) return fail(C1_ERR_ARG, "%s: more than 2^28 values", what);
+  *total = offsets[problems];
+  return C1_OK;
+}
+}  // namespace
+
+int c1_perform_fft(c1_ctx *ctx, const double *samples, const int64_t *offsets, int64_t problems, int fft_size, const double *w,
+                   float *magnitudes) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (fft_size < 1 || (fft_size & (fft_size - 1)) || fft_size > (1 << 22))
+    return fail(C1_ERR_ARG, "perform fft: fftSize must be a power of two <= 2^22, got %d", fft_size);
+  if (problems < 0 || problems > kMaxDecisionProblems) return fail(C1_ERR_ARG, "perform fft: problems must be 0 .. 2^20, got %lld", (long long)problems);
+  if (problems == 0 || fft_size == 1) return C1_OK;          // fft.js:16; Float32Array(1 / 2) is empty
+  if (!offsets || !w || !magnitudes) return fail(C1_ERR_ARG, "perform fft: NULL argument");
+  if (problems * fft_size > ((int64_t)1 << 26)) return fail(C1_ERR_ARG, "perform fft: problems * fftSize above 2^26");
+  int64_t total = 0;
+  if ((rc = check_csr("perform fft", offsets, problems, &total))) return rc;
+  if (total > 0 && !samples) return fail(C1_ERR_ARG, "perform fft: NULL argument");
+  int stages = 0;
+  while ((1 << stages) < fft_size) stages++;
+  const size_t n = (size_t)fft_size, np = (size_t)problems;
+  DeviceScratch ds;
+  double *dsamp, *dw, *dtw; int64_t *doff; float *dre, *dim, *dmag;
+  if ((rc = ds.alloc(&dsamp, (size_t)total)) || (rc = ds.alloc(&doff, np + 1)) || (rc = ds.alloc(&dw, 2 * (size_t)stages)) ||
+      (rc = ds.alloc(&dtw, 2 * n)) || (rc = ds.alloc(&dre, np * n)) || (rc = ds.alloc(&dim, np * n)) || (rc = ds.alloc(&dmag, np * n / 2))) return rc;
+  if (total > 0) HIP_TRY(hipMemcpyAsync(dsamp, samples, (size_t)total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(doff, offsets, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dw, w, 2 * (size_t)stages * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_perform_fft(dsamp, doff, problems, fft_size, dw, dtw, dre, dim, dmag, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(magnitudes, dmag, np * n / 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_detect_transients(c1_ctx *ctx, const double *cur, const int64_t *cur_offsets, const double *prev, const int64_t *prev_offsets,
+                         const uint8_t *has_prev, const double *thresholds, int64_t problems, uint8_t *transient, double *scores) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (problems < 0 || problems > kMaxDecisionProblems) return fail(C1_ERR_ARG, "detect transients: problems must be 0 .. 2^20, got %lld", (long long)problems);
+  if (problems == 0) return C1_OK;
+  if (!cur_offsets || !prev_offsets || !thresholds || !transient || !scores) return fail(C1_ERR_ARG, "detect transients: NULL argument");
+  int64_t nc = 0, np_ = 0;
+  if ((rc = check_csr("detect transients (current)", cur_offsets, problems, &nc)) ||
+      (rc = check_csr("detect transients (previous)", prev_offsets, problems, &np_))) return rc;
+  if ((nc > 0 && !cur) || (np_ > 0 && !prev)) return fail(C1_ERR_ARG, "detect transients: NULL argument");
+  const size_t n = (size_t)problems;
+  DeviceScratch ds;
+  double *dc, *dp, *dthr, *dscore; int64_t *dco, *dpo; uint8_t *dhas = nullptr, *dout;
+  if ((rc = ds.alloc(&dc, (size_t)nc)) || (rc = ds.alloc(&dp, (size_t)np_)) || (rc = ds.alloc(&dco, n + 1)) || (rc = ds.alloc(&dpo, n + 1)) ||
+      (rc = ds.alloc(&dthr, n)) || (rc = ds.alloc(&dscore, n)) || (rc = ds.alloc(&dout, n)) || (has_prev && (rc = ds.alloc(&dhas, n)))) return rc;
+  if (nc > 0) HIP_TRY(hipMemcpyAsync(dc, cur, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (np_ > 0) HIP_TRY(hipMemcpyAsync(dp, prev, (size_t)np_ * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dco, cur_offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dpo, prev_offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dthr, thresholds, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (has_prev) HIP_TRY(hipMemcpyAsync(dhas, has_prev, n, hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_detect_transients(dc, dco, dp, dpo, dhas, dthr, problems, ctx->d_tables, dout, dscore, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(transient, dout, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(scores, dscore, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_find_scale_factors(c1_ctx *ctx, const double *values, const int64_t *offsets, const int64_t *lengths, int64_t problems,
+                          int32_t *indices) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (problems < 0 || problems > kMaxDecisionProblems) return fail(C1_ERR_ARG, "find scale factors: problems must be 0 .. 2^20, got %lld", (long long)problems);
+  if (problems == 0) return C1_OK;
+  if (!offsets || !lengths || !indices) return fail(C1_ERR_ARG, "find scale factors: NULL argument");
+  int64_t total = 0;
+  if ((rc = check_csr("find scale factors", offsets, problems, &total))) return rc;
+  if (total > 0 && !values) return fail(C1_ERR_ARG, "find scale factors: NULL argument");
+  // `length` past the array reads undefined, which never raises the maximum: read min(length, array length), none for length <= 0
+  const size_t n = (size_t)problems;
+  std::vector<int64_t> counts(n);
+  for (size_t p = 0; p < n; p++) counts[p] = std::max<int64_t>(0, std::min(lengths[p], offsets[p + 1] - offsets[p]));
+  DeviceScratch ds;
+  double *dv; int64_t *doff, *dcnt; int32_t *dout;
+  if ((rc = ds.alloc(&dv, (size_t)total)) || (rc = ds.alloc(&doff, n + 1)) || (rc = ds.alloc(&dcnt, n)) || (rc = ds.alloc(&dout, n))) return rc;
+  if (total > 0) HIP_TRY(hipMemcpyAsync(dv, values, (size_t)total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(doff, offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dcnt, counts.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_find_scale_factors(dv, doff, dcnt, problems, dout, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(indices, dout, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_allocate_bits(c1_ctx *ctx, const double *data, int64_t data_len, const int64_t *bfu_offsets, const int32_t *bfu_lengths,
+                     const int32_t *bfu_sizes, const int32_t *max_bfu_counts, int64_t problems, const double *biased_scale_factors,
+                     int32_t *bfu_count, int32_t *allocation, int32_t *scale_factor_indices, uint8_t *fallback) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (problems < 0 || problems > kMaxDecisionProblems) return fail(C1_ERR_ARG, "allocate bits: problems must be 0 .. 2^20, got %lld", (long long)problems);
+  if (problems == 0) return C1_OK;
+  if (!bfu_offsets || !bfu_lengths || !bfu_sizes || !max_bfu_counts || !biased_scale_factors || !bfu_count || !allocation ||
+      !scale_factor_indices || !fallback) return fail(C1_ERR_ARG, "allocate bits: NULL argument");
+  if (data_len < 0 || data_len > kMaxDecisionValues || (data_len > 0 && !data)) return fail(C1_ERR_ARG, "allocate bits: bad data length");
+  const size_t n = (size_t)problems;
+  for (size_t p = 0; p < n; p++) {
+    const int mb = max_bfu_counts[p];
+    if (mb < 0 || mb > 52) return fail(C1_ERR_ARG, "allocate bits: problem %zu: maxBfuCount %d outside 0..52", p, mb);
+    for (int i = 0; i < mb; i++) {
+      const int64_t off = bfu_offsets[52 * p + i], len = bfu_lengths[52 * p + i];
+      if (bfu_sizes[52 * p + i] != 0 && (off < 0 || len < 0 || off > data_len || len > data_len - off))
+        return fail(C1_ERR_ARG, "allocate bits: problem %zu: BFU %d's values lie outside the data", p, i);
+    }
+  }
+  DeviceScratch ds;
+  double *dd, *dbsf; int64_t *doff; int32_t *dlen, *dsz, *dmb, *dcount, *dwl, *dsfi; uint8_t *dfb;
+  if ((rc = ds.alloc(&dd, (size_t)data_len)) || (rc = ds.alloc(&dbsf, 64)) || (rc = ds.alloc(&doff, 52 * n)) || (rc = ds.alloc(&dlen, 52 * n)) ||
+      (rc = ds.alloc(&dsz, 52 * n)) || (rc = ds.alloc(&dmb, n)) || (rc = ds.alloc(&dcount, n)) || (rc = ds.alloc(&dwl, 52 * n)) ||
+      (rc = ds.alloc(&dsfi, 52 * n)) || (rc = ds.alloc(&dfb, n))) return rc;
+  if (data_len > 0) HIP_TRY(hipMemcpyAsync(dd, data, (size_t)data_len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dbsf, biased_scale_factors, 64 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(doff, bfu_offsets, 52 * n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dlen, bfu_lengths, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dsz, bfu_sizes, 52 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dmb, max_bfu_counts, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  c1k_launch_allocate_bits(dd, doff, dlen, dsz, dmb, problems, dbsf, dcount, dwl, dsfi, dfb, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(bfu_count, dcount, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(allocation, dwl, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(scale_factor_indices, dsfi, 52 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(fallback, dfb, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }

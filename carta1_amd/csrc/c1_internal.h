@@ -237,6 +237,21 @@ void c1k_launch_quantize_one(const C1DevTables *tables, const float *x, int n, i
 void c1k_launch_dequantize_one(const C1DevTables *tables, const int32_t *q, int n, int sfi, int bits, float *out, hipStream_t stream);
 void c1k_launch_fft_reference(float *real, float *imag, int n, const double *w, double *twiddle_scratch /* n doubles */, hipStream_t stream);
 void c1k_launch_window_bands(const float *bands, const uint8_t *modes, int64_t units, const C1DevTables *tables, float *out, hipStream_t stream);
+// the decision functions of analysis/transient.js and coding/bitallocation.js over batches of independent problems
+// (c1_k_decision.hip); device pointers.  Offsets index `values`; every range has been checked by the caller
+void c1k_launch_js_log2(const double *in, double *out, int64_t n, hipStream_t stream);
+void c1k_launch_find_scale_factors(const double *values, const int64_t *offsets, const int64_t *counts, int64_t problems, int32_t *out,
+                                   hipStream_t stream);
+// offsets[problems + 1]; w = log2(n) host twiddle pairs; tw 2n doubles, re / im problems * n floats, mag problems * n / 2; n >= 2
+void c1k_launch_perform_fft(const double *samples, const int64_t *offsets, int64_t problems, int n, const double *w, double *tw,
+                            float *re, float *im, float *mag, hipStream_t stream);
+void c1k_launch_detect_transients(const double *cur, const int64_t *cur_off, const double *prev, const int64_t *prev_off,
+                                  const uint8_t *has_prev, const double *thresholds, int64_t problems, const C1DevTables *tables,
+                                  uint8_t *transient, double *scores, hipStream_t stream);
+// max_bfus 0..52; bfu_off / bfu_len / bfu_sizes / wl / sfi: problems * 52; bsf = 64 biased scale factors
+void c1k_launch_allocate_bits(const double *data, const int64_t *bfu_off, const int32_t *bfu_len, const int32_t *bfu_sizes,
+                              const int32_t *max_bfus, int64_t problems, const double *bsf, int32_t *count, int32_t *wl, int32_t *sfi,
+                              uint8_t *fallback, hipStream_t stream);
 void c1k_launch_detect_spec_tap(const C1EncodeLaunch &L, float *bands_ws, double *feat_ws, hipStream_t stream);   // L.mags, L.mag_bounds
 void c1k_launch_libm(int fn, const double *in, double *out, int64_t n, hipStream_t stream);
 void c1k_launch_log2f_error(uint32_t first, uint64_t count, unsigned long long *out, hipStream_t stream);   // out: 2 x u64 on the device

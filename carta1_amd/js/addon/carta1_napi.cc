@@ -837,6 +837,92 @@ napi_value QmfSynthesis(napi_env env, napi_callback_info info) {  // (ctx, Float
   return out;
 }
 
+// ---- the decision functions of analysis/transient.js and coding/bitallocation.js, one problem per call ----
+napi_value PerformFft(napi_env env, napi_callback_info info) {    // (ctx, Float64Array samples, fftSize, Float64Array w) -> Float32Array(fftSize / 2)
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx; void *x, *w; size_t n, nw; int32_t size = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float64_array, &x, &n) ||
+      !get_typed(env, argv[3], napi_float64_array, &w, &nw)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &size));
+  size_t stages = 0;
+  while (size > 0 && ((size_t)1 << stages) < (size_t)size) stages++;
+  if (nw < 2 * stages) { napi_throw_type_error(env, nullptr, "performFFT: log2(fftSize) twiddle pairs"); return nullptr; }
+  const int64_t off[2] = {0, (int64_t)n};
+  float *mag;
+  napi_value out = make_f32(env, size > 1 ? (size_t)size / 2 : 0, &mag);
+  const int rc = c1_perform_fft(ctx, static_cast<const double *>(x), off, 1, size, static_cast<const double *>(w), mag);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+napi_value DetectTransient(napi_env env, napi_callback_info info) {  // (ctx, Float64Array cur, Float64Array prev, threshold) -> [transient, score]
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx; void *c, *p; size_t nc, np; double thr = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float64_array, &c, &nc) ||
+      !get_typed(env, argv[2], napi_float64_array, &p, &np)) return nullptr;
+  NAPI_OK(napi_get_value_double(env, argv[3], &thr));
+  const int64_t co[2] = {0, (int64_t)nc}, po[2] = {0, (int64_t)np};
+  uint8_t flag = 0;
+  double score = 0;
+  const int rc = c1_detect_transients(ctx, static_cast<const double *>(c), co, static_cast<const double *>(p), po, nullptr, &thr, 1, &flag, &score);
+  if (rc) return throw_c1(env, rc);
+  napi_value arr, b, sc;
+  NAPI_OK(napi_create_array_with_length(env, 2, &arr));
+  NAPI_OK(napi_get_boolean(env, flag != 0, &b));
+  NAPI_OK(napi_create_double(env, score, &sc));
+  NAPI_OK(napi_set_element(env, arr, 0, b));
+  NAPI_OK(napi_set_element(env, arr, 1, sc));
+  return arr;
+}
+napi_value FindScaleFactor(napi_env env, napi_callback_info info) {  // (ctx, Float64Array values, length as a double integer) -> number
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  c1_ctx *ctx; void *v; size_t n; int64_t len = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float64_array, &v, &n)) return nullptr;
+  NAPI_OK(napi_get_value_int64(env, argv[2], &len));
+  const int64_t off[2] = {0, (int64_t)n};
+  int32_t idx = 0;
+  const int rc = c1_find_scale_factors(ctx, static_cast<const double *>(v), off, &len, 1, &idx);
+  if (rc) return throw_c1(env, rc);
+  napi_value r;
+  NAPI_OK(napi_create_int32(env, idx, &r));
+  return r;
+}
+// (ctx, Float64Array data, Int32Array offsets[52], Int32Array lengths[52], Int32Array sizes[52], maxBfuCount, Float64Array(64) table)
+//   -> [bfuCount, Int32Array allocation(52), Int32Array scaleFactorIndices(52), fallback]
+napi_value AllocateBits(napi_env env, napi_callback_info info) {
+  napi_value argv[7];
+  if (!get_args(env, info, 7, argv)) return nullptr;
+  c1_ctx *ctx; void *d, *o, *l, *z, *t; size_t nd, no, nl, nz, nt; int32_t mb = 0;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float64_array, &d, &nd) ||
+      !get_typed(env, argv[2], napi_int32_array, &o, &no) || !get_typed(env, argv[3], napi_int32_array, &l, &nl) ||
+      !get_typed(env, argv[4], napi_int32_array, &z, &nz) || !get_typed(env, argv[6], napi_float64_array, &t, &nt)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[5], &mb));
+  if (no != 52 || nl != 52 || nz != 52 || nt != 64) { napi_throw_type_error(env, nullptr, "allocateBits: 52 offsets, lengths and sizes and a 64-entry table"); return nullptr; }
+  int64_t off[52];
+  for (int i = 0; i < 52; i++) off[i] = static_cast<const int32_t *>(o)[i];
+  napi_value arr, ab, wl, sf, cnt, fb;
+  void *pw, *ps;
+  NAPI_OK(napi_create_arraybuffer(env, 52 * 4, &pw, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_int32_array, 52, ab, 0, &wl));
+  NAPI_OK(napi_create_arraybuffer(env, 52 * 4, &ps, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_int32_array, 52, ab, 0, &sf));
+  int32_t count = 0;
+  uint8_t fallback = 0;
+  const int rc = c1_allocate_bits(ctx, static_cast<const double *>(d), (int64_t)nd, off, static_cast<const int32_t *>(l),
+                                  static_cast<const int32_t *>(z), &mb, 1, static_cast<const double *>(t), &count,
+                                  static_cast<int32_t *>(pw), static_cast<int32_t *>(ps), &fallback);
+  if (rc) return throw_c1(env, rc);
+  NAPI_OK(napi_create_array_with_length(env, 4, &arr));
+  NAPI_OK(napi_create_int32(env, count, &cnt));
+  NAPI_OK(napi_get_boolean(env, fallback != 0, &fb));
+  NAPI_OK(napi_set_element(env, arr, 0, cnt));
+  NAPI_OK(napi_set_element(env, arr, 1, wl));
+  NAPI_OK(napi_set_element(env, arr, 2, sf));
+  NAPI_OK(napi_set_element(env, arr, 3, fb));
+  return arr;
+}
 napi_value Init(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"abiVersion", nullptr, AbiVersion, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -870,6 +956,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"packUnits", nullptr, PackUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"imdct", nullptr, Imdct, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"qmfSynthesis", nullptr, QmfSynthesis, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"performFFT", nullptr, PerformFft, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"detectTransient", nullptr, DetectTransient, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"findScaleFactor", nullptr, FindScaleFactor, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"allocateBits", nullptr, AllocateBits, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

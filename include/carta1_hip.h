@@ -361,6 +361,42 @@ int c1_quantize_frames(c1_ctx *ctx, const float *coefs, int64_t frames, const in
 int c1_pack_units(c1_ctx *ctx, int64_t frames, const int32_t *nbfu, const int32_t *block_modes, const int32_t *sfi,
                   const int32_t *wl, const int32_t *quantized, uint8_t *units);
 
+/* The decision functions of codec/analysis/transient.js (performFFT, detectTransient) and codec/coding/bitallocation.js
+ * (findScaleFactor, allocateBits), which the encoder runs at the codec's fixed shapes, for any shapes and values, batched over
+ * `problems` (0 .. 2^20) independent problems.  Host pointers, synchronous; the reference's number model (binary64 operations
+ * in its index order, binary32 at every typed-array store).  Input values are doubles as JavaScript reads them; variable-length
+ * inputs are concatenated, with offsets[problems + 1] starting at 0 and non-decreasing (problem p owns values
+ * [offsets[p], offsets[p + 1])), at most 2^28 values per call.  C1_ERR_ARG for a NULL pointer or a range outside these. */
+/* performFFT, transient.js:17-35: the first min(length, fft_size) samples of each problem rounded to binary32 (real.set),
+ * zero padding, FFT.fft with w as for c1_fft (log2(fft_size) pairs from the host's Math.cos / Math.sin), then
+ * Float32(Math.sqrt(re*re + im*im)) of bins 0 .. fft_size/2 - 1 -> magnitudes = problems * (fft_size / 2) floats.  fft_size is a
+ * power of two 1 .. 2^22 (1 writes nothing, as Float32Array(1 / 2) is empty); problems * fft_size <= 2^26.  Deviation: any
+ * other fft_size is C1_ERR_ARG (the reference's FFT does not define it). */
+int c1_perform_fft(c1_ctx *ctx, const double *samples, const int64_t *offsets, int64_t problems, int fft_size, const double *w,
+                   float *magnitudes);
+/* detectTransient, transient.js:44-226: currentCoeffs and prevCoeffs of any lengths (cur_offsets, prev_offsets).  has_prev
+ * (NULL: every problem has one) = 0 is a falsy prevCoeffs: false, score NaN.  A read of prevCoeffs past its end is undefined
+ * (NaN in flux and energy); extra previous bins count in its flatness and high-frequency ratio only.  Math.max / Math.min
+ * propagate NaN, and `Math.sqrt(e) || 1e-6` also replaces a NaN.  Math.log1p(10) is the installed tables' log1p_10.
+ * transient[p] = score > thresholds[p] (a NaN score never is); scores[p] = the score (a test tap). */
+int c1_detect_transients(c1_ctx *ctx, const double *cur, const int64_t *cur_offsets, const double *prev, const int64_t *prev_offsets,
+                         const uint8_t *has_prev, const double *thresholds, int64_t problems, uint8_t *transient, double *scores);
+/* findScaleFactor, bitallocation.js:290-299: max |v| over the first `lengths[p]` values (a read past the array is undefined and,
+ * like NaN, never raises the maximum; lengths <= 0 read nothing), then 0 for a zero maximum, else
+ * clamp(ceil(3 (Math.log2(max) + 21)), 0, 63) with V8's Math.log2 (c1_libm_device fn 4): +Inf gives 63. */
+int c1_find_scale_factors(c1_ctx *ctx, const double *values, const int64_t *offsets, const int64_t *lengths, int64_t problems,
+                          int32_t *indices);
+/* allocateBits, bitallocation.js:74-288: per problem max_bfu_counts[p] (0..52) BFUs; BFU i (p*52 + i) has bfu_sizes (any int32,
+ * bfuSizes[i] | 0) and bfu_lengths values at data + bfu_offsets (entries at and above max_bfu_counts[p] are not read, nor those
+ * of size 0).  A BFU shorter than its size reads undefined past its end; a negative size reads nothing.  biased_scale_factors =
+ * the 64 entries of buildBiasedScaleFactorTable(allocationBias), any doubles.  Out per problem: bfu_count; allocation[52] (the
+ * first bfu_count word lengths, zeros behind); scale_factor_indices[52] (the first maxBfuCount, zeros behind); fallback = 1
+ * when no candidate total is < +Inf (bfuCount 20, zero word lengths, 52 zero indices; :132-139).  Deviation: maxBfuCount
+ * above 52 is C1_ERR_ARG. */
+int c1_allocate_bits(c1_ctx *ctx, const double *data, int64_t data_len, const int64_t *bfu_offsets, const int32_t *bfu_lengths,
+                     const int32_t *bfu_sizes, const int32_t *max_bfu_counts, int64_t problems, const double *biased_scale_factors,
+                     int32_t *bfu_count, int32_t *allocation, int32_t *scale_factor_indices, uint8_t *fallback);
+
 /* The decode() frame closure (codec/pipeline/decoder.js:408-411: dequantizationStage, imdctStage, qmfSynthesisStage) over frame
  * fields in the layout c1_unpack_units writes, in one device launch: what the reference's decode() computes for a frameData
  * object, also for fields serializeFrame would not carry (an nBfu outside BFU_AMOUNTS, band modes other than 0 and the
@@ -422,7 +458,8 @@ int c1_log2f_error_device(c1_ctx *ctx, uint32_t first_bits, uint64_t count, doub
 
 /* Test tap: Math.log (fn 0), Math.exp (1), Math.log1p (2), Math.log10 (3) as the reference's engine evaluates them and as
  * the detector's kernels use them (transient.js:129, :137, :185, :211; V8 src/base/ieee754.cc = fdlibm, not correctly
- * rounded, so the algorithm itself is part of the parity contract).  in, out: n doubles, device pointers. */
+ * rounded, so the algorithm itself is part of the parity contract), and Math.log2 (4) as c1_find_scale_factors uses it
+ * (bitallocation.js:297).  in, out: n doubles, device pointers. */
 int c1_libm_device(c1_ctx *ctx, int fn, const double *in, double *out, int64_t n);
 
 /* Test tap of the bit allocation (allocateBits, bitallocation.js:74-142).  The library runs the greedy heap only for the
