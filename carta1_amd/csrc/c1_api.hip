@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <atomic>
@@ -351,6 +352,51 @@ int build_table_fields(const c1_encode_options &o, C1DevEncOpts *d) {
             d->rank_affine = 1; d->rank_a = A; d->rank_b = B; d->rank_c = C; d->rank_off = 1 - lo;
           }
         }
+  }
+  // With the integer form, a successful step of the spending loop is one addition to the root's heap entry
+  // (rank(10) | size(5) | sfi(6) | wl(4) | bfu(6), c1_k_allocate.hip): word length + 1, rank - B (from word length 0:
+  // rank - 2B - C).  Walk every (sfi, wl) with the two steps; anything out of line and the kernels read the table.
+  if (d->rank_affine) {
+    const int A = d->rank_a, B = d->rank_b, C = d->rank_c, off = d->rank_off;
+    auto rk = [&](int s, int wl) { return wl == 0 ? A * s + C + off : A * s + off - B * (wl + 1); };
+    auto entry = [&](int s, int wl) { return ((uint32_t)rk(s, wl) << 21) | ((uint32_t)s << 10) | ((uint32_t)wl << 6); };
+    d->rank_step0 = (1u << 6) + ((uint32_t)(-2 * B - C) << 21);
+    d->rank_step = (1u << 6) - ((uint32_t)B << 21);
+    bool ok = true;
+    for (int s = 1; s < 64 && ok; s++)
+      for (int wl = 0; wl < 15 && ok; wl++) {
+        if (rk(s, wl) < 1 || rk(s, wl) > 1022) ok = false;
+        if (wl < 14 && entry(s, wl) + (wl == 0 ? d->rank_step0 : d->rank_step) != entry(s, wl + 1)) ok = false;
+      }
+    if (!ok) { d->rank_affine = 0; d->rank_step0 = d->rank_step = 0; }
+  }
+  // The terms of calculateTotalDistortion (bitallocation.js:157-190) per BFU size and sfi: see C1DevEncOpts::dist.
+  // (b * 2^-k) * n == (b * n) * 2^-k as long as neither side leaves the normal range, and then multiplying by 2^-k is
+  // subtracting k from the exponent field; the installed table may hold anything, so every case is tried here.
+  {
+    bool ok = true;
+    for (int c = 0; c < 8; c++) {
+      const double size = (double)kDistSizes[c];
+      for (int s = 0; s < 64; s++) {
+        const double bs = d->biased[s];
+        const double zb = s != 0 ? (double)(float)(bs * 2.0 * size) : 0.0;     // zeroBitDistortions (:76, 87-89)
+        const double cs = bs * size;
+        d->dist[c][s][0] = zb;
+        d->dist[c][s][1] = cs;
+        if (s == 0) continue;
+        if (!(zb >= (double)std::numeric_limits<float>::min())) ok = false;   // a binary32 subnormal: leave it to the device's own conversion
+        uint64_t u;
+        memcpy(&u, &cs, sizeof u);
+        for (int wl = 1; wl <= 15; wl++) {
+          const int bits = wl + 1;
+          const double want = bs * std::ldexp(1.0, -bits) * size;               // (:183-187): biased * INV_POWER_OF_TWO[bits] * size
+          if ((int)((u >> 52) & 0x7ff) <= bits || (int)((u >> 52) & 0x7ff) == 0x7ff) { ok = false; continue; }
+          const uint64_t v = u - ((uint64_t)bits << 52);
+          if (memcmp(&v, &want, sizeof v) != 0) ok = false;
+        }
+      }
+    }
+    d->dist_tables = (ok && !getenv("C1_NO_DIST_TABLES")) ? 1 : 0;
   }
   return C1_OK;
 }
@@ -949,6 +995,25 @@ int c1_alloc_rank_form(const c1_encode_options *opts, int *affine, int *coef) {
   if (rc) return rc;
   if (affine) *affine = d->rank_affine;
   if (coef) { coef[0] = d->rank_a; coef[1] = d->rank_b; coef[2] = d->rank_c; coef[3] = d->rank_off; }
+  return C1_OK;
+}
+
+int c1_alloc_tables(const c1_encode_options *opts, int *affine, uint32_t *steps, uint16_t *rank, int *dist_ok, double *dist) {
+  if (!opts) return fail(C1_ERR_ARG, "opts is NULL");
+  std::unique_ptr<C1DevEncOpts> d(new C1DevEncOpts);
+  const int rc = build_table_fields(*opts, d.get());
+  if (rc) return rc;
+  if (affine) *affine = d->rank_affine;
+  if (steps) { steps[0] = d->rank_step0; steps[1] = d->rank_step; }
+  if (rank) {
+    // the rank field of the heap entries the kernels build for (sfi, wl): the integer form where there is one
+    for (int s = 0; s < 64; s++)
+      for (int wl = 0; wl < 16; wl++)
+        rank[s * 16 + wl] = !d->rank_affine ? d->rank[s * 16 + wl]
+                            : (uint16_t)(wl == 0 ? d->rank_a * s + d->rank_c + d->rank_off : d->rank_a * s + d->rank_off - d->rank_b * (wl + 1));
+  }
+  if (dist_ok) *dist_ok = d->dist_tables;
+  if (dist) memcpy(dist, d->dist, sizeof d->dist);
   return C1_OK;
 }
 

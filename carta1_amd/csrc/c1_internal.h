@@ -75,7 +75,17 @@ struct C1DevEncOpts {
   // the bounds themselves are formed from `biased`, so an inexact fit costs pruning power, never correctness
   float la_slope, la_off;
   int32_t alloc_no_tonal;     // experiments (C1_ALLOC_NO_TONAL=1): always run the 52-BFU candidate first
+  // with rank_affine: what one successful heap step adds to the root's entry (word length + 1 and the rank of the next
+  // priority), from word length 0 and from any other; checked on the host for every (sfi, wl), else rank_affine is 0
+  uint32_t rank_step0, rank_step;
+  // calculateTotalDistortion's terms per (BFU size, sfi), sizes in the order of kDistSizes: [..][0] = the zero-bit term
+  // Float32(biased * 2 * size) as a double (0 for sfi 0), [..][1] = biased * size, whose exponent minus `bits` is the
+  // coded term biased * 2^-bits * size.  dist_tables = 1 when the host found that identity to hold bit for bit for every
+  // (size, sfi, word length) of this table; the kernels form the terms as the reference does otherwise.
+  int32_t dist_tables;
+  alignas(16) double dist[8][64][2];
 };
+constexpr int kDistSizes[8] = {4, 6, 7, 8, 9, 10, 12, 20};   // the BFU sizes there are (constants.js:29-36)
 
 // ---- geometry ------------------------------------------------------------------------------------
 constexpr int kRunFrames = 16;   // consecutive frames of one channel processed by one wave

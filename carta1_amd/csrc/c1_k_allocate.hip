@@ -68,36 +68,61 @@ __device__ __forceinline__ void heap_sift_down(uint32_t *hp, int sentinel, int i
   }
 }
 
-// One greedy heap per lane: candidate with `n` BFUs.  sf = the unit's 52 scale-factor indices (13 dwords).
-// Returns the 52 final word-length indices (4 bits each) and the candidate's total distortion.
+// kSpecs as compile-time constants: in the 52-way unrolled loops below a size is then part of an immediate, where the
+// table in constant memory cost a scalar register per BFU (168 of them spilled to vector lanes in k_alloc_first)
+constexpr int kSpecsHost[52] = {8, 8, 8, 8, 4, 4, 4, 4, 8, 8, 8, 8, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 7, 7, 7, 7, 9, 9, 9, 9, 10, 10, 10, 10,
+                                12, 12, 12, 12, 12, 12, 12, 12, 20, 20, 20, 20, 20, 20, 20, 20};
+constexpr int dist_class(int size) {   // index of a BFU size in kDistSizes (C1DevEncOpts::dist)
+  for (int c = 0; c < 8; c++) if (kDistSizes[c] == size) return c;
+  return -1;
+}
+constexpr bool sizes_come_in_fours() {
+  for (int b = 0; b < 52; b++) if (kSpecsHost[b] != kSpecsHost[b & ~3]) return false;
+  return true;
+}
+static_assert(sizes_come_in_fours(), "the four BFUs whose indices share a dword share a size");
+static_assert(dist_class(4) == 0 && dist_class(20) == 7 && dist_class(kSpecsHost[24]) == 2, "every BFU size has its row of the distortion tables");
+
+// The 52 scale-factor indices are taken apart three times (guess, initial heap, totals).  Left alone, the compiler forms
+// the 52 "s != 0" lane masks once and keeps them for later: 104 scalar registers, which it then spills to vector lanes.
+// Passing the packed indices through an empty asm between the phases makes each phase form what it needs itself.
+__device__ __forceinline__ void reopen(uint32_t (&sf)[13]) {
+#pragma unroll
+  for (int i = 0; i < 13; i++) asm volatile("" : "+v"(sf[i]));
+}
+
+// The heap phase of one candidate: initial heap, heapify, spending loop.  AFFINE (wave-uniform, C1DevEncOpts::rank_affine)
+// chooses between two instances so that neither carries the other's code: ranks by the integer form, where a
+// successful step is ONE addition to the root's entry (rank_step0 / rank_step, verified on the host for every
+// (sfi, wl)), or ranks looked up in the table of the Float32 priorities.
 // During the spending loop the three top slots of the heap live in registers (r0 = root, r1/r2 = its
 // children): most steps end at the root (equal priorities do not move, :325-331), so they touch no memory.
-__device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_t (&sf)[13], const C1DevEncOpts *O,
-                                              bool live, uint64_t &res0, uint64_t &res1, uint64_t &res2,
-                                              uint64_t &res3, double &total) {
+template <bool AFFINE>
+__device__ __forceinline__ void heap_phase(uint32_t *hp, int n, const uint32_t (&sf)[13], const C1DevEncOpts *O, bool live) {
   const __attribute__((address_space(4))) uint16_t *rank_t = (const __attribute__((address_space(4))) uint16_t *)O->rank;
   // (an LDS copy of this table is slower: 512 more bytes per wave cost a wave per CU, measured 1.50 -> 1.63 ms)
-  const __attribute__((address_space(4))) double *biased = (const __attribute__((address_space(4))) double *)O->biased;
-  const bool affine = O->rank_affine != 0;
-  const int ka = O->rank_a, kb = O->rank_b, kc = O->rank_c, koff = O->rank_off;
-  // (24-bit multiplies: every factor is below 64 in magnitude, and the full 32-bit v_mul_lo_u32 issues at a quarter of the rate)
-  const int nkb = -kb, kc_off = kc + koff;
-  auto rank_of = [&](int s, int wl) -> uint32_t {
-    if (affine) return (uint32_t)(wl == 0 ? __mul24(ka, s) + kc_off : __mul24(ka, s) + koff + __mul24(nkb, wl + 1));
-    return rank_t[s * 16 + (wl & 15)];
-  };
+  // entry of (s, wl = 0) in the integer form: ((A s + C + off) << 21) | (s << 10) = (((A << 11) | 1) s + ((C + off) << 11)) << 10,
+  // a 24-bit multiply-add and a shift that ORs the BFU's constant bits in
+  const uint32_t mul0 = ((uint32_t)O->rank_a << 11) | 1u, add0 = (uint32_t)(O->rank_c + O->rank_off) << 11;
+  const uint32_t step0 = O->rank_step0, step = O->rank_step;
   int remaining = 212 * 8 - 40 - 10 * n;                   // bitallocation.js:97-100
   int hs = 0;
   // distributeBitsRDO (:203-281): initial heap = BFUs below n with a non-zero scale factor
   // branch-free: every BFU writes its entry at the cursor, only live ones advance it (the next one overwrites the
   // slot otherwise; what the last dead one leaves behind is cleared with the sentinels)
+  // (in blocks of 13 BFUs that the scheduler cannot interleave: see totals_tabled)
 #pragma unroll
-  for (int b = 0; b < 52; b++) {
+  for (int b0 = 0; b0 < 52; b0 += 13) if (own_block()) {
+#pragma unroll
+  for (int b = b0; b < b0 + 13; b++) {
     if (b < n) {
       const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
-      hp[hs * 64] = heap_entry(rank_of(s, 0), kSpecs[b], s, 0, b);
+      const uint32_t fixed = ((uint32_t)kSpecsHost[b] << 16) | (uint32_t)b;
+      if constexpr (AFFINE) hp[hs * 64] = ((__umul24(mul0, (uint32_t)s) + add0) << 10) | fixed;
+      else hp[hs * 64] = ((uint32_t)rank_t[s * 16] << 21) | ((uint32_t)s << 10) | fixed;
       hs += (s != 0 && live) ? 1 : 0;
     }
+  }
   }
   for (int k = hs; k < kHeapSlotsPerLane; k++) hp[k * 64] = kSentinel;   // rank 0: below every live entry
   for (int i = (hs >> 1) - 1; i >= 0; i--) {               // heapify (:238-241); per-lane trip counts
@@ -112,13 +137,24 @@ __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_
   bool run = remaining >= 4 && hs > 0;
   while (__builtin_amdgcn_ballot_w64(run) != 0) {
     const uint32_t top = r0;
-    const int wl = (top >> 6) & 15, size = (top >> 16) & 31, s = (top >> 10) & 63;
-    const int cost = size << (wl == 0 ? 1 : 0);            // WORD_LENGTH_DELTA_BITS = [2,1,1,...]
+    const bool wl0 = (top & (15u << 6)) == 0;
+    const int size = (top >> 16) & 31;
+    const int cost = size << (wl0 ? 1 : 0);                // WORD_LENGTH_DELTA_BITS = [2,1,1,...]
     const bool fits = cost <= remaining;
-    const int nxt = wl + (fits ? 1 : 0);
-    const bool leaves = run && (!fits || nxt >= 15);
-    const uint32_t upd = (top & ~((0x3FFu << 21) | (15u << 6))) | ((uint32_t)nxt << 6);   // same BFU, new word length, rank 0
-    uint32_t v = upd | (rank_of(s, nxt) << 21);
+    uint32_t v, upd;                                       // the root after its step; the same BFU as it leaves (rank 0)
+    bool last_wl;                                          // the step reaches the last word length
+    if constexpr (AFFINE) {
+      v = top + (wl0 ? step0 : step);
+      upd = (fits ? v : top) & kLow;
+      last_wl = (v & (15u << 6)) == (15u << 6);
+    } else {
+      const int wl = (top >> 6) & 15, s = (top >> 10) & 63;
+      const int nxt = wl + (fits ? 1 : 0);
+      upd = (top & ~((0x3FFu << 21) | (15u << 6))) | ((uint32_t)nxt << 6);
+      v = upd | ((uint32_t)rank_t[s * 16 + (nxt & 15)] << 21);
+      last_wl = nxt >= 15;
+    }
+    const bool leaves = run && (!fits || last_wl);
     if (__builtin_amdgcn_ballot_w64(leaves) != 0) {
       // the last element replaces the root; the leaver is parked, rank 0, in the slot that frees
       const int li = hs - 1;
@@ -154,10 +190,9 @@ __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_
       const uint32_t val = mv1 ? (tr1 ? er : el) : v;
       if (mv0) { if (tr0) r2 = val; else r1 = val; }
       // levels 2..5 unrolled (a heap of 52 has six): node i2 in slots 3..6 against its children (the grandchildren above),
-      // then ONE more round trip for the children (slots 15..30) and grandchildren (31..62, clamped to the sentinel slot,
-      // whose rank 0 never wins) of the node in slots 7..14 it moves to.  Two round trips per step where the loop of
-      // heap_sift_down made up to five (one per level and one more to find that the last level has no children); a
-      // lane that stops early just stops writing.
+      // then ONE more round trip for the children (slots 15..30) and grandchildren (31..62) of the node in slots 7..14 it
+      // moves to.  Two round trips per step where the loop of heap_sift_down made up to five (one per level and one more
+      // to find that the last level has no children); a lane that stops early just stops writing.
       {
         const int i2 = 2 * i1 + 1 + (tr1 ? 1 : 0);
         const uint32_t c0 = tr1 ? g2 : g0, c1 = tr1 ? g3 : g1;
@@ -169,17 +204,23 @@ __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_
           const int i3 = 2 * i2 + 1 + (tr2 ? 1 : 0);                  // 7..14
           const uint32_t *s3 = hp + (2 * i3 + 1) * 64;                // children: slots 15..30
           const uint32_t d0 = s3[0], d1 = s3[64];
-          const int q = 4 * i3 + 3;                                   // grandchildren: slots 31..62
-          const uint32_t h0 = hp[min(q, 52) * 64], h1 = hp[min(q + 1, 52) * 64], h2 = hp[min(q + 2, 52) * 64], h3 = hp[min(q + 3, 52) * 64];
+          // grandchildren: the four slots from 4 i3 + 3, one base and immediate offsets.  Only nodes 12..14 have grandchildren
+          // past slot 51; of those only slots 51 (a real one) and 52 (the sentinel row, whose rank 0 never wins) matter, as the
+          // children of slot 25.  Such a lane reads slots 49..52 and takes the upper pair; a node from 26 on has no
+          // children, which its number says.
+          const bool far = i3 >= 12;
+          const uint32_t *s4 = hp + min(4 * i3 + 3, 49) * 64;
+          const uint32_t h0 = s4[0], h1 = s4[64], h2 = s4[128], h3 = s4[192];
           const bool tr3 = d1 > max(d0 | kLow, vmax);
           const bool tl3 = !tr3 && d0 > vmax;
           const bool mv3 = mv2 && (tr3 || tl3);
           if (mv2) hp[i3 * 64] = mv3 ? (tr3 ? d1 : d0) : v;
           const int i4 = 2 * i3 + 1 + (tr3 ? 1 : 0);                  // 15..30
-          const uint32_t e0 = tr3 ? h2 : h0, e1 = tr3 ? h3 : h1;
+          const bool upper = tr3 || far;
+          const uint32_t e0 = upper ? h2 : h0, e1 = upper ? h3 : h1;
           const bool tr4 = e1 > max(e0 | kLow, vmax);
           const bool tl4 = !tr4 && e0 > vmax;
-          const bool mv4 = mv3 && (tr4 || tl4);
+          const bool mv4 = mv3 && i4 < 26 && (tr4 || tl4);
           if (mv3) hp[i4 * 64] = mv4 ? (tr4 ? e1 : e0) : v;
           if (mv4) hp[(2 * i4 + 1 + (tr4 ? 1 : 0)) * 64] = v;          // slots 31..51: no children
         }
@@ -188,6 +229,94 @@ __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_
     run = run && remaining >= 4 && hs > 0;
   }
   hp[0] = r0; hp[64] = r1; hp[128] = r2;
+}
+
+// calculateTotalDistortion (:157-190), sequential double sum, index ascending, from the host's tables of its terms
+// (C1DevEncOpts::dist, verified there): one 16-byte lane-varying read and an exponent subtraction per BFU where the
+// reference's order of operations costs two conversions and three binary64 products.  BOUND: moreover the first lower
+// bounds of the seven smaller candidates (k_alloc_first), which are sums of the zero-bit terms this loop loads anyway.
+// The reads go where `biased` goes (constant address space): unconditional, so the compiler requests them in batches
+// (tools/isa_waits.py).  A silent BFU (s = 0) has word length 0 and a zero-bit term of 0.
+template <bool BOUND>
+__device__ __forceinline__ void totals_tabled(int n, const uint32_t (&sf)[13], const C1DevEncOpts *O, uint64_t res0, uint64_t res1,
+                                              uint64_t res2, uint64_t res3, double &total, double (&lbs)[7]) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const __attribute__((address_space(4))) d2 *dist = (const __attribute__((address_space(4))) d2 *)O->dist;
+  total = 0.0;
+#pragma unroll
+  for (int c = 0; c < 7; c++) lbs[c] = 0.0;
+  // (in blocks of 13 BFUs the scheduler cannot interleave: across all 52 it forms every "wl == 0" lane mask first and
+  // runs out of scalar registers to hold them)
+#pragma unroll
+  for (int b0 = 0; b0 < 52; b0 += 13) if (own_block()) {
+#pragma unroll
+  for (int b = b0; b < b0 + 13; b++) {
+    const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
+    const uint64_t word = b < 16 ? res0 : (b < 32 ? res1 : (b < 48 ? res2 : res3));
+    const int wl = (int)((word >> ((b & 15) * 4)) & 15);
+    const d2 zc = dist[dist_class(kSpecsHost[b]) * 64 + s];
+    // biased * size * INV_POWER_OF_TWO[wl + 1]
+    const double coded = __hiloint2double(__double2hiint(zc.y) - ((wl + 1) << 20), __double2loint(zc.y));
+    total += (b >= n || wl == 0) ? zc.x : coded;
+    if constexpr (BOUND) {
+      if (b >= 20) lbs[0] += zc.x;
+      if (b >= 28) lbs[1] += zc.x;
+      if (b >= 32) lbs[2] += zc.x;
+      if (b >= 36) lbs[3] += zc.x;
+      if (b >= 40) lbs[4] += zc.x;
+      if (b >= 44) lbs[5] += zc.x;
+      if (b >= 48) lbs[6] += zc.x;
+    }
+  }
+  }
+}
+
+// the same in the reference's own order of operations: for a biased table whose terms the host could not tabulate
+template <bool BOUND>
+__device__ __forceinline__ void totals_direct(int n, const uint32_t (&sf)[13], const C1DevEncOpts *O, uint64_t res0, uint64_t res1,
+                                              uint64_t res2, uint64_t res3, double &total, double (&lbs)[7]) {
+  const __attribute__((address_space(4))) double *biased = (const __attribute__((address_space(4))) double *)O->biased;
+  total = 0.0;
+#pragma unroll
+  for (int c = 0; c < 7; c++) lbs[c] = 0.0;
+#pragma unroll
+  for (int b0 = 0; b0 < 52; b0 += 13) if (own_block()) {
+#pragma unroll
+  for (int b = b0; b < b0 + 13; b++) {
+    const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
+    const uint64_t word = b < 16 ? res0 : (b < 32 ? res1 : (b < 48 ? res2 : res3));
+    const int wl = (int)((word >> ((b & 15) * 4)) & 15);
+    const int size = kSpecsHost[b];
+    // the table value is loaded whatever s is (index 0 is a valid entry) and masked afterwards: a lane-varying table read is
+    // a cache round trip, and under a condition each of the 52 is waited for where it is issued, one after the other
+    const double bs = biased[s];
+    // zeroBitDistortions[b] = Float32(biasedSF * 2 * size), 0 when sfi == 0 (:76,87-89)
+    const double z = s != 0 ? (double)f32(bs * 2.0 * (double)size) : 0.0;
+    const double ip2 = __hiloint2double((1023 - wl_bits(wl)) << 20, 0);     // INV_POWER_OF_TWO[bits] = 2^-bits
+    const double coded = s != 0 ? bs * ip2 * (double)size : 0.0;            // (a silent BFU adds nothing: the total is never -0)
+    total += (b >= n || wl == 0) ? z : coded;
+    if constexpr (BOUND) {
+      if (b >= 20) lbs[0] += z;
+      if (b >= 28) lbs[1] += z;
+      if (b >= 32) lbs[2] += z;
+      if (b >= 36) lbs[3] += z;
+      if (b >= 40) lbs[4] += z;
+      if (b >= 44) lbs[5] += z;
+      if (b >= 48) lbs[6] += z;
+    }
+  }
+  }
+}
+
+// One greedy heap per lane: candidate with `n` BFUs.  sf = the unit's 52 scale-factor indices (13 dwords).
+// Returns the 52 final word-length indices (4 bits each) and the candidate's total distortion; with BOUND also the
+// zero-bit distortion of BFUs 20.., 28.., 32.., .. 48.. upwards, each summed from its first BFU.
+template <bool BOUND>
+__device__ __forceinline__ void run_candidate(uint32_t *hp, int n, uint32_t (&sf)[13], const C1DevEncOpts *O,
+                                              bool live, uint64_t &res0, uint64_t &res1, uint64_t &res2,
+                                              uint64_t &res3, double &total, double (&lbs)[7]) {
+  if (O->rank_affine != 0) heap_phase<true>(hp, n, sf, O, live);
+  else heap_phase<false>(hp, n, sf, O, live);
   // Every BFU that ever entered the heap now sits in one of the first slots (as many as the heap started with) with its final
   // word length; the slots behind hold the sentinel, which names slot 52.  The word lengths are put in BFU order through the lane's own column of the heap: the
   // top byte of slot b takes BFU b's word length (a byte store: the rank bits up there are done with, and the low bits
@@ -216,26 +345,9 @@ __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, const uint32_
     res0 = (uint64_t)d[0] | ((uint64_t)d[1] << 32); res1 = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
     res2 = (uint64_t)d[4] | ((uint64_t)d[5] << 32); res3 = (uint64_t)d[6] | ((uint64_t)d[7] << 32);
   }
-  // calculateTotalDistortion (:157-190): sequential double sum, index ascending
-  total = 0.0;
-#pragma unroll
-  for (int b = 0; b < 52; b++) {
-    const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
-    const uint64_t word = b < 16 ? res0 : (b < 32 ? res1 : (b < 48 ? res2 : res3));
-    const int wl = (int)((word >> ((b & 15) * 4)) & 15);
-    const int size = kSpecs[b];
-    // the table value is loaded whatever s is (index 0 is a valid entry) and masked afterwards: a lane-varying table read is
-    // a cache round trip, and under a condition each of the 52 is waited for where it is issued, one after the other;
-    // unconditional, the compiler requests them in batches (tools/isa_waits.py)
-    const double bs = biased[s];
-    if (b >= n || wl == 0) {
-      // zeroBitDistortions[b] = Float32(biasedSF * 2 * size), 0 when sfi == 0 (:76,87-89)
-      total += s != 0 ? (double)f32(bs * 2.0 * (double)size) : 0.0;
-    } else if (s != 0) {
-      const double ip2 = __hiloint2double((1023 - wl_bits(wl)) << 20, 0);   // INV_POWER_OF_TWO[bits] = 2^-bits
-      total += bs * ip2 * (double)size;
-    }
-  }
+  reopen(sf);
+  if (O->dist_tables != 0) totals_tabled<BOUND>(n, sf, O, res0, res1, res2, res3, total, lbs);
+  else totals_direct<BOUND>(n, sf, O, res0, res1, res2, res3, total, lbs);
 }
 
 __device__ __forceinline__ void load_sfi(const uint8_t *side, int64_t unit, uint32_t (&sf)[13]) {
@@ -280,14 +392,17 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_first(C1EncodeLaunch L) {
   // white, pink and mixed material), units where a smaller candidate wins mostly below 0.4 (tools/alloc_tonal_stats.py).
   bool tonal = false;
   {
-    float n_coef = 0.0f, s_la = 0.0f;
+    // N and sum size_b s_b as integers, four BFUs (one dword of indices, one size) at a time: both stay far below 2^24, so
+    // the binary32 sums they stand for are exact
+    uint32_t n_int = 0, s_int = 0;
 #pragma unroll
-    for (int b = 0; b < 52; b++) {
-      const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
-      const float w = s != 0 ? (float)kSpecs[b] : 0.0f;
-      n_coef += w;
-      s_la = __builtin_fmaf(w, (float)s, s_la);
+    for (int g = 0; g < 13; g++) {
+      const uint32_t x = sf[g] & 0x3F3F3F3Fu;
+      const uint32_t nz = ((x + 0x3F3F3F3Fu) >> 6) & 0x01010101u;              // 1 in every byte whose index is not 0
+      n_int = __umul24(__builtin_amdgcn_sad_u8(nz, 0u, 0u), (uint32_t)kSpecsHost[4 * g]) + n_int;
+      s_int = __umul24(__builtin_amdgcn_sad_u8(x, 0u, 0u), (uint32_t)kSpecsHost[4 * g]) + s_int;
     }
+    const float n_coef = (float)n_int, s_la = (float)s_int;
     // sum size la = la_slope * sum size s + la_off * N
     const float la_sum = __builtin_fmaf(O->la_slope, s_la, O->la_off * n_coef);
     const float t_est = 1.442695f * n_coef * __builtin_amdgcn_exp2f((la_sum - 1136.0f) / n_coef);
@@ -296,7 +411,7 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_first(C1EncodeLaunch L) {
     for (int b = 48; b < 52; b++) {
       const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
       const float bs = (float)biased[s];
-      t6f += s != 0 ? bs * (2.0f * (float)kSpecs[b]) : 0.0f;
+      t6f += s != 0 ? bs * (2.0f * (float)kSpecsHost[b]) : 0.0f;
     }
     const bool mine = n_coef > 0.0f && t6f < 0.35f * t_est && !getenv_no_tonal(O);
     // one decision per wave (the majority's): a heap loop runs as long as any lane of the wave needs it, so skipping
@@ -305,25 +420,14 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_first(C1EncodeLaunch L) {
   }
   uint64_t r0, r1, r2, r3;
   double total;
-  run_candidate(heap + lane, 52, sf, O, live && !tonal, r0, r1, r2, r3, total);
-  // lower bounds of the other seven candidates: zero-bit distortion of the BFUs they do not code, each
-  // summed from its first uncoded BFU upwards (one pass, seven running sums)
+  // with it, the lower bounds of the other seven candidates: zero-bit distortion of the BFUs they do not code, each
+  // summed from its first uncoded BFU upwards (seven running sums in the pass that forms the total)
+  double lbs[7];
+  reopen(sf);
+  run_candidate<true>(heap + lane, 52, sf, O, live && !tonal, r0, r1, r2, r3, total, lbs);
   uint32_t survivors = 0;
   {
-    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-#pragma unroll
-    for (int b = 20; b < 52; b++) {
-      const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
-      const double bs = biased[s];                                  // unconditional: see run_candidate
-      const double z = s != 0 ? (double)f32(bs * 2.0 * (double)kSpecs[b]) : 0.0;
-      t0 += z;
-      if (b >= 28) t1 += z;
-      if (b >= 32) t2 += z;
-      if (b >= 36) t3 += z;
-      if (b >= 40) t4 += z;
-      if (b >= 44) t5 += z;
-      if (b >= 48) t6 += z;
-    }
+    const double t0 = lbs[0], t1 = lbs[1], t2 = lbs[2], t3 = lbs[3], t4 = lbs[4], t5 = lbs[5], t6 = lbs[6];
     // skip only when the bound is strictly above a finite 52-BFU total; NaN / Inf totals prune nothing
     const bool finite = total < __builtin_huge_val();
     survivors = (!(finite && t0 > total) ? 1u : 0u) | (!(finite && t1 > total) ? 2u : 0u) |
@@ -378,8 +482,6 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_first(C1EncodeLaunch L) {
 // computed, i.e. when it cannot even tie (:116-129 keeps the earlier candidate on ties).
 // =====================================================================================================
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-constexpr int kSpecsHost[52] = {8, 8, 8, 8, 4, 4, 4, 4, 8, 8, 8, 8, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 6, 7, 7, 7, 7, 9, 9, 9, 9, 10, 10, 10, 10,
-                                12, 12, 12, 12, 12, 12, 12, 12, 20, 20, 20, 20, 20, 20, 20, 20};   // kSpecs as compile-time constants
 __global__ __launch_bounds__(256) void k_alloc_bound(C1EncodeLaunch L) {
   __shared__ double biased_s[64];
   const C1DevEncOpts *O = L.opts;
@@ -508,7 +610,8 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_rest(C1EncodeLaunch L, con
     load_sfi(L.side, unit, sf);
     uint64_t r0, r1, r2, r3;
     double total;
-    run_candidate(heap + lane, bfu_amount(c), sf, O, live, r0, r1, r2, r3, total);
+    double unused[7];
+    run_candidate<false>(heap + lane, bfu_amount(c), sf, O, live, r0, r1, r2, r3, total, unused);
     total = total < __builtin_huge_val() ? total : __builtin_huge_val();
     if (live) store_candidate(L.cand, unit, c, total, r0, r1, r2, r3);
     if constexpr (FIRST_ROUND) {

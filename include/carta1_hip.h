@@ -104,6 +104,15 @@ int c1_table_fast_paths(int *scale_factor_bits, int *dequant_reciprocal);
  * the integer form A*sfi + C (word length 0) / A*sfi - B*(wl + 1) (wl >= 1) plus an offset, coef = {A, B, C, offset};
  * affine = 0: by the table of ranks of the Float32 priorities (coef zero).  Fails as encoding would on a bad table. */
 int c1_alloc_rank_form(const c1_encode_options *opts, int *affine, int *coef);
+/* Diagnostics (host only): the tables the bit allocation kernels derive from opts' biased table (any pointer may be NULL).
+ *  affine, steps   1 and the two words a successful heap step adds to the root's entry (from word length 0, from any
+ *                  other); 0 and zeros when the kernels look ranks up instead
+ *  rank            64 x 16: the rank field of the heap entry of (sfi, wl) as the kernels form it (sfi 0 and wl 15 unused)
+ *  dist_ok, dist   8 x 64 x 2 doubles per (BFU size in the order 4 6 7 8 9 10 12 20, sfi): the zero-bit term
+ *                  Float32(biased * 2 * size) and biased * size, whose exponent minus the bit count is the coded term;
+ *                  dist_ok = 1 when that equals the reference's biased * 2^-bits * size for every case (else the kernels
+ *                  form the terms as the reference does) */
+int c1_alloc_tables(const c1_encode_options *opts, int *affine, uint32_t *steps, uint16_t *rank, int *dist_ok, double *dist);
 
 /* ---- contexts ------------------------------------------------------------------------- */
 int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stream */, c1_ctx **out);
