@@ -108,6 +108,13 @@ class Context:
     """One c1_ctx: a device, a stream, tables and workspace on it."""
 
     def __init__(self, device=0, stream=None):
+        """stream: a hipStream_t as an integer (torch: `torch.cuda.Stream().cuda_stream`), or None for a stream of the
+        context's own.  On a caller's stream every *_device call is ordered like a kernel launch on it: after everything
+        queued before it, and finished with every buffer, inputs included, for everything queued after it.  The library
+        never destroys that stream (close() waits for the context's work on it), and several contexts may share one.
+        The trap: a zero handle means "own stream", and torch's legacy default stream has the handle 0, so
+        `Context(0, stream=torch.cuda.current_stream().cuda_stream)` outside a `torch.cuda.stream(...)` block gives a
+        context whose work is NOT ordered with the default stream's; synchronise by hand or use a stream of your own."""
         self._h = C.c_void_p()
         capi.check(capi.load().c1_ctx_create(int(device), C.c_void_p(stream) if stream else None, C.byref(self._h)))
         self.device = device

@@ -115,6 +115,16 @@ int c1_alloc_rank_form(const c1_encode_options *opts, int *affine, int *coef);
 int c1_alloc_tables(const c1_encode_options *opts, int *affine, uint32_t *steps, uint16_t *rank, int *dist_ok, double *dist);
 
 /* ---- contexts ------------------------------------------------------------------------- */
+/* A context works on one device and one stream: its own (hip_stream NULL; a non-blocking stream, ordered with nothing of
+ * the caller's, see c1_ctx_synchronize) or the caller's.  On a caller's stream every *_device call behaves like one kernel
+ * launch on that stream, whatever internal streams it uses:
+ *   - it is ordered after everything queued on the stream before it: inputs written by earlier work are read as written;
+ *   - when it returns, the stream has been made to wait for all of its work, so everything queued after it sees the finished
+ *     outputs and may overwrite every buffer of the call, inputs included;
+ *   - the host-resident entry points return with the stream drained, work queued before them included;
+ *   - the stream is never destroyed by the library: c1_ctx_destroy waits for the context's work on it and leaves it usable;
+ *   - several contexts may be created on one stream; their calls are ordered as they are issued.
+ * A call that changes the options or grows the workspace synchronises the stream on the host. */
 int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stream */, c1_ctx **out);
 int c1_ctx_destroy(c1_ctx *ctx);
 int c1_ctx_synchronize(c1_ctx *ctx);
