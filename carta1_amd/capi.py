@@ -37,6 +37,21 @@ class EncodeOptions(C.Structure):
                 ('fixed_block_modes', C.c_int32 * 3), ('reserved', C.c_int32)]
 
 
+class EncState(C.Structure):
+    """c1_enc_state: one channel's encoder half of the reference's BufferPool (483 floats, 1932 bytes)"""
+    _fields_ = [('qmf_low', C.c_float * 46), ('qmf_mid', C.c_float * 46), ('qmf_high', C.c_float * 39),
+                ('mdct_overlap', (C.c_float * 32) * 3), ('transient_mags', C.c_float * 256)]
+
+
+class DecState(C.Structure):
+    """c1_dec_state: one channel's decoder half of the pool (179 floats, 716 bytes)"""
+    _fields_ = [('qmf_low', C.c_float * 46), ('qmf_mid', C.c_float * 46), ('qmf_high', C.c_float * 39),
+                ('imdct_tail', (C.c_float * 16) * 3)]
+
+
+ENC_STATE_FLOATS = 483
+DEC_STATE_FLOATS = 179
+
 # every exported symbol with its signature; tests/test_abi.py checks this list against the header
 SIGNATURES = {
     'c1_abi_version': (C.c_int, []),
@@ -122,6 +137,16 @@ SIGNATURES = {
     'c1_find_scale_factors': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'c1_allocate_bits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_frames_from_states_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(EncodeOptions),
+                                                      C.c_void_p, C.c_void_p]),
+    'c1_encode_frames_from_states': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(EncodeOptions),
+                                               C.c_void_p, C.c_void_p]),
+    'c1_decode_frames_from_states_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_decode_frames_from_states': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_enc_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'c1_enc_stream_set_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'c1_dec_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'c1_dec_stream_set_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'c1_pack_spec_tap_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                           C.c_void_p, C.c_void_p]),
 }

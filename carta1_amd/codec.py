@@ -568,6 +568,32 @@ class Context:
         capi.check(capi.load().c1_qmf_synthesis_batch(self._h, b.ctypes.data, frames, halo_frames, out.ctypes.data))
         return out
 
+    def encode_frames_from_states(self, pcm, states, options=None, in_place=False):
+        """encode(options, pool)(frame) for n independent pools: pcm (n, 512) float32, states (n, 483) float32 rows laid out
+        as capi.EncState (qmf_low 46 | qmf_mid 46 | qmf_high 39 | mdct_overlap 3 x 32 | transient_mags 64 | 64 | 128).
+        Returns (units (n, 212) uint8, states after the frame (n, 483)); in_place overwrites `states` instead of returning a
+        new array.  Non-finite state raises."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1, 512)
+        st = _state_rows(states, capi.ENC_STATE_FLOATS, x.shape[0])
+        out = st if in_place else np.empty_like(st)
+        units = np.zeros((x.shape[0], 212), dtype=np.uint8)
+        opts = (options or EncoderOptions()).to_c()
+        capi.check(capi.load().c1_encode_frames_from_states(self._h, x.shape[0], x.ctypes.data, st.ctypes.data, C.byref(opts),
+                                                            units.ctypes.data, out.ctypes.data))
+        return units, out
+
+    def decode_frames_from_states(self, units, states, in_place=False):
+        """decode(pool)(unit) for n independent pools: units (n, 212) uint8, states (n, 179) float32 rows laid out as
+        capi.DecState (qmf_low 46 | qmf_mid 46 | qmf_high 39 | imdct_tail 3 x 16).  Returns (pcm (n, 512) float32, states
+        after the frame (n, 179))."""
+        u = np.ascontiguousarray(units, dtype=np.uint8).reshape(-1, 212)
+        st = _state_rows(states, capi.DEC_STATE_FLOATS, u.shape[0])
+        out = st if in_place else np.empty_like(st)
+        pcm = np.zeros((u.shape[0], 512), dtype=np.float32)
+        capi.check(capi.load().c1_decode_frames_from_states(self._h, u.shape[0], u.ctypes.data, st.ctypes.data, pcm.ctypes.data,
+                                                            out.ctypes.data))
+        return pcm, out
+
     def pack_spec_tap_device(self, coefs_ptr, eps_ptr, side_ptr, alloc_ptr, units, units_out_ptr, lists_ptr, all_long=True):
         """Test tap: the speculative quantizer + packer on caller-supplied coefficients, bounds and records (device pointers)."""
         capi.check(capi.load().c1_pack_spec_tap_device(
@@ -639,6 +665,20 @@ class EncoderStream:
         opts = options.to_c()
         capi.check(capi.load().c1_enc_stream_set_options(self._h, C.byref(opts)))
 
+    def get_state(self):
+        """The stream's state in the reference's BufferPool layout: a (channels, 483) float32 array, one capi.EncState per
+        row -- what the reference's pool would hold after the same pushes, option changes and restores (zeros when fresh)."""
+        out = np.zeros((self.channels, capi.ENC_STATE_FLOATS), dtype=np.float32)
+        capi.check(capi.load().c1_enc_stream_get_state(self._h, out.ctypes.data))
+        return out
+
+    def set_state(self, states):
+        """Replace the whole state of every channel, also mid-stream; the following pushes continue as the reference's
+        encode() continues from that pool.  states: (channels, 483) float32 (or anything np.asarray turns into it, a ctypes
+        array of capi.EncState included).  Non-finite entries raise and leave the stream as it was."""
+        st = _state_rows(states, capi.ENC_STATE_FLOATS, self.channels)
+        capi.check(capi.load().c1_enc_stream_set_state(self._h, st.ctypes.data))
+
     def close(self):
         if self._h:
             capi.load().c1_enc_stream_destroy(self._h)
@@ -670,6 +710,17 @@ class DecoderStream:
         capi.check(capi.load().c1_dec_stream_push_fields(self._h, frames, *[a.ctypes.data for a in arrs],
                                                          capi.ptr_array([o.ctypes.data for o in outs])))
         return outs
+
+    def get_state(self):
+        """(channels, 179) float32, one capi.DecState per row: the decoder half of the reference's pool after the same pushes"""
+        out = np.zeros((self.channels, capi.DEC_STATE_FLOATS), dtype=np.float32)
+        capi.check(capi.load().c1_dec_stream_get_state(self._h, out.ctypes.data))
+        return out
+
+    def set_state(self, states):
+        """Replace the decoder state of every channel; unit and field pushes continue from it, in any interleaving"""
+        st = _state_rows(states, capi.DEC_STATE_FLOATS, self.channels)
+        capi.check(capi.load().c1_dec_stream_set_state(self._h, st.ctypes.data))
 
     def close(self):
         if self._h:
@@ -715,6 +766,17 @@ def pinned_empty(shape, dtype=np.float32):
 
 
 _default_ctx = None
+
+
+def _state_rows(states, floats, rows):
+    """states as a contiguous (rows, floats) float32 array; a ctypes array of capi.EncState / DecState is viewed, not converted"""
+    if isinstance(states, (C.Array, C.Structure)):
+        st = np.frombuffer(states, dtype=np.float32).copy()
+    else:
+        st = np.ascontiguousarray(states, dtype=np.float32)
+    if st.size != rows * floats:
+        raise ValueError('expected %d state(s) of %d floats, got %d floats' % (rows, floats, st.size))
+    return st.reshape(rows, floats)
 
 
 def _field_arrays(fields):

@@ -410,8 +410,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state"};
 
 }  // namespace
 
@@ -2542,7 +2542,13 @@ int c1_decode_wav16_batch(c1_ctx *ctx, const uint8_t *units, int channels, int64
 // from the previous frame, which is right whenever that frame was detected.  After fixed modes it was not: the history is
 // then a fresh pool's zeros (detection never ran) or the bands of the last detected frame, kept here since the switch to
 // fixed modes, and the first frame of the next push under detection is encoded by the stage kernels against them.
-enum EncHistory { HIST_PREV = 0, HIST_ZEROS = 1, HIST_STORED = 2 };
+// After a restore (c1_enc_stream_set_state) the whole pool is explicit: d_state holds it, and the next two pushed frames are
+// encoded from it by the from-state kernel (c1_k_state.hip), which keeps d_state current.  Two frames on the PCM history is
+// real again and every later frame takes the usual path (all state after a frame is a function of that frame
+// and the 138 samples before it).  If the last of those frames ran under fixed modes, the detection history is neither a
+// previous frame's nor stored bands but the magnitudes d_state still holds (HIST_MAGS: restored verbatim, or written by a
+// from-state frame under detection); the first frame under detection after that is encoded from the state again.
+enum EncHistory { HIST_PREV = 0, HIST_ZEROS = 1, HIST_STORED = 2, HIST_MAGS = 3 };
 
 // scratch of the switch frame, one allocation carved per stream on first use; channels-interleaved where several
 struct EncSwitchScratch {
@@ -2573,6 +2579,9 @@ struct c1_enc_stream {
   float *d_stored = nullptr;       // channels x 512: the bands of the last detected frame (HIST_STORED), from d_sw's block
   void *d_sw_block = nullptr;
   EncSwitchScratch sw;
+  float *d_state = nullptr;        // channels x c1_enc_state, then the same again as scratch, then one zero state per channel
+  int state_frames = 0;            // frames still to be encoded from d_state (2 after a restore)
+  bool state_live = false;         // d_state is the stream's whole current state (nothing was pushed on the usual path since)
 };
 
 namespace {
@@ -2668,6 +2677,118 @@ int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *
   }
   return C1_OK;
 }
+
+// ---- the frame closures over explicit pools (c1_k_state.hip) ---------------------------------------------------------
+constexpr int kEncStateFloats = (int)(sizeof(c1_enc_state) / sizeof(float)), kDecStateFloats = (int)(sizeof(c1_dec_state) / sizeof(float));
+constexpr int64_t kMaxStatePools = (int64_t)1 << 27;
+constexpr int64_t kStateDecodeChunk = 65536;      // pools whose unpacked fields (2.4 KB each) one decode launch keeps in scratch
+
+// n pools on the context's stream: the from-state kernel into the workspace, then the encoder's own allocation and packing
+// kernels on it (one unit per pool).  Device pointers; pool i reads pcm + i * pcm_stride.  out may be in, or null.
+int encode_from_states_impl(c1_ctx *ctx, int64_t n, const float *pcm, int64_t pcm_stride, const float *in,
+                            const c1_encode_options *opts, uint8_t *units, float *out) {
+  int rc;
+  if ((rc = upload_opts(ctx, opts))) return rc;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if (n == 0) return C1_OK;
+  if ((rc = join_tail(ctx))) return rc;
+  const int64_t chunk = chunk_for_call(ctx, n, 1, false);
+  if ((rc = ensure_workspace(ctx, std::min(n, chunk)))) return rc;
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
+    const int64_t m = std::min(chunk, n - n0);
+    C1EncStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.pcm = pcm + n0 * pcm_stride;
+    K.pcm_stride = pcm_stride;
+    K.in = in + n0 * kEncStateFloats;
+    K.out = out ? out + n0 * kEncStateFloats : nullptr;
+    K.n = m;
+    K.tables = ctx->d_tables;
+    K.opts = ctx->d_opts;
+    K.coefs = ctx->d_coefs[0];
+    K.side = ctx->d_side[0];
+    K.detect = -1;
+    { ScopedTiming t(ctx, K_FROM_STATE); c1k_launch_encode_from_states(K, ctx->stream); }
+    C1EncodeLaunch L;
+    memset(&L, 0, sizeof L);
+    L.channels = 1;
+    L.frames = m;
+    L.tables = ctx->d_tables;
+    L.opts = ctx->d_opts;
+    L.coefs = ctx->d_coefs[0];
+    L.side = ctx->d_side[0];
+    L.alloc = ctx->d_alloc[0];
+    L.cand = ctx->d_cand[0];
+    L.work_count = ctx->d_work[0];
+    L.work_list = ctx->d_work[0] + 4;
+    L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
+    L.units = units + n0 * C1_UNIT_BYTES;
+    { ScopedTiming t(ctx, K_ALLOCATE); c1k_launch_allocate(L, ctx->stream); }
+    { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
+// the first non-finite entry of `count` states of `floats` floats each: C1_ERR_ARG naming pool (or channel) and field
+struct StateField { const char *name; int first, count; };
+const StateField kEncStateFields[] = {{"qmf_low", 0, 46}, {"qmf_mid", 46, 46}, {"qmf_high", 92, 39}, {"mdct_overlap", 131, 96}, {"transient_mags", 227, 256}};
+const StateField kDecStateFields[] = {{"qmf_low", 0, 46}, {"qmf_mid", 46, 46}, {"qmf_high", 92, 39}, {"imdct_tail", 131, 48}};
+int check_states_finite(const char *what, const char *unit, const void *states, int64_t count, int floats, const StateField *fields, int n_fields) {
+  const uint32_t *w = static_cast<const uint32_t *>(states);
+  for (int64_t i = 0; i < count; i++)
+    for (int k = 0; k < floats; k++)
+      if ((w[i * floats + k] & 0x7f800000u) == 0x7f800000u) {
+        for (int f = 0; f < n_fields; f++)
+          if (k >= fields[f].first && k < fields[f].first + fields[f].count)
+            return fail(C1_ERR_ARG, "%s: %s %lld: %s[%d] is not finite", what, unit, (long long)i, fields[f].name, k - fields[f].first);
+      }
+  return C1_OK;
+}
+
+int enc_stream_state_buffer(c1_enc_stream *s) {
+  if (s->d_state) return C1_OK;
+  const size_t bytes = 3 * (size_t)s->channels * sizeof(c1_enc_state);
+  HIP_TRY(hipMalloc(&s->d_state, bytes));
+  HIP_TRY(hipMemsetAsync(s->d_state, 0, bytes, s->ctx->stream));
+  return C1_OK;
+}
+
+// d_state <- the pool the reference would hold now, for a stream on the usual path: delay lines and overlap from the two
+// history frames (the from-state kernel, state output only, from a zero state: what a frame leaves is a function of that
+// frame and the 138 samples before it), the magnitudes from wherever the stream's EncHistory says they live
+int enc_stream_current_state(c1_enc_stream *s) {
+  if (s->state_live) return C1_OK;
+  c1_ctx *ctx = s->ctx;
+  int rc = enc_stream_state_buffer(s);
+  if (rc) return rc;
+  const int C = s->channels;
+  float *cur = s->d_state, *tmp = cur + (size_t)C * kEncStateFloats, *zero = tmp + (size_t)C * kEncStateFloats;
+  C1EncStateLaunch K;
+  memset(&K, 0, sizeof K);
+  K.pcm = s->d_hist;
+  K.pcm_stride = 1024;
+  K.in = zero;
+  K.out = tmp;
+  K.n = C;
+  K.tables = ctx->d_tables;
+  K.opts = ctx->d_opts;
+  K.state_only = 1;
+  c1k_launch_encode_from_states(K, ctx->stream);
+  K.pcm = s->d_hist + 512;
+  K.in = tmp;
+  K.detect = s->hist == HIST_PREV ? 1 : 0;     // the last pushed frame's own spectrum; else the zero state's zeros pass through
+  c1k_launch_encode_from_states(K, ctx->stream);
+  if (s->hist == HIST_STORED) c1k_launch_state_mags(ctx->d_tables, s->d_stored, C, tmp, ctx->stream);
+  else if (s->hist == HIST_MAGS)
+    HIP_TRY(hipMemcpy2DAsync(tmp + offsetof(c1_enc_state, transient_mags) / sizeof(float), sizeof(c1_enc_state),
+                             cur + offsetof(c1_enc_state, transient_mags) / sizeof(float), sizeof(c1_enc_state),
+                             sizeof(((c1_enc_state *)0)->transient_mags), (size_t)C, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(cur, tmp, (size_t)C * sizeof(c1_enc_state), hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(hipGetLastError());
+  s->state_live = true;
+  return C1_OK;
+}
 }  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
@@ -2698,6 +2819,11 @@ int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts) {
   if (!opts) return fail(C1_ERR_ARG, "opts is NULL");
   C1DevEncOpts probe;
   if ((rc = build_encode_opts(*opts, &probe))) return rc;
+  if (s->state_frames > 0) {
+    // the pool is explicit (d_state): the from-state kernel reads the options frame by frame, as the reference does
+    s->opts = *opts;
+    return C1_OK;
+  }
   if (opts_detect(s->opts) && !opts_detect(*opts) && s->hist == HIST_PREV) {
     if (s->pushed > 0) {
       // detection -> fixed modes: the history freezes at the last pushed frame's magnitudes; keep that frame's bands
@@ -2728,7 +2854,14 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   for (int c = 0; c < s->channels; c++)
     if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
   const bool detect = opts_detect(s->opts);
-  const bool switch_frame = detect && s->hist != HIST_PREV && s->pushed > 0;
+  // frames of this push that are encoded from the explicit state: the first two after a restore, or the first under
+  // detection when the detection history is a set of magnitudes only the state holds
+  int64_t from_state = std::min<int64_t>(frames, s->state_frames);
+  if (from_state == 0 && detect && s->hist == HIST_MAGS) {
+    if ((rc = enc_stream_current_state(s))) return rc;
+    from_state = 1;
+  }
+  const bool switch_frame = from_state == 0 && detect && s->hist != HIST_PREV && s->pushed > 0;
   if (switch_frame && (rc = enc_stream_scratch(s))) return rc;
   if (frames > s->cap_frames) {
     if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); }
@@ -2745,7 +2878,17 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
     HIP_TRY(hipMemcpyAsync(d + 1024, pcm[c], (size_t)frames * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     dptr[c] = d + 1024;
   }
-  if (switch_frame) {
+  if (from_state > 0) {
+    for (int64_t f = 0; f < from_state; f++)   // frame after frame: each continues the pool the one before left
+      if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
+                                        s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state))) return rc;
+    if (frames > from_state) {
+      const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
+      for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + from_state * 512;
+      if ((rc = encode_device_joined(ctx, rest, s->channels, frames - from_state, 2, &s->opts,
+                                     s->d_units + (size_t)from_state * s->channels * C1_UNIT_BYTES))) return rc;
+    }
+  } else if (switch_frame) {
     if ((rc = enc_stream_switch_frame(s, dptr, s->d_units))) return rc;
     if (frames > 1) {
       const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
@@ -2762,6 +2905,13 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   HIP_TRY(hipMemcpyAsync(units, s->d_units, (size_t)s->channels * frames * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   s->pushed += frames;
+  if (from_state > 0) {
+    if (s->state_frames > 0) s->state_frames -= (int)from_state;
+    s->state_live = frames == from_state;
+    if (!detect) s->hist = HIST_MAGS;              // the magnitudes d_state holds are the pool's transientDetection
+  } else {
+    s->state_live = false;
+  }
   if (detect) s->hist = HIST_PREV;
   return C1_OK;
 }
@@ -2774,6 +2924,7 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (s->d_buf) hipFree(s->d_buf);
   if (s->d_units) hipFree(s->d_units);
   if (s->d_sw_block) hipFree(s->d_sw_block);
+  if (s->d_state) hipFree(s->d_state);
   delete s;
   return C1_OK;
 }
@@ -2798,6 +2949,10 @@ struct c1_dec_stream {
   int32_t *d_prev_fields = nullptr;            // channels units, field_layout
   int32_t *h_stage = nullptr;                  // page-locked staging of a field push (one host-to-device copy)
   int64_t stage_cap = 0;                       // units
+  // after c1_dec_stream_set_state: the pool is explicit (d_state) and the next pushed frame is decoded from it by the
+  // from-state kernel; its fields are the history of everything behind it, as after any field push
+  bool restored = false;
+  float *d_state = nullptr;                    // channels x c1_dec_state, then one zero state per channel, then scratch
 };
 
 namespace {
@@ -2824,22 +2979,51 @@ int dec_stream_fields(c1_dec_stream *s, int64_t units, int32_t **out) {
   *out = s->d_fields[p];
   return C1_OK;
 }
+// the previous frame as fields: unpack the unit the last push ended with
+int dec_stream_prev_fields(c1_dec_stream *s) {
+  if (!s->have_prev || s->prev_fields.nbfu) return C1_OK;
+  if (!s->d_prev_fields) HIP_TRY(hipMalloc(&s->d_prev_fields, (size_t)(kFieldInts * s->channels) * sizeof(int32_t)));
+  const C1FieldPtrs pf = field_layout(s->d_prev_fields, s->channels);
+  c1k_launch_unpack_units(s->d_prev, s->channels, (int32_t *)pf.nbfu, (int32_t *)pf.modes, (int32_t *)pf.sfi, (int32_t *)pf.wl,
+                          (int32_t *)pf.q, s->ctx->stream);
+  s->prev_fields = pf;
+  return C1_OK;
+}
+int dec_stream_state_buffer(c1_dec_stream *s) {
+  if (s->d_state) return C1_OK;
+  const size_t bytes = 3 * (size_t)s->channels * sizeof(c1_dec_state);
+  HIP_TRY(hipMalloc(&s->d_state, bytes));
+  HIP_TRY(hipMemsetAsync(s->d_state, 0, bytes, s->ctx->stream));
+  return C1_OK;
+}
 // decode `frames` frames whose fields are at `cur` (layout over frames * channels units) from the stream's history, then make
 // the last of them the history; downloads the PCM and synchronises
 int dec_stream_decode_fields(c1_dec_stream *s, const C1FieldPtrs &cur, int64_t frames, float *const *pcm) {
   c1_ctx *ctx = s->ctx;
   int rc;
-  if (s->have_prev && !s->prev_fields.nbfu) {      // the previous frame as fields: unpack the unit the last push ended with
-    if (!s->d_prev_fields) HIP_TRY(hipMalloc(&s->d_prev_fields, (size_t)(kFieldInts * s->channels) * sizeof(int32_t)));
-    const C1FieldPtrs pf = field_layout(s->d_prev_fields, s->channels);
-    c1k_launch_unpack_units(s->d_prev, s->channels, (int32_t *)pf.nbfu, (int32_t *)pf.modes, (int32_t *)pf.sfi, (int32_t *)pf.wl,
-                            (int32_t *)pf.q, ctx->stream);
-    s->prev_fields = pf;
-  }
+  if (!s->restored && (rc = dec_stream_prev_fields(s))) return rc;
   float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
   for (int c = 0; c < s->channels; c++) dptr[c] = s->d_pcm + (size_t)c * s->cap_frames * 512;
   if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
-  if ((rc = launch_decode_fields(ctx, cur, s->prev_fields, s->channels, frames, s->have_prev ? 1 : 0, dptr))) return rc;
+  if (s->restored) {
+    // the first frame from the restored pool, the others from that frame's fields as their halo
+    C1DecStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.fields = cur;
+    K.in = s->d_state;
+    K.pcm = s->d_pcm;
+    K.pcm_stride = s->cap_frames * 512;
+    K.n = s->channels;
+    K.tables = ctx->d_tables;
+    { ScopedTiming t(ctx, K_FROM_STATE); c1k_launch_decode_from_states(K, ctx->stream); }
+    HIP_TRY(hipGetLastError());
+    if (frames > 1) {
+      float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
+      for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + 512;
+      if ((rc = launch_decode_fields(ctx, field_unit(cur, s->channels), cur, s->channels, frames - 1, 1, rest))) return rc;
+    }
+    s->restored = false;
+  } else if ((rc = launch_decode_fields(ctx, cur, s->prev_fields, s->channels, frames, s->have_prev ? 1 : 0, dptr))) return rc;
   s->prev_fields = field_unit(cur, (frames - 1) * s->channels);
   s->fields_next ^= 1;
   s->have_prev = true;
@@ -2877,8 +3061,8 @@ int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units, int64_t frames, f
   for (int c = 0; c < s->channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
   const size_t ub = (size_t)s->channels * C1_UNIT_BYTES;
   if ((rc = dec_stream_reserve(s, frames))) return rc;
-  if (s->have_prev && !s->prev_is_unit) {
-    // the previous frame is held as fields, which a unit cannot stand in for: unpack this push's units and decode them
+  if (s->restored || (s->have_prev && !s->prev_is_unit)) {
+    // the previous frame is held as fields (or the pool is a restored one), which a unit cannot stand in for: unpack this push's units and decode them
     // from fields too (k_unpack_units + k_decode_fields decode any unit exactly as k_decode does)
     const int64_t units_n = frames * s->channels;
     int32_t *d;
@@ -2950,7 +3134,182 @@ int c1_dec_stream_destroy(c1_dec_stream *s) {
   for (int p = 0; p < 2; p++) if (s->d_fields[p]) hipFree(s->d_fields[p]);
   if (s->d_prev_fields) hipFree(s->d_prev_fields);
   if (s->h_stage) hipHostFree(s->h_stage);
+  if (s->d_state) hipFree(s->d_state);
   delete s;
+  return C1_OK;
+}
+
+// ---- stream state in the reference's BufferPool layout: the frame closures over explicit pools, snapshot and restore -------
+int c1_encode_frames_from_states_device(c1_ctx *ctx, int64_t n, const float *pcm, const c1_enc_state *in, const c1_encode_options *opts,
+                                        uint8_t *units, c1_enc_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (n < 0 || n > kMaxStatePools) return fail(C1_ERR_ARG, "encode from states: n must be 0 .. 2^27, got %lld", (long long)n);
+  if (!pcm || !in || !opts || !units) return fail(C1_ERR_ARG, "encode from states: NULL argument");
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "encode from states: pcm must be 16-byte aligned on the device");
+  if (((uintptr_t)in | (uintptr_t)out) & 3) return fail(C1_ERR_ARG, "encode from states: states must be 4-byte aligned on the device");
+  return encode_from_states_impl(ctx, n, pcm, 512, reinterpret_cast<const float *>(in), opts, units, reinterpret_cast<float *>(out));
+}
+
+int c1_encode_frames_from_states(c1_ctx *ctx, int64_t n, const float *pcm, const c1_enc_state *in, const c1_encode_options *opts,
+                                 uint8_t *units, c1_enc_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (n < 0 || n > kMaxStageFrames) return fail(C1_ERR_ARG, "encode from states: n must be 0 .. 2^20, got %lld", (long long)n);
+  if (!pcm || !in || !opts || !units) return fail(C1_ERR_ARG, "encode from states: NULL argument");
+  C1DevEncOpts probe;
+  if ((rc = build_encode_opts(*opts, &probe))) return rc;
+  if (n == 0) return C1_OK;
+  if ((rc = check_states_finite("encode from states", "pool", in, n, kEncStateFloats, kEncStateFields, 5))) return rc;
+  DeviceScratch ds;
+  float *dp, *dst; uint8_t *du;
+  const size_t N = (size_t)n;
+  if ((rc = ds.alloc(&dp, N * 512)) || (rc = ds.alloc(&dst, N * kEncStateFloats)) || (rc = ds.alloc(&du, N * C1_UNIT_BYTES))) return rc;
+  HIP_TRY(hipMemcpyAsync(dp, pcm, N * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_enc_state), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = encode_from_states_impl(ctx, n, dp, 512, dst, opts, du, out ? dst : nullptr))) return rc;
+  HIP_TRY(hipMemcpyAsync(units, du, N * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+namespace {
+// device pointers; the unpacked fields of a chunk of pools live in the context's call scratch
+int decode_from_states_impl(c1_ctx *ctx, int64_t n, const uint8_t *units, const float *in, float *pcm, float *out) {
+  int rc;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if (n == 0) return C1_OK;
+  const int64_t chunk = std::min(n, kStateDecodeChunk);
+  if ((rc = ensure_io(ctx, (size_t)(kFieldInts * chunk) * sizeof(int32_t)))) return rc;
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
+    const int64_t m = std::min(chunk, n - n0);
+    const C1FieldPtrs f = field_layout(static_cast<int32_t *>(ctx->d_io), m);
+    c1k_launch_unpack_units(units + n0 * C1_UNIT_BYTES, m, (int32_t *)f.nbfu, (int32_t *)f.modes, (int32_t *)f.sfi, (int32_t *)f.wl,
+                            (int32_t *)f.q, ctx->stream);
+    C1DecStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.fields = f;
+    K.in = in + n0 * kDecStateFloats;
+    K.out = out ? out + n0 * kDecStateFloats : nullptr;
+    K.pcm = pcm + n0 * 512;
+    K.pcm_stride = 512;
+    K.n = m;
+    K.tables = ctx->d_tables;
+    { ScopedTiming t(ctx, K_FROM_STATE); c1k_launch_decode_from_states(K, ctx->stream); }
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+}  // namespace
+
+int c1_decode_frames_from_states_device(c1_ctx *ctx, int64_t n, const uint8_t *units, const c1_dec_state *in, float *pcm,
+                                        c1_dec_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (n < 0 || n > kMaxStatePools) return fail(C1_ERR_ARG, "decode from states: n must be 0 .. 2^27, got %lld", (long long)n);
+  if (!units || !in || !pcm) return fail(C1_ERR_ARG, "decode from states: NULL argument");
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "decode from states: pcm must be 16-byte aligned on the device");
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)units) & 3) return fail(C1_ERR_ARG, "decode from states: units and states must be 4-byte aligned on the device");
+  return decode_from_states_impl(ctx, n, units, reinterpret_cast<const float *>(in), pcm, reinterpret_cast<float *>(out));
+}
+
+int c1_decode_frames_from_states(c1_ctx *ctx, int64_t n, const uint8_t *units, const c1_dec_state *in, float *pcm, c1_dec_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (n < 0 || n > kMaxStageFrames) return fail(C1_ERR_ARG, "decode from states: n must be 0 .. 2^20, got %lld", (long long)n);
+  if (!units || !in || !pcm) return fail(C1_ERR_ARG, "decode from states: NULL argument");
+  if (n == 0) return C1_OK;
+  if ((rc = check_states_finite("decode from states", "pool", in, n, kDecStateFloats, kDecStateFields, 4))) return rc;
+  DeviceScratch ds;
+  float *dp, *dst; uint8_t *du;
+  const size_t N = (size_t)n;
+  if ((rc = ds.alloc(&dp, N * 512)) || (rc = ds.alloc(&dst, N * kDecStateFloats)) || (rc = ds.alloc(&du, N * C1_UNIT_BYTES))) return rc;
+  HIP_TRY(hipMemcpyAsync(du, units, N * C1_UNIT_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_dec_state), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = decode_from_states_impl(ctx, n, du, dst, dp, out ? dst : nullptr))) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm, dp, N * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_dec_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_enc_stream_get_state(c1_enc_stream *s, c1_enc_state *out) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!out) return fail(C1_ERR_ARG, "out is NULL");
+  if ((rc = enc_stream_current_state(s))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, s->d_state, (size_t)s->channels * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_enc_stream_set_state(c1_enc_stream *s, const c1_enc_state *in) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!in) return fail(C1_ERR_ARG, "in is NULL");
+  if ((rc = check_states_finite("encoder state", "channel", in, s->channels, kEncStateFloats, kEncStateFields, 5))) return rc;
+  if ((rc = enc_stream_state_buffer(s))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_state, in, (size_t)s->channels * sizeof(c1_enc_state), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  s->state_frames = 2;
+  s->state_live = true;
+  return C1_OK;
+}
+
+int c1_dec_stream_get_state(c1_dec_stream *s, c1_dec_state *out) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!out) return fail(C1_ERR_ARG, "out is NULL");
+  const size_t bytes = (size_t)s->channels * sizeof(c1_dec_state);
+  if (!s->restored && !s->have_prev) { memset(out, 0, bytes); return C1_OK; }   // a fresh pool
+  if ((rc = dec_stream_state_buffer(s))) return rc;
+  const float *src = s->d_state;
+  if (!s->restored) {
+    // what a frame leaves is a function of that frame alone: decode the previous frame once more, state output only
+    if ((rc = dec_stream_prev_fields(s))) return rc;
+    float *zero = s->d_state + (size_t)s->channels * kDecStateFloats, *tmp = zero + (size_t)s->channels * kDecStateFloats;
+    C1DecStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.fields = s->prev_fields;
+    K.in = zero;
+    K.out = tmp;
+    K.n = s->channels;
+    K.tables = ctx->d_tables;
+    c1k_launch_decode_from_states(K, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    src = tmp;
+  }
+  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_dec_stream_set_state(c1_dec_stream *s, const c1_dec_state *in) {
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if (!in) return fail(C1_ERR_ARG, "in is NULL");
+  if ((rc = check_states_finite("decoder state", "channel", in, s->channels, kDecStateFloats, kDecStateFields, 4))) return rc;
+  if ((rc = dec_stream_state_buffer(s))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_state, in, (size_t)s->channels * sizeof(c1_dec_state), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  s->restored = true;
   return C1_OK;
 }
 

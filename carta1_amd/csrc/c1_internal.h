@@ -170,6 +170,34 @@ struct C1DecodeFieldsLaunch {
   int run_frames;        // consecutive frames of one channel a wave decodes (set by the launcher)
 };
 
+// The frame closures over explicit BufferPool state (c1_k_state.hip): pool i encodes the frame at pcm + i * pcm_stride from
+// in[i] (c1_enc_state, 483 floats) and leaves its pool in out[i]; out may be in, or null.  Coefficients and side records go
+// to coefs + i * 512 / side + i * kSideBytes, where the allocation and packing kernels take over (channels = 1, frames = n).
+struct C1EncStateLaunch {
+  const float *pcm;      // 16-byte aligned, as pcm_stride * 4 is
+  int64_t pcm_stride;    // floats between the frames of consecutive pools
+  const float *in;
+  float *out;
+  int64_t n;
+  const C1DevTables *tables;
+  const C1DevEncOpts *opts;
+  float *coefs;
+  uint8_t *side;
+  int detect;            // -1: as opts say; 0: transient_mags pass through; 1: the frame's magnitudes are written
+  int state_only;        // no coefficients, no side records, no block decision: only the state after the frame
+};
+// decode twin: pool i decodes the frame fields of unit i (layout of c1_unpack_units) from in[i] (c1_dec_state, 179 floats)
+// into pcm + i * pcm_stride (null: state only) and leaves its pool in out[i]; out may be in, or null
+struct C1DecStateLaunch {
+  C1FieldPtrs fields;
+  const float *in;
+  float *out;
+  float *pcm;
+  int64_t pcm_stride;
+  int64_t n;
+  const C1DevTables *tables;
+};
+
 // Run length of the frame-walking kernels: consecutive frames of one channel a wave walks, carrying the filter state
 // (one extra warm-up frame per run).  Measured on MI355X (1 M stereo frames, A/B in one session): 64-frame runs beat
 // runs sized to fill the wave slots exactly once (205 frames: every wave then finishes at the same moment, and the
@@ -281,6 +309,11 @@ void c1k_launch_decode(const C1DecodeLaunch &L, bool binary32, hipStream_t strea
 // is memory-safe (nbfu clamped to 0..52, wl & 15, sfi & 63 on the read path); the output is the reference's for nbfu 0..52 and,
 // below nbfu, wl 0..15 and sfi 0..63
 void c1k_launch_decode_fields(const C1DecodeFieldsLaunch &L, hipStream_t stream);
+// the frame closures over explicit pool state (c1_k_state.hip); n <= 0 launches nothing
+void c1k_launch_encode_from_states(const C1EncStateLaunch &L, hipStream_t stream);
+void c1k_launch_decode_from_states(const C1DecStateLaunch &L, hipStream_t stream);
+// performFFT's magnitudes of `rows` stored band rows (512 floats each) into the transient_mags of states[0 .. rows)
+void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_t rows, float *states, hipStream_t stream);
 // kind_mask: bit k = fill the 512-frame segments with (segment & 3) == k (15 = all)
 void c1k_launch_generate_white(const uint32_t *frame_states, int64_t frames, float *pcm, int kind_mask, double amp, hipStream_t stream);
 void c1k_launch_generate_pink(const uint32_t *segment_states, int64_t frames, float *pcm, int kind_mask, hipStream_t stream);

@@ -525,6 +525,46 @@ napi_value EncStreamSetOptions(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return nullptr;
 }
+// Stream state in the reference's BufferPool layout (c1_enc_state / c1_dec_state, include/carta1_hip.h) as one Float32Array of
+// channels * 483 (encoder) or channels * 179 (decoder) floats, the fields of each channel back to back; core/buffers.js gives
+// them the reference's names.
+// encStreamGetState(stream, channels) / decStreamGetState(stream, channels) -> Float32Array
+template <typename Stream, typename State, int (*Get)(Stream *, State *)>
+napi_value StreamGetState(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  Stream *s;
+  int32_t channels = 1;
+  if (!get_external(env, argv[0], &s)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &channels));
+  if (channels < 1 || channels > C1_MAX_CHANNELS) { napi_throw_type_error(env, nullptr, "channels must be 1 or 2"); return nullptr; }
+  float *p = nullptr;
+  napi_value out = make_f32(env, (size_t)channels * (sizeof(State) / sizeof(float)), &p);
+  if (!out || !p) { napi_throw_error(env, nullptr, "could not allocate the result"); return nullptr; }
+  const int rc = Get(s, reinterpret_cast<State *>(p));
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+// encStreamSetState(stream, channels, Float32Array) / decStreamSetState(stream, channels, Float32Array)
+template <typename Stream, typename State, int (*Set)(Stream *, const State *)>
+napi_value StreamSetState(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  Stream *s;
+  int32_t channels = 1;
+  void *d;
+  size_t n;
+  if (!get_external(env, argv[0], &s)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &channels));
+  if (!get_typed(env, argv[2], napi_float32_array, &d, &n)) return nullptr;
+  if (channels < 1 || channels > C1_MAX_CHANNELS || n != (size_t)channels * (sizeof(State) / sizeof(float))) {
+    napi_throw_type_error(env, nullptr, "state: wrong length");
+    return nullptr;
+  }
+  const int rc = Set(s, static_cast<const State *>(d));
+  if (rc) return throw_c1(env, rc);
+  return nullptr;
+}
 napi_value DecStreamCreate(napi_env env, napi_callback_info info) {
   napi_value argv[2];
   if (!get_args(env, info, 2, argv)) return nullptr;
@@ -940,6 +980,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamGetState", nullptr, StreamGetState<c1_enc_stream, c1_enc_state, c1_enc_stream_get_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamSetState", nullptr, StreamSetState<c1_enc_stream, c1_enc_state, c1_enc_stream_set_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decStreamGetState", nullptr, StreamGetState<c1_dec_stream, c1_dec_state, c1_dec_stream_get_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decStreamSetState", nullptr, StreamSetState<c1_dec_stream, c1_dec_state, c1_dec_stream_set_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamCreate", nullptr, DecStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamPush", nullptr, DecStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decStreamPushFields", nullptr, DecStreamPushFields, nullptr, nullptr, nullptr, napi_default, nullptr},

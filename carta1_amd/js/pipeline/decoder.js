@@ -12,7 +12,13 @@ export function decode(bufferPool = new BufferPool()) {
   if (!bufferPool) throwError('imdctStage: bufferPool is required')
   return (frameData) => {
     const addon = native()
-    if (!bufferPool.decoderStream) bufferPool.decoderStream = addon.decStreamCreate(context(), 1)
+    if (!bufferPool.decoderStream) {
+      bufferPool.decoderStream = addon.decStreamCreate(context(), 1)
+      if (bufferPool.pendingDecoderState) { // a state set before the stream existed (BufferPool.setDecoderState)
+        addon.decStreamSetState(bufferPool.decoderStream, 1, bufferPool.pendingDecoderState)
+        bufferPool.pendingDecoderState = null
+      }
+    }
     if (frameData instanceof Uint8Array) return addon.decStreamPush(bufferPool.decoderStream, frameData, 1)[0]
     const f = frameFields(frameData)
     return addon.decStreamPushFields(bufferPool.decoderStream, f.nbfu, f.modes, f.sfi, f.wl, f.q, 1)[0]

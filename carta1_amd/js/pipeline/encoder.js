@@ -25,6 +25,10 @@ export function encode(options = new EncoderOptions(), bufferPool = new BufferPo
     if (!bufferPool.encoderStream) {
       bufferPool.encoderStream = addon.encStreamCreate(context(), 1, packed)
       bufferPool.encoderOptionsKey = key
+      if (bufferPool.pendingEncoderState) { // a state set before the stream existed (BufferPool.setEncoderState)
+        addon.encStreamSetState(bufferPool.encoderStream, 1, bufferPool.pendingEncoderState)
+        bufferPool.pendingEncoderState = null
+      }
     } else if (bufferPool.encoderOptionsKey !== key) {
       addon.encStreamSetOptions(bufferPool.encoderStream, packed)
       bufferPool.encoderOptionsKey = key

@@ -131,7 +131,8 @@ int c1_ctx_synchronize(c1_ctx *ctx);
 /* milliseconds the device spent in the named kernel during the most recent *_device call on this
  * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), in the most recent c1_pack_units call
  * ("pack_units"), or in the most recent decode from frame fields -- c1_decode_fields_*, c1_dec_stream_push_fields or a
- * unit push that follows one ("decode_fields") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
+ * unit push that follows one ("decode_fields") -- or in the from-state kernel of the most recent c1_*_frames_from_states*
+ * call ("from_state") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
  * must have been set before the call */
 int c1_ctx_set_profiling(c1_ctx *ctx, int enabled);
 int c1_ctx_kernel_ms(c1_ctx *ctx, const char *name, double *ms, int *launches);
@@ -252,6 +253,59 @@ int c1_dec_stream_destroy(c1_dec_stream *s);
  * of that frame alone).  The domain is validated as c1_decode_fields_batch validates it; frames 0 .. 2^20 per call. */
 int c1_dec_stream_push_fields(c1_dec_stream *s, int64_t frames, const int32_t *nbfu, const int32_t *block_modes,
                               const int32_t *sfi, const int32_t *wl, const int32_t *quantized, float *const *pcm /* host */);
+
+/* ---- stream state in the reference's BufferPool layout (codec/core/buffers.js:30-72).  In the reference a stream IS its
+ *      pool: encode(options, pool) and decode(pool) continue from whatever the pool holds (encoder.js:438-441), so a pool can
+ *      be checkpointed, copied to fork a stream, or handed to another worker.  These two structs are that state, one per
+ *      channel, and the entry points below read it, write it and encode / decode from it.  Finite values only, denormals
+ *      and -0 included; every value is honoured bit for bit, also state no PCM or unit history could have produced. ------- */
+typedef struct c1_enc_state {   /* 483 floats = 1932 bytes */
+  float qmf_low[46];            /* qmfDelays.lowBand:  the last 46 inputs of the first QMF stage (encoder.js:66)          */
+  float qmf_mid[46];            /* qmfDelays.midBand:  the last 46 inputs of the second stage (:75)                       */
+  float qmf_high[39];           /* qmfDelays.highBand: the last 39 high-band samples, its delay (:84-90)                  */
+  float mdct_overlap[3][32];    /* mdctOverlap: W[i] * the last 32 samples of every band (:309-316)                       */
+  float transient_mags[256];    /* transientDetection, 64 | 64 | 128: performFFT's magnitudes of the last frame detection
+                                   ran on (:142); untouched by frames under fixed block modes (:130-132)                 */
+} c1_enc_state;
+typedef struct c1_dec_state {   /* 179 floats = 716 bytes */
+  float qmf_low[46], qmf_mid[46], qmf_high[39];   /* the decoder's qmfDelays, as c1_qmf_synthesis_batch's comment defines them */
+  float imdct_tail[3][16];      /* the last 16 entries of imdctOverlap[band], the only ones that carry (c1_imdct_batch's comment) */
+} c1_dec_state;
+
+/* The frame closures over explicit pools, batched: the reference's encode(options, pool)(frame) and decode(pool)(unit) for n
+ * independent pools at once.  Pool i encodes pcm[i*512 ..] from in[i] into units[i*212 ..] and leaves its pool in out[i]
+ * (decode: units[i*212 ..] from in[i] into pcm[i*512 ..]).  out may be in (in place) or NULL; n == 0 writes nothing.  All
+ * pools share opts: detection -- the frame's magnitudes are compared with in[i].transient_mags and written to out[i] -- or
+ * fixed block modes, any mix of long and short, under which transient_mags passes through unchanged (encoder.js:130-132);
+ * any supported allocation bias.  Number model: the reference's always (binary64 operations, binary32 at every typed-array
+ * store): nothing is speculated and c1_ctx_set_decode_precision does not apply.  C1_ERR_ARG for a NULL pointer or n out of range. */
+/* device pointers, asynchronous on the context's stream (the caller's-stream contract above); n 0 .. 2^27; pcm 16-byte
+ * aligned, units (decode) and states 4-byte aligned.  The state is not checked: for non-finite entries the output is unspecified, and no access leaves the buffers. */
+int c1_encode_frames_from_states_device(c1_ctx *ctx, int64_t n, const float *pcm, const c1_enc_state *in,
+                                        const c1_encode_options *opts, uint8_t *units, c1_enc_state *out);
+int c1_decode_frames_from_states_device(c1_ctx *ctx, int64_t n, const uint8_t *units, const c1_dec_state *in, float *pcm,
+                                        c1_dec_state *out);
+/* host pointers, synchronous; n 0 .. 2^20.  A non-finite state entry is C1_ERR_ARG, naming its pool and field. */
+int c1_encode_frames_from_states(c1_ctx *ctx, int64_t n, const float *pcm, const c1_enc_state *in,
+                                 const c1_encode_options *opts, uint8_t *units, c1_enc_state *out);
+int c1_decode_frames_from_states(c1_ctx *ctx, int64_t n, const uint8_t *units, const c1_dec_state *in, float *pcm,
+                                 c1_dec_state *out);
+
+/* Snapshot and restore of a stream: host pointers, `channels` entries.  get_state returns what the reference's pool would hold
+ * after the same calls -- pushes, option changes and earlier restores; every field zero on a fresh stream.  transient_mags is
+ * the spectrum of the last frame detection ran on: the last pushed frame while detection is on, the kept frame after a switch
+ * to fixed modes, the restored values verbatim when nothing was detected since a restore, zeros when detection never ran.
+ * set_state replaces the whole state of every channel, also mid-stream: whatever PCM, unit or field history the stream held
+ * stops counting, and the following pushes (units or fields, in any interleaving; under later c1_enc_stream_set_options calls
+ * too) continue as the reference continues from that pool.  set_state then get_state returns the same bits.  A non-finite
+ * entry is C1_ERR_ARG and leaves the stream as it was.  How: the two frames after an encoder restore, and the frame after a
+ * decoder restore, run through the from-state kernels; from then on the stream's own PCM / unit history is real again
+ * (all state after a frame is a function of that frame and the 138 samples before it; the decoder's, of that
+ * frame's unit alone). */
+int c1_enc_stream_get_state(c1_enc_stream *s, c1_enc_state *out);
+int c1_enc_stream_set_state(c1_enc_stream *s, const c1_enc_state *in);
+int c1_dec_stream_get_state(c1_dec_stream *s, c1_dec_state *out);
+int c1_dec_stream_set_state(c1_dec_stream *s, const c1_dec_state *in);
 
 /* ---- device-resident synthetic input for measurement ------------- */
 enum { C1_SIGNAL_WHITE = 0, C1_SIGNAL_PINK_BURSTS = 1, C1_SIGNAL_MIXED = 2, C1_SIGNAL_PARTIALS = 3 };
