@@ -143,6 +143,14 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     'c1_decode_frames_from_states_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_decode_frames_from_states': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_signals_device': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                           C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
+    'c1_decode_signals_device': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    'c1_encode_signals': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                    C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
+    'c1_decode_signals': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     'c1_enc_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'c1_enc_stream_set_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'c1_dec_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),

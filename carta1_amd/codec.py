@@ -594,6 +594,66 @@ class Context:
                                                             out.ctypes.data))
         return pcm, out
 
+    # ---- n signals of any lengths, each from its own pool, in one call (include/carta1_hip.h, c1_*_signals*) ----
+    def encode_signals(self, signals, options=None, states=None, return_states=False, in_place=False):
+        """signals: a list of float32 arrays, each one mono signal (zero padded to whole frames, as encode_pcm pads).  Signal i
+        is encoded as its own stream from states[i] ((n, 483) float32 rows laid out as capi.EncState; None: fresh pools).
+        Returns a list of (frames_i, 212) uint8 arrays, and with return_states the (n, 483) pools after every signal's last
+        frame as well; in_place writes those into `states`.  An empty signal gives no units and its pool unchanged."""
+        pcm, off = signals_layout([pad_signal(x) for x in signals])
+        n = off.size - 1
+        st = None if states is None else _state_rows(states, capi.ENC_STATE_FLOATS, n)
+        if in_place and st is None:
+            raise ValueError('in_place needs states')
+        out = st if in_place else (np.zeros((n, capi.ENC_STATE_FLOATS), dtype=np.float32) if return_states else None)
+        units = np.zeros((int(off[-1]), 212), dtype=np.uint8)
+        opts = (options or EncoderOptions()).to_c()
+        capi.check(capi.load().c1_encode_signals(self._h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), pcm.ctypes.data,
+                                                 st.ctypes.data if st is not None else None, C.byref(opts), units.ctypes.data,
+                                                 out.ctypes.data if out is not None else None))
+        res = split_rows(units, off)
+        return (res, out) if (return_states or in_place) else res
+
+    def decode_signals(self, units_list, states=None, return_states=False, in_place=False):
+        """units_list: a list of (frames_i, 212) uint8 arrays, each one mono signal's sound units; states: (n, 179) float32 rows
+        laid out as capi.DecState, or None for fresh pools.  Returns a list of float32 arrays of frames_i * 512 samples, and
+        with return_states the (n, 179) pools after every signal's last unit."""
+        rows = [np.ascontiguousarray(u, dtype=np.uint8).reshape(-1, 212) for u in units_list]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            off[1:] = np.cumsum([r.shape[0] for r in rows])
+        u = np.concatenate(rows) if rows else np.zeros((0, 212), dtype=np.uint8)
+        u = np.ascontiguousarray(u)
+        n = len(rows)
+        st = None if states is None else _state_rows(states, capi.DEC_STATE_FLOATS, n)
+        if in_place and st is None:
+            raise ValueError('in_place needs states')
+        out = st if in_place else (np.zeros((n, capi.DEC_STATE_FLOATS), dtype=np.float32) if return_states else None)
+        pcm = np.zeros(int(off[-1]) * 512, dtype=np.float32)
+        capi.check(capi.load().c1_decode_signals(self._h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), u.ctypes.data,
+                                                 st.ctypes.data if st is not None else None, pcm.ctypes.data,
+                                                 out.ctypes.data if out is not None else None))
+        res = [pcm[int(off[i]) * 512:int(off[i + 1]) * 512] for i in range(n)]
+        return (res, out) if (return_states or in_place) else res
+
+    def encode_signals_device(self, frame_offsets, pcm_ptr, units_ptr, states_ptr=None, out_states_ptr=None, options=None,
+                              c_options=None):
+        """raw device pointers (e.g. torch tensor .data_ptr()); frame_offsets: n + 1 host integers.  Asynchronous on the
+        context's stream."""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        opts = c_options if c_options is not None else (options or EncoderOptions()).to_c()
+        capi.check(capi.load().c1_encode_signals_device(
+            self._h, off.size - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(pcm_ptr),
+            C.c_void_p(states_ptr) if states_ptr else None, C.byref(opts), C.c_void_p(units_ptr),
+            C.c_void_p(out_states_ptr) if out_states_ptr else None))
+
+    def decode_signals_device(self, frame_offsets, units_ptr, pcm_ptr, states_ptr=None, out_states_ptr=None):
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        capi.check(capi.load().c1_decode_signals_device(
+            self._h, off.size - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(units_ptr),
+            C.c_void_p(states_ptr) if states_ptr else None, C.c_void_p(pcm_ptr),
+            C.c_void_p(out_states_ptr) if out_states_ptr else None))
+
     def pack_spec_tap_device(self, coefs_ptr, eps_ptr, side_ptr, alloc_ptr, units, units_out_ptr, lists_ptr, all_long=True):
         """Test tap: the speculative quantizer + packer on caller-supplied coefficients, bounds and records (device pointers)."""
         capi.check(capi.load().c1_pack_spec_tap_device(
@@ -851,8 +911,76 @@ def encode_aea_pcm(channels, options=None, ctx=None):
     return aea_header(title, units.shape[0], len(channels)) + units.tobytes()
 
 
-def decode_aea_pcm(data, ctx=None):
-    """decodeAeaPcm (processor.js:628-654): bytes / bytearray / ndarray(uint8) -> list of float32 arrays."""
+# ---- many items in one call: the pure host part (layout only, no device) ---------------------------------------------
+def pad_signal(x):
+    """one mono signal as float32, zero padded to whole frames (frameBufferToFrames, processor.js:246-279)"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if x.size % 512 == 0:
+        return x
+    p = np.zeros((x.size + 511) // 512 * 512, dtype=np.float32)
+    p[:x.size] = x
+    return p
+
+
+def signals_layout(signals):
+    """whole-frame signals -> (the concatenated PCM, int64 frame offsets [n + 1]) as the c1_*_signals* calls take them"""
+    for x in signals:
+        if x.size % 512:
+            raise ValueError('signals must hold whole frames of 512 samples')
+    off = np.zeros(len(signals) + 1, dtype=np.int64)
+    if signals:
+        off[1:] = np.cumsum([x.size // 512 for x in signals])
+    pcm = np.concatenate(signals) if signals else np.zeros(0, dtype=np.float32)
+    return np.ascontiguousarray(pcm, dtype=np.float32), off
+
+
+def split_rows(rows, off):
+    return [rows[int(off[i]):int(off[i + 1])] for i in range(off.size - 1)]
+
+
+def items_to_signals(items):
+    """items, each [L] or [L, R] -> (signals, channel counts): one padded mono signal per channel in item order, both channels
+    of an item padded to the longer one (encode_pcm does the same for one item)"""
+    signals, counts = [], []
+    for channels in items:
+        _check_channels(channels)
+        frames = (max(len(c) for c in channels) + 511) // 512
+        for c in channels:
+            p = np.zeros(frames * 512, dtype=np.float32)
+            p[:len(c)] = c
+            signals.append(p)
+        counts.append(len(channels))
+    return signals, counts
+
+
+def interleave_item_units(signal_units, counts):
+    """per-signal units (as items_to_signals ordered the signals) -> per item (frames * channels, 212), interleaved L, R"""
+    out, k = [], 0
+    for nch in counts:
+        chans = signal_units[k:k + nch]
+        k += nch
+        u = np.zeros((chans[0].shape[0] * nch, 212), dtype=np.uint8)
+        for c in range(nch):
+            u[c::nch] = chans[c]
+        out.append(u)
+    return out
+
+
+def deinterleave_item_units(item_units, counts):
+    """the inverse: per item (frames * channels, 212) -> one (frames, 212) array per channel, in item order"""
+    out = []
+    for u, nch in zip(item_units, counts):
+        u = np.asarray(u, dtype=np.uint8).reshape(-1, 212)
+        if u.shape[0] % nch:
+            raise ValueError('an item of %d channels needs a multiple of %d units' % (nch, nch))
+        for c in range(nch):
+            out.append(np.ascontiguousarray(u[c::nch]))
+    return out
+
+
+def aea_image_units(data):
+    """one AEA image -> (units (n, 212) with the dummy right unit behind a lone trailing left one, channel count):
+    decodeAeaPcm's reading of a file (processor.js:628-654, :222-232, :516-521)"""
     if isinstance(data, np.ndarray):
         data = data.tobytes()
     if not isinstance(data, (bytes, bytearray, memoryview)):
@@ -869,6 +997,37 @@ def decode_aea_pcm(data, ctx=None):
         units = np.concatenate([units, dummy])
     if nch not in (1, 2):
         raise ValueError('Unsupported channel count: %d' % nch)
+    return units, nch
+
+
+def encode_aea_pcm_many(items, options=None, ctx=None):
+    """encode_aea_pcm for many items in one device call: items is a list of [L] or [L, R]; options.title may be one string
+    or one per item.  Every result is byte for byte what encode_aea_pcm returns for that item alone."""
+    options = dict(options or {})
+    title = options.pop('title', 'encoded by carta1')
+    titles = [title] * len(items) if isinstance(title, str) else list(title)
+    if len(titles) != len(items):
+        raise ValueError('title must be one string or one per item')
+    signals, counts = items_to_signals(items)
+    units = _ctx(ctx).encode_signals(signals, EncoderOptions(options))
+    return [aea_header(t, u.shape[0], nch) + u.tobytes() for t, u, nch in zip(titles, interleave_item_units(units, counts), counts)]
+
+
+def decode_aea_pcm_many(images, ctx=None):
+    """decode_aea_pcm for many AEA images in one device call -> per image a list of float32 arrays (one per channel)"""
+    parsed = [aea_image_units(d) for d in images]
+    counts = [nch for _, nch in parsed]
+    pcm = _ctx(ctx).decode_signals(deinterleave_item_units([u for u, _ in parsed], counts))
+    out, k = [], 0
+    for nch in counts:
+        out.append(list(pcm[k:k + nch]))
+        k += nch
+    return out
+
+
+def decode_aea_pcm(data, ctx=None):
+    """decodeAeaPcm (processor.js:628-654): bytes / bytearray / ndarray(uint8) -> list of float32 arrays."""
+    units, nch = aea_image_units(data)
     return _ctx(ctx).decode(units, nch)
 
 

@@ -410,8 +410,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts"};
 
 }  // namespace
 
@@ -477,6 +477,14 @@ struct c1_ctx {
   // scratch for host-resident calls
   void *d_io = nullptr;
   size_t d_io_bytes = 0;
+  // the signals entry points: device scratch of one call (index lists, states in flight, rows of units or frame fields) and
+  // the page-locked image the index lists are uploaded from; ev_rows: that upload is through, the image may be rewritten
+  void *d_sig = nullptr;
+  size_t d_sig_bytes = 0;
+  uint32_t *h_rows = nullptr;
+  size_t h_rows_bytes = 0;
+  hipEvent_t ev_rows = nullptr;
+  bool rows_pending = false;
   // streamed host path (pinned buffers): copy streams, two chunk-sized staging sets and their events
   hipStream_t s_up = nullptr, s_down = nullptr;
   void *d_ring = nullptr;
@@ -1131,6 +1139,9 @@ int c1_ctx_destroy(c1_ctx *ctx) {
     if (ctx->ev_end[p]) (void)hipEventDestroy(ctx->ev_end[p]);
   }
   if (ctx->d_io) hipFree(ctx->d_io);
+  if (ctx->d_sig) (void)hipFree(ctx->d_sig);
+  if (ctx->h_rows) (void)hipHostFree(ctx->h_rows);
+  if (ctx->ev_rows) (void)hipEventDestroy(ctx->ev_rows);
   if (ctx->d_ring) (void)hipFree(ctx->d_ring);
   if (ctx->s_up) (void)hipStreamDestroy(ctx->s_up);
   if (ctx->s_down) (void)hipStreamDestroy(ctx->s_down);
@@ -3233,6 +3244,365 @@ int c1_decode_frames_from_states(c1_ctx *ctx, int64_t n, const uint8_t *units, c
   HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_dec_state), hipMemcpyHostToDevice, ctx->stream));
   if ((rc = decode_from_states_impl(ctx, n, du, dst, dp, out ? dst : nullptr))) return rc;
   HIP_TRY(hipMemcpyAsync(pcm, dp, N * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_dec_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// ---- n signals of any lengths from their own pools in one call ---------------------------------------------
+namespace {
+constexpr int64_t kMaxSignals = (int64_t)1 << 20;
+constexpr int64_t kMaxSignalFrames = (int64_t)1 << 27, kMaxSignalFramesHost = (int64_t)1 << 22;
+constexpr int kUnitDwords = C1_UNIT_BYTES / 4;
+static_assert(C1_UNIT_BYTES % 4 == 0, "sound units move as dwords");
+
+int check_frame_offsets(const char *what, int64_t n, const int64_t *off, int64_t max_total, int64_t *total) {
+  if (n < 0 || n > kMaxSignals) return fail(C1_ERR_ARG, "%s: n must be 0 .. 2^20, got %lld", what, (long long)n);
+  if (!off) return fail(C1_ERR_ARG, "%s: frame_offsets is NULL", what);
+  if (off[0] != 0) return fail(C1_ERR_ARG, "%s: frame_offsets must start at 0, got %lld", what, (long long)off[0]);
+  for (int64_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return fail(C1_ERR_ARG, "%s: frame_offsets decreases at signal %lld (%lld after %lld)", what, (long long)i, (long long)off[i + 1], (long long)off[i]);
+  if (off[n] > max_total) return fail(C1_ERR_ARG, "%s: %lld frames in all, at most %lld per call", what, (long long)off[n], (long long)max_total);
+  *total = off[n];
+  return C1_OK;
+}
+
+struct TimingScope {         // one profiled call around several *_device calls: they keep the timings (c1_ctx::timing_depth)
+  c1_ctx *ctx;
+  explicit TimingScope(c1_ctx *c) : ctx(c) {
+    if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+    ctx->timing_depth++;
+  }
+  ~TimingScope() { ctx->timing_depth--; }
+};
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// device scratch of a signals call, carved from one allocation that lives with the context
+struct SigCarve {
+  size_t bytes = 0;
+  size_t take(size_t b) { const size_t at = bytes; bytes += align256(b); return at; }
+};
+int ensure_sig(c1_ctx *ctx, size_t bytes) {
+  if (bytes <= ctx->d_sig_bytes) return C1_OK;
+  if (ctx->d_sig) (void)hipFree(ctx->d_sig);               // waits for the device: nothing queued still reads it
+  ctx->d_sig = nullptr; ctx->d_sig_bytes = 0;
+  HIP_TRY(hipMalloc(&ctx->d_sig, bytes));
+  ctx->d_sig_bytes = bytes;
+  return C1_OK;
+}
+// the page-locked image of the index lists, free to be rewritten: the previous call's upload has left it
+int rows_image(c1_ctx *ctx, size_t words, uint32_t **out) {
+  if (ctx->rows_pending) { HIP_TRY(hipEventSynchronize(ctx->ev_rows)); ctx->rows_pending = false; }
+  if (!ctx->ev_rows) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_rows, hipEventDisableTiming));
+  const size_t bytes = std::max<size_t>(words, 1) * sizeof(uint32_t);
+  if (bytes > ctx->h_rows_bytes) {
+    if (ctx->h_rows) (void)hipHostFree(ctx->h_rows);
+    ctx->h_rows = nullptr; ctx->h_rows_bytes = 0;
+    HIP_TRY(hipHostMalloc((void **)&ctx->h_rows, bytes, hipHostMallocDefault));
+    ctx->h_rows_bytes = bytes;
+  }
+  *out = ctx->h_rows;
+  return C1_OK;
+}
+int upload_rows(c1_ctx *ctx, uint32_t *dst, size_t words) {
+  if (!words) return C1_OK;
+  HIP_TRY(hipMemcpyAsync(dst, ctx->h_rows, words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev_rows, ctx->stream));
+  ctx->rows_pending = true;
+  return C1_OK;
+}
+
+// One fix-up pass of the encoder: `rows` frames, row r the PCM frame src[r] from state in[in_rows[r]] (in_rows null: in[r];
+// bcast: in[0]) to state out[out_rows[r]] (null: out[r]; out null: no state), through the from-state kernel into the
+// workspace, the encoder's own allocation and packing on it, and the units scattered to units[src[r]].  W rows at a time.
+int encode_rows_pass(c1_ctx *ctx, const float *pcm, const uint32_t *src, const float *in, const uint32_t *in_rows, bool bcast,
+                     float *out, const uint32_t *out_rows, int64_t rows, int64_t W, uint8_t *units, uint8_t *row_units) {
+  for (int64_t r0 = 0; r0 < rows; r0 += W) {
+    const int64_t m = std::min(W, rows - r0);
+    C1EncStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.pcm = pcm;
+    K.src_rows = src + r0;
+    K.in = (in_rows || bcast) ? in : in + r0 * kEncStateFloats;
+    K.in_rows = in_rows ? in_rows + r0 : nullptr;
+    K.in_broadcast = bcast ? 1 : 0;
+    K.out = (!out || out_rows) ? out : out + r0 * kEncStateFloats;
+    K.out_rows = out_rows ? out_rows + r0 : nullptr;
+    K.n = m;
+    K.tables = ctx->d_tables;
+    K.opts = ctx->d_opts;
+    K.coefs = ctx->d_coefs[0];
+    K.side = ctx->d_side[0];
+    K.detect = -1;
+    { ScopedTiming t(ctx, K_SIGNAL_STARTS); c1k_launch_encode_rows(K, ctx->stream); }
+    C1EncodeLaunch L;
+    memset(&L, 0, sizeof L);
+    L.channels = 1;
+    L.frames = m;
+    L.tables = ctx->d_tables;
+    L.opts = ctx->d_opts;
+    L.coefs = ctx->d_coefs[0];
+    L.side = ctx->d_side[0];
+    L.alloc = ctx->d_alloc[0];
+    L.cand = ctx->d_cand[0];
+    L.work_count = ctx->d_work[0];
+    L.work_list = ctx->d_work[0] + 4;
+    L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
+    L.units = row_units;
+    { ScopedTiming t(ctx, K_ALLOCATE); c1k_launch_allocate(L, ctx->stream); }
+    { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
+    { ScopedTiming t(ctx, K_SIGNAL_STARTS);
+      c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(units), src + r0, reinterpret_cast<const uint32_t *>(row_units), nullptr, 0, m, kUnitDwords, ctx->stream); }
+  }
+  return C1_OK;
+}
+
+// device pointers but frame_offsets; arguments checked by the callers
+int encode_signals_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const float *pcm, const float *in, const c1_encode_options *opts,
+                        uint8_t *units, float *out) {
+  int rc;
+  TimingScope scope(ctx);
+  const int64_t total = off[n];
+  // 1. the whole concatenation as one mono stream: every unit but those of the first two frames of a signal is final.  The
+  //    call returns with the context's stream waiting for all of its work (tails and internal streams): what follows is ordered
+  const float *chan[1] = {pcm};
+  if ((rc = encode_device_impl(ctx, chan, 1, total, 0, opts, units, nullptr, nullptr, nullptr, nullptr, false))) return rc;
+  int64_t nA = 0, nB = 0, nC = 0, nZ = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t len = off[i + 1] - off[i];
+    nA += len >= 1; nB += len >= 2; nC += len >= 3; nZ += len == 0;
+  }
+  const bool copy_empty = out && out != in && nZ > 0;
+  if (nA == 0 && !copy_empty) return C1_OK;
+  if (!out) nC = 0;
+  // index lists: A = signals of >= 1 frame (frame 0), B = of >= 2 (frame 1), C = of >= 3 (the last two frames), Z = empty ones
+  const size_t words = (size_t)(2 * nA + 3 * nB + 3 * nC + nZ);
+  uint32_t *h;
+  if ((rc = rows_image(ctx, words, &h))) return rc;
+  uint32_t *a_src = h, *a_sig = a_src + nA, *b_src = a_sig + nA, *b_sig = b_src + nB, *b_row = b_sig + nB, *c_src0 = b_row + nB,
+           *c_src1 = c_src0 + nC, *c_sig = c_src1 + nC, *z_sig = c_sig + nC;
+  {
+    int64_t a = 0, b = 0, c = 0, z = 0;
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t f0 = off[i], len = off[i + 1] - f0;
+      if (len == 0) { z_sig[z++] = (uint32_t)i; continue; }
+      if (len >= 2) { b_src[b] = (uint32_t)(f0 + 1); b_sig[b] = (uint32_t)i; b_row[b] = (uint32_t)a; b++; }
+      if (len >= 3 && out) { c_src0[c] = (uint32_t)(f0 + len - 2); c_src1[c] = (uint32_t)(f0 + len - 1); c_sig[c] = (uint32_t)i; c++; }
+      a_src[a] = (uint32_t)f0; a_sig[a] = (uint32_t)i; a++;
+    }
+  }
+  int64_t W = 0;
+  if (nA > 0) {
+    if ((rc = join_tail(ctx))) return rc;
+    W = std::min(nA, chunk_for_call(ctx, nA, 1, false));
+    if ((rc = ensure_workspace(ctx, W))) return rc;
+  }
+  SigCarve cv;
+  const size_t o_zero = cv.take(sizeof(c1_enc_state)), o_lists = cv.take(words * sizeof(uint32_t)),
+               o_tmp = cv.take(out ? 0 : (size_t)nA * sizeof(c1_enc_state)), o_tmp2 = cv.take((size_t)nC * sizeof(c1_enc_state)),
+               o_units = cv.take((size_t)W * C1_UNIT_BYTES);
+  if ((rc = ensure_sig(ctx, cv.bytes))) return rc;
+  uint8_t *base = static_cast<uint8_t *>(ctx->d_sig);
+  float *zero = reinterpret_cast<float *>(base + o_zero), *tmp = reinterpret_cast<float *>(base + o_tmp), *tmp2 = reinterpret_cast<float *>(base + o_tmp2);
+  uint32_t *d = reinterpret_cast<uint32_t *>(base + o_lists);
+  const uint32_t *da_src = d, *da_sig = da_src + nA, *db_src = da_sig + nA, *db_sig = db_src + nB, *db_row = db_sig + nB, *dc_src0 = db_row + nB,
+                 *dc_src1 = dc_src0 + nC, *dc_sig = dc_src1 + nC, *dz_sig = dc_sig + nC;
+  HIP_TRY(hipMemsetAsync(zero, 0, sizeof(c1_enc_state), ctx->stream));
+  if ((rc = upload_rows(ctx, d, words))) return rc;
+  // the pools in flight live in `out` at their signal's index, or in scratch at their row of list A when out is NULL
+  float *S = out ? out : tmp;
+  // 2. frame 0 of every signal from in[i] (a fresh pool when in is NULL)
+  if ((rc = encode_rows_pass(ctx, pcm, da_src, in ? in : zero, in ? da_sig : nullptr, !in, (out || nB) ? S : nullptr, out ? da_sig : nullptr,
+                             nA, W, units, base + o_units))) return rc;
+  // 3. frame 1 from the pool step 2 left, in place
+  if ((rc = encode_rows_pass(ctx, pcm, db_src, S, out ? db_sig : db_row, false, S, out ? db_sig : db_row, nB, W, units, base + o_units))) return rc;
+  if (out) {
+    // 4. signals of three frames and more: the pool after the last frame is a function of the last two frames (state only, from
+    //    zeros: c1_enc_stream_get_state does the same); under fixed modes transient_mags keeps what steps 2 and 3 passed through
+    const bool detect = opts->fixed_block_modes[0] < 0;
+    C1EncStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.pcm = pcm;
+    K.src_rows = dc_src0;
+    K.in = zero;
+    K.in_broadcast = 1;
+    K.out = tmp2;
+    K.n = nC;
+    K.tables = ctx->d_tables;
+    K.opts = ctx->d_opts;
+    K.state_only = 1;
+    K.detect = 0;                                          // the zero pool's magnitudes pass through: every float of tmp2 is written
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    c1k_launch_encode_rows(K, ctx->stream);
+    K.src_rows = dc_src1;
+    K.in = tmp2;
+    K.in_broadcast = 0;
+    K.out = out;
+    K.out_rows = dc_sig;
+    K.detect = detect ? 1 : 0;
+    K.keep_mags = detect ? 0 : 1;
+    c1k_launch_encode_rows(K, ctx->stream);
+    // empty signals: the pool passes through
+    if (copy_empty)
+      c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(out), dz_sig, reinterpret_cast<const uint32_t *>(in ? in : zero), in ? dz_sig : nullptr,
+                           in ? 0 : 1, nZ, kEncStateFloats, ctx->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
+int decode_signals_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const uint8_t *units, const float *in, float *pcm, float *out) {
+  int rc;
+  TimingScope scope(ctx);
+  const int64_t total = off[n];
+  // 1. the concatenation as one mono stream: every frame but the first of a signal is final
+  float *chan[1] = {pcm};
+  if ((rc = c1_decode_device(ctx, units, 1, total, 0, chan))) return rc;
+  int64_t nA = 0, nZ = 0;
+  for (int64_t i = 0; i < n; i++) { nA += off[i + 1] > off[i]; nZ += off[i + 1] == off[i]; }
+  const bool copy_empty = out && out != in && nZ > 0;
+  if (nA == 0 && !copy_empty) return C1_OK;
+  const size_t words = (size_t)(3 * nA + nZ);
+  uint32_t *h;
+  if ((rc = rows_image(ctx, words, &h))) return rc;
+  uint32_t *a_first = h, *a_last = a_first + nA, *a_sig = a_last + nA, *z_sig = a_sig + nA;
+  {
+    int64_t a = 0, z = 0;
+    for (int64_t i = 0; i < n; i++) {
+      if (off[i + 1] == off[i]) { z_sig[z++] = (uint32_t)i; continue; }
+      a_first[a] = (uint32_t)off[i]; a_last[a] = (uint32_t)(off[i + 1] - 1); a_sig[a] = (uint32_t)i; a++;
+    }
+  }
+  const int64_t W = std::min(nA, kStateDecodeChunk / 2), per = out ? 2 : 1;       // rows per pass: first units, then last units
+  SigCarve cv;
+  const size_t o_zero = cv.take(sizeof(c1_dec_state)), o_lists = cv.take(words * sizeof(uint32_t)),
+               o_units = cv.take((size_t)(per * W) * C1_UNIT_BYTES), o_fields = cv.take((size_t)(per * W * kFieldInts) * sizeof(int32_t));
+  if ((rc = ensure_sig(ctx, cv.bytes))) return rc;
+  uint8_t *base = static_cast<uint8_t *>(ctx->d_sig);
+  float *zero = reinterpret_cast<float *>(base + o_zero);
+  uint32_t *d = reinterpret_cast<uint32_t *>(base + o_lists);
+  const uint32_t *da_first = d, *da_last = da_first + nA, *da_sig = da_last + nA, *dz_sig = da_sig + nA;
+  uint32_t *g = reinterpret_cast<uint32_t *>(base + o_units);
+  HIP_TRY(hipMemsetAsync(zero, 0, sizeof(c1_dec_state), ctx->stream));
+  if ((rc = upload_rows(ctx, d, words))) return rc;
+  const uint32_t *u32 = reinterpret_cast<const uint32_t *>(units);
+  for (int64_t r0 = 0; r0 < nA; r0 += W) {
+    const int64_t m = std::min(W, nA - r0);
+    const C1FieldPtrs f = field_layout(reinterpret_cast<int32_t *>(base + o_fields), per * m);
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    c1k_launch_copy_rows(g, nullptr, u32, da_first + r0, 0, m, kUnitDwords, ctx->stream);
+    if (out) c1k_launch_copy_rows(g + m * kUnitDwords, nullptr, u32, da_last + r0, 0, m, kUnitDwords, ctx->stream);
+    c1k_launch_unpack_units(reinterpret_cast<const uint8_t *>(g), per * m, (int32_t *)f.nbfu, (int32_t *)f.modes, (int32_t *)f.sfi, (int32_t *)f.wl,
+                            (int32_t *)f.q, ctx->stream);
+    // 2. the first frame of every signal from in[i], straight to its place
+    C1DecStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.fields = f;
+    K.in = in ? in : zero;
+    K.in_rows = in ? da_sig + r0 : nullptr;
+    K.in_broadcast = in ? 0 : 1;
+    K.pcm = pcm;
+    K.dst_rows = da_first + r0;
+    K.n = m;
+    K.tables = ctx->d_tables;
+    c1k_launch_decode_rows(K, ctx->stream);
+    if (out) {
+      // 3. the pool after a signal is a function of its last unit alone: state only, from zeros (c1_dec_stream_get_state)
+      K.fields = field_unit(f, m);
+      K.in = zero;
+      K.in_rows = nullptr;
+      K.in_broadcast = 1;
+      K.pcm = nullptr;
+      K.dst_rows = nullptr;
+      K.out = out;
+      K.out_rows = da_sig + r0;
+      c1k_launch_decode_rows(K, ctx->stream);
+    }
+  }
+  if (copy_empty) {
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(out), dz_sig, reinterpret_cast<const uint32_t *>(in ? in : zero), in ? dz_sig : nullptr,
+                         in ? 0 : 1, nZ, kDecStateFloats, ctx->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+}  // namespace
+
+int c1_encode_signals_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                             const c1_encode_options *opts, uint8_t *units, c1_enc_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets("encode signals", n, frame_offsets, kMaxSignalFrames, &total))) return rc;
+  if (!opts) return fail(C1_ERR_ARG, "encode signals: options are NULL");
+  if (total > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "encode signals: %s is NULL", !pcm ? "pcm" : "units");
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "encode signals: pcm must be 16-byte aligned on the device");
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)units) & 3) return fail(C1_ERR_ARG, "encode signals: units and states must be 4-byte aligned on the device");
+  return encode_signals_impl(ctx, n, frame_offsets, pcm, reinterpret_cast<const float *>(in), opts, units, reinterpret_cast<float *>(out));
+}
+
+int c1_decode_signals_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const uint8_t *units, const c1_dec_state *in, float *pcm,
+                             c1_dec_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets("decode signals", n, frame_offsets, kMaxSignalFrames, &total))) return rc;
+  if (total > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "decode signals: %s is NULL", !pcm ? "pcm" : "units");
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "decode signals: pcm must be 16-byte aligned on the device");
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)units) & 3) return fail(C1_ERR_ARG, "decode signals: units and states must be 4-byte aligned on the device");
+  return decode_signals_impl(ctx, n, frame_offsets, units, reinterpret_cast<const float *>(in), pcm, reinterpret_cast<float *>(out));
+}
+
+int c1_encode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                      const c1_encode_options *opts, uint8_t *units, c1_enc_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets("encode signals", n, frame_offsets, kMaxSignalFramesHost, &total))) return rc;
+  if (!opts) return fail(C1_ERR_ARG, "encode signals: options are NULL");
+  if (total > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "encode signals: %s is NULL", !pcm ? "pcm" : "units");
+  C1DevEncOpts probe;
+  if ((rc = build_encode_opts(*opts, &probe))) return rc;
+  if (in && (rc = check_states_finite("encode signals", "signal", in, n, kEncStateFloats, kEncStateFields, 5))) return rc;
+  if (n == 0) return C1_OK;
+  DeviceScratch ds;
+  float *dp, *dst = nullptr; uint8_t *du;
+  const size_t T = (size_t)total, N = (size_t)n;
+  if ((rc = ds.alloc(&dp, T * 512)) || (rc = ds.alloc(&du, T * C1_UNIT_BYTES))) return rc;
+  if ((in || out) && (rc = ds.alloc(&dst, N * kEncStateFloats))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(dp, pcm, T * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_enc_state), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = encode_signals_impl(ctx, n, frame_offsets, dp, in ? dst : nullptr, opts, du, out ? dst : nullptr))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(units, du, T * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_decode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const uint8_t *units, const c1_dec_state *in, float *pcm,
+                      c1_dec_state *out) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets("decode signals", n, frame_offsets, kMaxSignalFramesHost, &total))) return rc;
+  if (total > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "decode signals: %s is NULL", !pcm ? "pcm" : "units");
+  if (in && (rc = check_states_finite("decode signals", "signal", in, n, kDecStateFloats, kDecStateFields, 4))) return rc;
+  if (n == 0) return C1_OK;
+  DeviceScratch ds;
+  float *dp, *dst = nullptr; uint8_t *du;
+  const size_t T = (size_t)total, N = (size_t)n;
+  if ((rc = ds.alloc(&dp, T * 512)) || (rc = ds.alloc(&du, T * C1_UNIT_BYTES))) return rc;
+  if ((in || out) && (rc = ds.alloc(&dst, N * kDecStateFloats))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(du, units, T * C1_UNIT_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_dec_state), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = decode_signals_impl(ctx, n, frame_offsets, du, in ? dst : nullptr, dp, out ? dst : nullptr))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(pcm, dp, T * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_dec_state), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;

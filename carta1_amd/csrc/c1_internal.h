@@ -185,6 +185,12 @@ struct C1EncStateLaunch {
   uint8_t *side;
   int detect;            // -1: as opts say; 0: transient_mags pass through; 1: the frame's magnitudes are written
   int state_only;        // no coefficients, no side records, no block decision: only the state after the frame
+  // row-indexed form (c1k_launch_encode_rows; the signals entry points): row r reads the PCM frame at pcm + src_rows[r] * 512
+  // and the state in[in_rows[r]], and writes the state out[out_rows[r]]; coefficients and side records stay at row r.  A null
+  // list is the identity; in_broadcast: every row reads in[0] (a fresh pool).  keep_mags: transient_mags of `out` is left as
+  // it is (a state rebuilt from zeros under fixed block modes keeps what the pool held)
+  const uint32_t *src_rows, *in_rows, *out_rows;
+  int in_broadcast, keep_mags;
 };
 // decode twin: pool i decodes the frame fields of unit i (layout of c1_unpack_units) from in[i] (c1_dec_state, 179 floats)
 // into pcm + i * pcm_stride (null: state only) and leaves its pool in out[i]; out may be in, or null
@@ -196,6 +202,10 @@ struct C1DecStateLaunch {
   int64_t pcm_stride;
   int64_t n;
   const C1DevTables *tables;
+  // row-indexed form (c1k_launch_decode_rows): row r decodes the fields of unit r from in[in_rows[r]] into the PCM frame at
+  // pcm + dst_rows[r] * 512 and writes the state out[out_rows[r]]; null lists and in_broadcast as in C1EncStateLaunch
+  const uint32_t *dst_rows, *in_rows, *out_rows;
+  int in_broadcast;
 };
 
 // Run length of the frame-walking kernels: consecutive frames of one channel a wave walks, carrying the filter state
@@ -312,6 +322,14 @@ void c1k_launch_decode_fields(const C1DecodeFieldsLaunch &L, hipStream_t stream)
 // the frame closures over explicit pool state (c1_k_state.hip); n <= 0 launches nothing
 void c1k_launch_encode_from_states(const C1EncStateLaunch &L, hipStream_t stream);
 void c1k_launch_decode_from_states(const C1DecStateLaunch &L, hipStream_t stream);
+// the same closures over index lists (C1EncStateLaunch / C1DecStateLaunch, row-indexed form)
+void c1k_launch_encode_rows(const C1EncStateLaunch &L, hipStream_t stream);
+void c1k_launch_decode_rows(const C1DecStateLaunch &L, hipStream_t stream);
+// rows of `dwords` 32-bit words each: dst[dst_rows[r]] = src[src_rows[r]] for r < n, a lane per dword (sound units are 53
+// dwords, states 483 / 179: multiples of 4 bytes, not of 16).  A null list is the identity; src_broadcast: every row copies
+// src row 0.  Rows of one launch must not overlap each other
+void c1k_launch_copy_rows(uint32_t *dst, const uint32_t *dst_rows, const uint32_t *src, const uint32_t *src_rows, int src_broadcast,
+                          int64_t n, int dwords, hipStream_t stream);
 // performFFT's magnitudes of `rows` stored band rows (512 floats each) into the transient_mags of states[0 .. rows)
 void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_t rows, float *states, hipStream_t stream);
 // kind_mask: bit k = fill the 512-frame segments with (segment & 3) == k (15 = all)

@@ -87,6 +87,9 @@ __device__ __forceinline__ void mix_stage_rt(const float *band_, const float *ov
   }
 }
 
+// kRows: the row-indexed form (C1EncStateLaunch's index lists: the signals entry points).  The lists are wave-uniform: scalar
+// loads, no vector register of the frame body is spent on them
+template <bool kRows>
 __global__ __launch_bounds__(C1_WAVE, 3) void k_encode_from_state(C1EncStateLaunch L) {
   __shared__ EncStateLds S;
   const int lane0 = threadIdx.x;
@@ -98,9 +101,15 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_encode_from_state(C1EncStateLaun
     TablesPtr T = tables_for_this_frame(L.tables);
     const int lane = lane_for_this_frame(lane0);
     // `in` and `out` may be the same array: everything of the pool's state is read here, before anything is written
-    const float *in = L.in + pool * kEsFloats;
+    int64_t in_row = pool, src_off = pool * L.pcm_stride, out_row = pool;
+    if constexpr (kRows) {
+      in_row = L.in_broadcast ? 0 : (L.in_rows ? (int64_t)L.in_rows[pool] : pool);
+      src_off = (L.src_rows ? (int64_t)L.src_rows[pool] : pool) << 9;
+      out_row = L.out_rows ? (int64_t)L.out_rows[pool] : pool;
+    }
+    const float *in = L.in + in_row * kEsFloats;
     typedef float v4f __attribute__((ext_vector_type(4)));
-    const v4f *p4 = reinterpret_cast<const v4f *>(L.pcm + pool * L.pcm_stride);
+    const v4f *p4 = reinterpret_cast<const v4f *>(L.pcm + src_off);
     const v4f a = p4[lane], b = p4[64 + lane];
     const float s_low = in[kEsLow + (lane < 46 ? lane : 45)], s_mid = in[kEsMid + (lane < 46 ? lane : 45)];
     const float s_high = in[kEsHigh + (lane < 39 ? lane : 38)];
@@ -213,13 +222,15 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_encode_from_state(C1EncStateLaun
 
     // ---------------- the pool after the frame ----------------
     if (L.out) {
-      float *out = L.out + pool * kEsFloats;
+      float *out = L.out + out_row * kEsFloats;
       if (lane < 46) { out[kEsLow + lane] = nd1; out[kEsMid + lane] = nd2; }
       if (lane < 39) out[kEsHigh + lane] = S.high[lane];
       out[kEsOverlap + lane] = S.ovl[lane];
       if (lane < 32) out[kEsOverlap + 64 + lane] = S.ovl[64 + lane];
+      if (!kRows || !L.keep_mags) {
 #pragma unroll
-      for (int k = 0; k < 4; k++) out[kEsMags + mag0 + k * magS] = mg[k];
+        for (int k = 0; k < 4; k++) out[kEsMags + mag0 + k * magS] = mg[k];
+      }
     }
     wave_fence();
   }
@@ -274,6 +285,7 @@ __device__ __forceinline__ PoolFields load_pool_fields(const C1FieldPtrs &P, int
 }
 
 // the LDS image is k_decode_fields' own (DecodeLds<double>): the same stages run on it
+template <bool kRows>
 __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaunch L) {
   __shared__ DecodeLds<double> S;
   const int lane0 = threadIdx.x;
@@ -285,7 +297,13 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaun
     TablesPtr T = tables_for_this_frame(L.tables);
     const int lane = lane_for_this_frame(lane0);
     // `in` and `out` may be the same array: the pool's state is read here, before anything is written
-    const float *in = L.in + pool * kDsFloats;
+    int64_t in_row = pool, dst_off = pool * L.pcm_stride, out_row = pool;
+    if constexpr (kRows) {
+      in_row = L.in_broadcast ? 0 : (L.in_rows ? (int64_t)L.in_rows[pool] : pool);
+      dst_off = (L.dst_rows ? (int64_t)L.dst_rows[pool] : pool) << 9;
+      out_row = L.out_rows ? (int64_t)L.out_rows[pool] : pool;
+    }
+    const float *in = L.in + in_row * kDsFloats;
     const PoolFields F = load_pool_fields(L.fields, pool, lane);
     const float s_low = in[kDsLow + (lane < 46 ? lane : 45)], s_mid = in[kDsMid + (lane < 46 ? lane : 45)];
     const float s_high = in[kDsHigh + (lane < 39 ? lane : 38)], s_tail = in[kDsTail + (lane < 48 ? lane : 47)];
@@ -331,17 +349,31 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaun
     qmf_synthesis_frame<double>(S, lane, T, s0, s1);
     wave_fence();
     if (L.pcm) {
-      float4 *dst = reinterpret_cast<float4 *>(L.pcm + pool * L.pcm_stride + 8 * lane);
+      float4 *dst = reinterpret_cast<float4 *>(L.pcm + dst_off + 8 * lane);
       dst[0] = make_float4((float)s1[0], (float)s0[0], (float)s1[1], (float)s0[1]);
       dst[1] = make_float4((float)s1[2], (float)s0[2], (float)s1[3], (float)s0[3]);
     }
     if (L.out) {
-      float *out = L.out + pool * kDsFloats;
+      float *out = L.out + out_row * kDsFloats;
       if (lane < 46) { out[kDsLow + lane] = (float)S.d1[lane]; out[kDsMid + lane] = (float)S.d2[lane]; }
       if (lane < 39) out[kDsHigh + lane] = S.dhi[lane];
       if (lane < 48) out[kDsTail + lane] = S.tail[lane];
     }
     wave_fence();
+  }
+}
+
+// dst[dst_rows[r]] = src[src_rows[r]], rows of `dwords` 32-bit words: a lane per dword, a wave per row and pass of the grid.
+// Every row's source is read by the lanes that write it, within one pass: rows that are their own source (in place) are safe
+__global__ __launch_bounds__(C1_WAVE) void k_copy_rows(uint32_t *__restrict__ dst, const uint32_t *__restrict__ dst_rows,
+                                                      const uint32_t *__restrict__ src, const uint32_t *__restrict__ src_rows,
+                                                      int src_broadcast, int64_t n, int dwords) {
+  const int lane = threadIdx.x;
+  for (int64_t r = blockIdx.x; r < n; r += gridDim.x) {
+    const int64_t sr = src_broadcast ? 0 : (src_rows ? (int64_t)src_rows[r] : r), dr = dst_rows ? (int64_t)dst_rows[r] : r;
+    const uint32_t *s = src + sr * dwords;
+    uint32_t *d = dst + dr * dwords;
+    for (int k = lane; k < dwords; k += C1_WAVE) d[k] = s[k];
   }
 }
 
@@ -352,7 +384,7 @@ unsigned state_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 256 * 12)
 
 void c1k_launch_encode_from_states(const C1EncStateLaunch &L, hipStream_t stream) {
   if (L.n <= 0) return;
-  hipLaunchKernelGGL(k_encode_from_state, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  hipLaunchKernelGGL(k_encode_from_state<false>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
 }
 void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_t rows, float *states, hipStream_t stream) {
   if (rows <= 0) return;
@@ -360,5 +392,18 @@ void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_
 }
 void c1k_launch_decode_from_states(const C1DecStateLaunch &L, hipStream_t stream) {
   if (L.n <= 0) return;
-  hipLaunchKernelGGL(k_decode_from_state, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  hipLaunchKernelGGL(k_decode_from_state<false>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+}
+void c1k_launch_encode_rows(const C1EncStateLaunch &L, hipStream_t stream) {
+  if (L.n <= 0) return;
+  hipLaunchKernelGGL(k_encode_from_state<true>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+}
+void c1k_launch_decode_rows(const C1DecStateLaunch &L, hipStream_t stream) {
+  if (L.n <= 0) return;
+  hipLaunchKernelGGL(k_decode_from_state<true>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+}
+void c1k_launch_copy_rows(uint32_t *dst, const uint32_t *dst_rows, const uint32_t *src, const uint32_t *src_rows, int src_broadcast,
+                          int64_t n, int dwords, hipStream_t stream) {
+  if (n <= 0 || dwords <= 0) return;
+  hipLaunchKernelGGL(k_copy_rows, dim3(state_grid(n)), dim3(C1_WAVE), 0, stream, dst, dst_rows, src, src_rows, src_broadcast, n, dwords);
 }

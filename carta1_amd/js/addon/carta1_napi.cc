@@ -255,6 +255,60 @@ napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+// n independent mono signals from fresh pools in one call (c1_encode_signals / c1_decode_signals).  frameOffsets: Float64Array of
+// n + 1 whole numbers, signal i owns frames [frameOffsets[i], frameOffsets[i + 1]) of the concatenated PCM / units.
+bool get_frame_offsets(napi_env env, napi_value v, std::vector<int64_t> *off) {
+  void *d;
+  size_t n;
+  if (!get_typed(env, v, napi_float64_array, &d, &n)) return false;
+  if (n < 1) { napi_throw_type_error(env, nullptr, "frameOffsets must hold n + 1 entries"); return false; }
+  const double *p = static_cast<const double *>(d);
+  for (size_t i = 0; i < n; i++) {
+    if (!(p[i] >= 0 && p[i] <= 4503599627370496.0) || p[i] != (double)(int64_t)p[i]) {
+      napi_throw_type_error(env, nullptr, "frameOffsets must be whole numbers >= 0");
+      return false;
+    }
+    off->push_back((int64_t)p[i]);
+  }
+  return true;
+}
+// encodeSignals(ctx, Float32Array pcm, Float64Array frameOffsets, options) -> Uint8Array(frames * 212)
+napi_value EncodeSignals(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_ctx *ctx;
+  void *d;
+  size_t samples;
+  std::vector<int64_t> off;
+  c1_encode_options o;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &samples) ||
+      !get_frame_offsets(env, argv[2], &off) || !get_options(env, argv[3], &o)) return nullptr;
+  if (samples % 512 || (uint64_t)off.back() != samples / 512) { napi_throw_type_error(env, nullptr, "pcm must hold frameOffsets[n] frames of 512 samples"); return nullptr; }
+  uint8_t *units;
+  napi_value out = make_u8(env, (samples / 512) * C1_UNIT_BYTES, &units);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_encode_signals(ctx, (int64_t)off.size() - 1, off.data(), static_cast<const float *>(d), nullptr, &o, units, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+// decodeSignals(ctx, Uint8Array units, Float64Array frameOffsets) -> Float32Array(frames * 512)
+napi_value DecodeSignals(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  c1_ctx *ctx;
+  void *d;
+  size_t bytes;
+  std::vector<int64_t> off;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_uint8_array, &d, &bytes) || !get_frame_offsets(env, argv[2], &off)) return nullptr;
+  if (bytes % C1_UNIT_BYTES || (uint64_t)off.back() != bytes / C1_UNIT_BYTES) { napi_throw_type_error(env, nullptr, "units must hold frameOffsets[n] units of 212 bytes"); return nullptr; }
+  float *pcm;
+  napi_value out = make_f32(env, (bytes / C1_UNIT_BYTES) * 512, &pcm);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_decode_signals(ctx, (int64_t)off.size() - 1, off.data(), static_cast<const uint8_t *>(d), nullptr, pcm, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+
 // encodeWavBatch(ctx, Int16Array | Uint8Array wavBody, bits, channels, options) -> Uint8Array units
 // (c1_encode_wav_batch: interleaved little-endian integer PCM converted on the device, ragged tail zero padded)
 napi_value EncodeWavBatch(napi_env env, napi_callback_info info) {
@@ -977,6 +1031,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatchAsync", nullptr, EncodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatchAsync", nullptr, DecodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeSignals", nullptr, EncodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"decodeSignals", nullptr, DecodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},

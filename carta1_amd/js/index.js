@@ -4,7 +4,7 @@
 export { encode, qmfAnalysisStage, mdctStage } from './pipeline/encoder.js'
 export { decode } from './pipeline/decoder.js'
 export { serializeFrame, deserializeFrame, AeaFile } from './io/serialization.js'
-export { AudioProcessor, encodeAeaPcm, decodeAeaPcm, encodeWavPcm, decodeAeaToWav16 } from './io/processor.js'
+export { AudioProcessor, encodeAeaPcm, decodeAeaPcm, encodeAeaPcmMany, decodeAeaPcmMany, encodeWavPcm, decodeAeaToWav16 } from './io/processor.js'
 export { quantize, dequantize } from './coding/quantization.js'
 export { FFT } from './transforms/fft.js'
 export { BufferPool } from './core/buffers.js'

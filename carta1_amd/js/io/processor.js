@@ -1,10 +1,10 @@
 // AudioProcessor + encodeAeaPcm / decodeAeaPcm: the stream/file level API of the reference
 // (codec/io/processor.js:37-671), with the per-frame hot loop (processor.js:119-136, :193-237)
-// replaced by ONE batched native call per buffer.  WAV blob helpers are outside the hot-path scope
-// (SURVEY.md section 8f) and are not provided.
+// replaced by ONE batched native call per buffer; encodeAeaPcmMany / decodeAeaPcmMany do that for many buffers at once.
+// The WAV helpers createWavBlob and assemblePcmFrames are host code with the reference's call shapes.
 import { EncoderOptions } from '../core/options.js'
 import { BufferPool } from '../core/buffers.js'
-import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE } from '../core/constants.js'
+import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from '../core/constants.js'
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
@@ -25,10 +25,7 @@ function padChannels(channels) {
 }
 
 export async function encodeAeaPcm(channels, options = {}) {
-  if (!Array.isArray(channels) || (channels.length !== 1 && channels.length !== 2) ||
-      channels.some((channel) => !(channel instanceof Float32Array))) {
-    throw new TypeError('ATRAC1 encoding requires one or two Float32 channels')
-  }
+  checkChannels(channels)
   // options.devices (not in the reference): device indices to shard the frame batch over, e.g. [0, 1, 2, 3]; contiguous
   // frame ranges, one context and host thread per entry, no collective -- same bytes as one device
   const { title = 'encoded by carta1', devices, ...encoderValues } = options
@@ -65,6 +62,125 @@ export async function decodeAeaPcm(input, options = {}) {
   if (body.length === 0) return nch === 1 ? [new Float32Array(0)] : [new Float32Array(0), new Float32Array(0)]
   const where = Array.isArray(options.devices) && options.devices.length ? options.devices : context()
   return native().decodeBatchAsync(where, body, nch, 0)
+}
+
+function checkChannels(channels) {
+  if (!Array.isArray(channels) || (channels.length !== 1 && channels.length !== 2) ||
+      channels.some((channel) => !(channel instanceof Float32Array))) {
+    throw new TypeError('ATRAC1 encoding requires one or two Float32 channels')
+  }
+}
+
+// ---- many items in one native call: the host part (layout only) ----
+// items, each [L] or [L, R] -> one padded mono signal per channel in item order, the frame offsets of the concatenation
+// (Float64Array, n + 1 entries) and the channel count of every item
+export function itemsToSignals(items) {
+  if (!Array.isArray(items)) throw new TypeError('items must be an array of [L] or [L, R]')
+  const signals = []
+  const counts = []
+  for (const channels of items) {
+    checkChannels(channels)
+    signals.push(...padChannels(channels).padded)
+    counts.push(channels.length)
+  }
+  const frameOffsets = new Float64Array(signals.length + 1)
+  signals.forEach((s, i) => { frameOffsets[i + 1] = frameOffsets[i] + s.length / SAMPLES_PER_FRAME })
+  return { signals, counts, frameOffsets }
+}
+
+function concatSignals(signals, frameOffsets) {
+  const pcm = new Float32Array(frameOffsets[signals.length] * SAMPLES_PER_FRAME)
+  signals.forEach((s, i) => pcm.set(s, frameOffsets[i] * SAMPLES_PER_FRAME))
+  return pcm
+}
+
+// the units of item k's channels (signal-major in `units`) -> one AEA body, interleaved L, R
+export function interleaveItemUnits(units, frameOffsets, first, channelCount) {
+  const frames = frameOffsets[first + 1] - frameOffsets[first]
+  const body = new Uint8Array(frames * channelCount * SOUND_UNIT_SIZE)
+  for (let c = 0; c < channelCount; c++) {
+    const from = frameOffsets[first + c] * SOUND_UNIT_SIZE
+    for (let f = 0; f < frames; f++) {
+      body.set(units.subarray(from + f * SOUND_UNIT_SIZE, from + (f + 1) * SOUND_UNIT_SIZE), (f * channelCount + c) * SOUND_UNIT_SIZE)
+    }
+  }
+  return body
+}
+
+// the inverse for one item: an AEA body interleaved L, R -> one run of units per channel, written into `units` from unit `at`
+export function deinterleaveItemUnits(body, channelCount, units, at) {
+  const frames = body.length / SOUND_UNIT_SIZE / channelCount
+  for (let c = 0; c < channelCount; c++) {
+    for (let f = 0; f < frames; f++) {
+      const from = (f * channelCount + c) * SOUND_UNIT_SIZE
+      units.set(body.subarray(from, from + SOUND_UNIT_SIZE), (at + c * frames + f) * SOUND_UNIT_SIZE)
+    }
+  }
+  return frames
+}
+
+// one AEA image -> { nch, body }: whole units only, a lone trailing left unit paired with the dummy right unit
+function imageBody(input) {
+  if (!(input instanceof Uint8Array) && !(input instanceof ArrayBuffer)) throw new TypeError('ATRAC1 decoding requires AEA bytes')
+  const { info, units } = AudioProcessor.parseAea(input instanceof Uint8Array ? input : new Uint8Array(input))
+  const nch = info.channelCount
+  if (nch !== 1 && nch !== 2) throw new Error(`Unsupported channel count: ${nch}`)
+  if (nch === 2 && (units.length / SOUND_UNIT_SIZE) % 2 === 1) {
+    const body = new Uint8Array(units.length + SOUND_UNIT_SIZE)
+    body.set(units)
+    body[units.length] = 0xac
+    return { nch, body }
+  }
+  return { nch, body: units }
+}
+
+// encodeAeaPcm for many items at once: every channel of every item is one signal of ONE native call (c1_encode_signals).
+// options.title: one string, or one per item.  Each image is byte for byte what encodeAeaPcm returns for that item alone.
+export async function encodeAeaPcmMany(items, options = {}) {
+  const { title = 'encoded by carta1', ...encoderValues } = options
+  const { signals, counts, frameOffsets } = itemsToSignals(items)
+  const titles = Array.isArray(title) ? title : items.map(() => title)
+  if (titles.length !== items.length || titles.some((t) => typeof t !== 'string')) {
+    throw new TypeError('options.title must be a string or one string per item')
+  }
+  const encoderOptions = new EncoderOptions(encoderValues)
+  const total = frameOffsets[signals.length]
+  const units = total > 0 ? native().encodeSignals(context(), concatSignals(signals, frameOffsets), frameOffsets, encoderOptions.toNative())
+    : new Uint8Array(0)
+  let first = 0
+  return counts.map((nch, k) => {
+    const body = interleaveItemUnits(units, frameOffsets, first, nch)
+    first += nch
+    const image = new Uint8Array(AEA_HEADER_SIZE + body.length)
+    image.set(AeaFile.createHeader(titles[k], body.length / SOUND_UNIT_SIZE, nch), 0)
+    image.set(body, AEA_HEADER_SIZE)
+    return image
+  })
+}
+
+// decodeAeaPcm for many AEA images (Uint8Array or ArrayBuffer) at once -> per image an array of Float32Array, one per channel
+export async function decodeAeaPcmMany(images) {
+  if (!Array.isArray(images)) throw new TypeError('images must be an array of AEA byte images')
+  const parsed = images.map(imageBody)
+  const frameOffsets = new Float64Array(parsed.reduce((n, p) => n + p.nch, 0) + 1)
+  let k = 0
+  for (const { nch, body } of parsed) {
+    for (let c = 0; c < nch; c++, k++) frameOffsets[k + 1] = frameOffsets[k] + body.length / SOUND_UNIT_SIZE / nch
+  }
+  const total = frameOffsets[k]
+  const units = new Uint8Array(total * SOUND_UNIT_SIZE)
+  k = 0
+  for (const { nch, body } of parsed) {
+    deinterleaveItemUnits(body, nch, units, frameOffsets[k])
+    k += nch
+  }
+  const pcm = total > 0 ? native().decodeSignals(context(), units, frameOffsets) : new Float32Array(0)
+  k = 0
+  return parsed.map(({ nch }) => {
+    const out = []
+    for (let c = 0; c < nch; c++, k++) out.push(pcm.slice(frameOffsets[k] * SAMPLES_PER_FRAME, frameOffsets[k + 1] * SAMPLES_PER_FRAME))
+    return out
+  })
 }
 
 // WAV body (interleaved little-endian integer PCM: Int16Array, or a Uint8Array with bits = 16, 24 or 32) -> AEA image.
@@ -107,6 +223,55 @@ export function decodeAeaToWav16(bytes) {
 export class AudioProcessor {
   static encodeAeaPcm(channels, options = {}) { return encodeAeaPcm(channels, options) }
   static decodeAeaPcm(input) { return decodeAeaPcm(input) }
+
+  // PCM frames -> a 16-bit PCM WAV file (the reference's createWavBlob, processor.js:349-447, returns a Blob; createWavBytes
+  // returns the same bytes as a Uint8Array so this also runs where Blob does not exist).  pcmFrames: mono frames (or one
+  // Float32Array), or [left, right] pairs; the shorter side of a pair is zero filled.  Samples are clipped to [-1, 1] and
+  // scaled by 0x7fff (>= 0) or 0x8000 (< 0), then truncated as DataView.setInt16 truncates.
+  static createWavBlob(pcmFrames, channelCount = 1, sampleRate = SAMPLE_RATE) {
+    const bytes = AudioProcessor.createWavBytes(pcmFrames, channelCount, sampleRate)
+    if (typeof Blob === 'undefined') throw new Error('Blob is not available in this runtime; use createWavBytes')
+    return new Blob([bytes], { type: 'audio/wav' })
+  }
+
+  static createWavBytes(pcmFrames, channelCount = 1, sampleRate = SAMPLE_RATE) {
+    if (channelCount !== 1 && channelCount !== 2) throw new Error(`Unsupported channel count: ${channelCount}`)
+    const pcm = AudioProcessor.assemblePcmFrames(Array.isArray(pcmFrames) ? pcmFrames : [pcmFrames], channelCount)
+    const dataBytes = pcm.length * 2
+    const view = new DataView(new ArrayBuffer(44 + dataBytes))
+    const tag = (at, text) => { for (let i = 0; i < 4; i++) view.setUint8(at + i, text.charCodeAt(i)) }
+    tag(0, 'RIFF'); view.setUint32(4, 36 + dataBytes, true); tag(8, 'WAVE')
+    tag(12, 'fmt '); view.setUint32(16, 16, true); view.setUint16(20, 1, true); view.setUint16(22, channelCount, true)
+    view.setUint32(24, sampleRate, true); view.setUint32(28, sampleRate * channelCount * 2, true)
+    view.setUint16(32, channelCount * 2, true); view.setUint16(34, 16, true)
+    tag(36, 'data'); view.setUint32(40, dataBytes, true)
+    for (let i = 0; i < pcm.length; i++) {
+      const x = Math.max(-1, Math.min(1, pcm[i]))
+      view.setInt16(44 + 2 * i, x < 0 ? x * 0x8000 : x * 0x7fff, true)
+    }
+    return new Uint8Array(view.buffer)
+  }
+
+  // PCM frames -> one continuous Float32Array (the reference's assemblePcmFrames, processor.js:545-579): mono frames back to
+  // back, or [left, right] pairs interleaved sample by sample, the shorter side of a pair zero filled
+  static assemblePcmFrames(pcmFrames, channelCount) {
+    if (channelCount === 1) {
+      const pcm = new Float32Array(pcmFrames.reduce((n, f) => n + f.length, 0))
+      let at = 0
+      for (const f of pcmFrames) { pcm.set(f, at); at += f.length }
+      return pcm
+    }
+    if (channelCount !== 2) throw new Error(`Unsupported channel count: ${channelCount}`)
+    const lengths = pcmFrames.map(([l, r]) => Math.max(l.length, r.length))
+    const pcm = new Float32Array(2 * lengths.reduce((n, m) => n + m, 0))
+    let at = 0
+    pcmFrames.forEach(([l, r], k) => {
+      for (let j = 0; j < l.length; j++) pcm[at + 2 * j] = l[j]
+      for (let j = 0; j < r.length; j++) pcm[at + 2 * j + 1] = r[j]
+      at += 2 * lengths[k]
+    })
+    return pcm
+  }
 
   // Streams of frames in, frame fields out: one closure per channel, as processor.js:69-136.
   // options.batchFrames (default 1 = a result after every frame, like the reference): with N > 1 the frames are

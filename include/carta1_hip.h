@@ -133,7 +133,9 @@ int c1_ctx_synchronize(c1_ctx *ctx);
  * ("pack_units"), or in the most recent decode from frame fields -- c1_decode_fields_*, c1_dec_stream_push_fields or a
  * unit push that follows one ("decode_fields") -- or in the from-state kernel of the most recent c1_*_frames_from_states*
  * call ("from_state") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
- * must have been set before the call */
+ * must have been set before the call.  After a c1_*_signals* call, "signal_starts" is the time in the kernels that call adds
+ * to the bulk pass (the row-indexed from-state kernels and the row copies), the other names cover the bulk pass plus the
+ * allocation and packing of the re-encoded frames, and "total" the whole call */
 int c1_ctx_set_profiling(c1_ctx *ctx, int enabled);
 int c1_ctx_kernel_ms(c1_ctx *ctx, const char *name, double *ms, int *launches);
 
@@ -290,6 +292,37 @@ int c1_encode_frames_from_states(c1_ctx *ctx, int64_t n, const float *pcm, const
                                  const c1_encode_options *opts, uint8_t *units, c1_enc_state *out);
 int c1_decode_frames_from_states(c1_ctx *ctx, int64_t n, const uint8_t *units, const c1_dec_state *in, float *pcm,
                                  c1_dec_state *out);
+
+/* n independent mono signals of any lengths, each from its own pool, in one call: what n reference closures produce.  Signal i
+ * owns frames [frame_offsets[i], frame_offsets[i+1]) of one concatenated PCM buffer (512 floats per frame) and the same unit
+ * indices of one concatenated unit buffer (212 bytes per unit).  frame_offsets has n + 1 entries, starts at 0 and never
+ * decreases; a signal may be empty.  All signals share opts.  Signal i starts from in[i], or from a fresh pool (all zeros)
+ * when in is NULL; out[i] receives the pool the reference holds after the signal's last frame.  out may be NULL or in (in
+ * place).  An empty signal writes no units and out[i] = in[i] bit for bit (zeros when in is NULL).  Under fixed block modes
+ * transient_mags passes from in[i] to out[i] unchanged (encoder.js:130-132); under detection it holds the magnitudes of the
+ * signal's last frame.  A stereo file is two signals: the reference's channels are independent closures (processor.js:119-136).
+ * The bytes do not depend on the speculation mode, on how the library chunks the work, or on the neighbouring signals.
+ * How: the concatenation runs once through c1_encode_device / c1_decode_device as one mono stream; then the
+ * first two frames of every signal (decode: the first frame) are computed again from in[i] by the from-state kernels, and the
+ * pools are rebuilt from the last two frames (decode: the last unit) as c1_*_stream_get_state rebuilds them.
+ * c1_ctx_set_decode_precision(1) applies to the bulk of a decode call; the first frame of every signal is still computed in
+ * the reference's number model (binary64 operations, binary32 at every typed-array store), because the from-state kernel has
+ * no other: that frame is bit-identical to the reference either way. */
+/* device pointers -- pcm, units, in, out -- but frame_offsets, a HOST pointer that is read before the call returns.
+ * Asynchronous on the context's stream (the caller's-stream contract above).  n 0 .. 2^20, frame_offsets[n] 0 .. 2^27; pcm
+ * 16-byte aligned, units and states 4-byte aligned.  The states are not checked, as in c1_encode_frames_from_states_device.
+ * A second signals call on the same context waits on the host until the first one's index lists have been uploaded. */
+int c1_encode_signals_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                             const c1_encode_options *opts, uint8_t *units, c1_enc_state *out);
+int c1_decode_signals_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const uint8_t *units, const c1_dec_state *in,
+                             float *pcm, c1_dec_state *out);
+/* host pointers, synchronous; frame_offsets[n] 0 .. 2^22.  C1_ERR_ARG for a non-finite state entry, naming its signal and
+ * field, for frame_offsets that do not start at 0, decrease or pass the limits, and for a NULL frame_offsets, opts, or (with
+ * frames to process) pcm or units.  A rejected call writes nothing. */
+int c1_encode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                      const c1_encode_options *opts, uint8_t *units, c1_enc_state *out);
+int c1_decode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const uint8_t *units, const c1_dec_state *in,
+                      float *pcm, c1_dec_state *out);
 
 /* Snapshot and restore of a stream: host pointers, `channels` entries.  get_state returns what the reference's pool would hold
  * after the same calls -- pushes, option changes and earlier restores; every field zero on a fresh stream.  transient_mags is
