@@ -74,6 +74,10 @@ SIGNATURES = {
                                    C.POINTER(EncodeOptions), C.c_void_p]),
     'c1_encode_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                   C.POINTER(EncodeOptions), C.c_void_p]),
+    'c1_encode_modes_device': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                         C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
+    'c1_encode_modes_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                        C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
     'c1_encode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                         C.POINTER(EncodeOptions), C.c_void_p]),
     'c1_decode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,
@@ -82,6 +86,7 @@ SIGNATURES = {
     'c1_decode_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     'c1_enc_stream_create': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EncodeOptions), C.POINTER(C.c_void_p)]),
     'c1_enc_stream_push': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),
+    'c1_enc_stream_push_modes': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p]),
     'c1_enc_stream_destroy': (C.c_int, [C.c_void_p]),
     'c1_enc_stream_set_options': (C.c_int, [C.c_void_p, C.POINTER(EncodeOptions)]),
     'c1_dec_stream_create': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

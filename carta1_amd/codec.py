@@ -197,6 +197,31 @@ class Context:
                                                units.ctypes.data))
         return units
 
+    def encode_modes(self, channels, modes, options=None, halo_frames=0, out=None):
+        """encode() with the block modes of every frame given: what the reference's closure produces with
+        options.fixedBlockModes set before each frame (the detector does not run).  channels and `out` as for encode();
+        modes: uint8 [frames, nch] or flat (frame-major, channels interleaved), one byte m0 | m1 << 2 | m2 << 4 per sound
+        unit as pack_block_modes() makes them and the detector taps return them.  Of `options` only the allocation bias
+        (or biased table) is used.  A byte outside the domain raises ValueError naming frame, channel and field."""
+        opts = (options or EncoderOptions()).to_c()
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = n // 512 - halo_frames
+        m = check_block_modes(modes, max(frames, 0), len(chans))
+        if out is None:
+            units = np.zeros((max(frames, 0) * len(chans), 212), dtype=np.uint8)
+        else:
+            units = out
+            if units.dtype != np.uint8 or not units.flags['C_CONTIGUOUS'] or units.size != max(frames, 0) * len(chans) * 212:
+                raise ValueError('out must be a contiguous uint8 array of frames * channels * 212 bytes')
+            units = units.reshape(-1, 212)
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_modes_batch(self._h, ptrs, len(chans), frames, halo_frames, C.byref(opts),
+                                                     m.ctypes.data, units.ctypes.data))
+        return units
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -218,6 +243,13 @@ class Context:
         opts = c_options if c_options is not None else (options or EncoderOptions()).to_c()
         capi.check(capi.load().c1_encode_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                 C.byref(opts), C.c_void_p(units_ptr)))
+
+    def encode_modes_device(self, pcm_ptrs, frames, modes_ptr, units_ptr, options=None, halo_frames=0):
+        """c1_encode_modes_device: modes_ptr = frames * channels mode bytes on the device (not checked: a byte outside the
+        domain gives an unspecified unit, never an access outside the buffers)."""
+        opts = (options or EncoderOptions()).to_c()
+        capi.check(capi.load().c1_encode_modes_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                      C.byref(opts), C.c_void_p(modes_ptr), C.c_void_p(units_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -709,14 +741,21 @@ class EncoderStream:
         opts = (options or EncoderOptions()).to_c()
         capi.check(capi.load().c1_enc_stream_create(ctx._h, channels, C.byref(opts), C.byref(self._h)))
 
-    def push(self, channels):
+    def push(self, channels, modes=None):
+        """modes: None, or the block modes of the pushed frames (uint8 [frames, nch] or flat, as for
+        Context.encode_modes): those frames are encoded as the reference encodes them with fixedBlockModes set frame by
+        frame and put back afterwards; the stream's options and its detection history stay as they are."""
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         if len(chans) != self.channels:
             raise ValueError('expected %d channels' % self.channels)
         frames = len(chans[0]) // 512
         units = np.zeros((frames * self.channels, 212), dtype=np.uint8)
-        capi.check(capi.load().c1_enc_stream_push(self._h, capi.ptr_array([c.ctypes.data for c in chans]), frames,
-                                                  units.ctypes.data))
+        ptrs = capi.ptr_array([c.ctypes.data for c in chans])
+        if modes is None:
+            capi.check(capi.load().c1_enc_stream_push(self._h, ptrs, frames, units.ctypes.data))
+        else:
+            m = check_block_modes(modes, frames, self.channels)
+            capi.check(capi.load().c1_enc_stream_push_modes(self._h, ptrs, frames, m.ctypes.data, units.ctypes.data))
         return units
 
     def set_options(self, options):
@@ -789,6 +828,48 @@ class DecoderStream:
 
 
 # ---- AEA container: codec/io/serialization.js:182-254 -------------------------------------------------
+# ---- block modes as bytes: m0 | m1 << 2 | m2 << 4, the detector taps' format and c1_encode_modes_*'s ------------------
+_MODE_FIELDS = ('low', 'mid', 'high')
+
+
+def pack_block_modes(triples):
+    """[n, 3] (or one triple) of block modes as blockSelectorStage returns them -> uint8 [n] mode bytes."""
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    if ((t < 0) | (t > 3)).any():
+        raise ValueError('block modes must be 0..3')
+    return (t[:, 0] | (t[:, 1] << 2) | (t[:, 2] << 4)).astype(np.uint8)
+
+
+def unpack_block_modes(mode_bytes):
+    """uint8 mode bytes (any shape) -> int array [n, 3]: low, mid, high field of each."""
+    b = np.asarray(mode_bytes, dtype=np.uint8).reshape(-1).astype(np.int64)
+    return np.stack([b & 3, (b >> 2) & 3, (b >> 4) & 3], axis=1)
+
+
+def check_block_modes(modes, frames, channels):
+    """modes as a contiguous uint8 array of frames * channels bytes, every one inside blockSelectorStage's domain (low and
+    mid field 0 or 2, high field 0 or 3, bits 6-7 clear); ValueError naming the first offender's frame, channel and field."""
+    m = np.ascontiguousarray(modes)
+    if m.dtype != np.uint8:
+        if m.size and ((m < 0) | (m > 255)).any():
+            raise ValueError('mode bytes must be 0..255')
+        m = m.astype(np.uint8)
+    m = m.reshape(-1)
+    if m.size != frames * channels:
+        raise ValueError('modes must hold frames * channels = %d bytes, got %d' % (frames * channels, m.size))
+    bad = np.flatnonzero(((m & 0xC5) != 0) | (((m & 0x30) != 0) & ((m & 0x30) != 0x30)))
+    if bad.size:
+        i = int(bad[0])
+        b = int(m[i])
+        where = 'frame %d, channel %d' % (i // channels, i % channels) if channels == 2 else 'frame %d' % i
+        for k, name in enumerate(_MODE_FIELDS):
+            f, other = (b >> (2 * k)) & 3, 3 if k == 2 else 2
+            if f not in (0, other):
+                raise ValueError('%s: %s field of mode byte 0x%02x is %d, not 0 or %d' % (where, name, b, f, other))
+        raise ValueError('%s: bits 6-7 of mode byte 0x%02x are set' % (where, b))
+    return m
+
+
 def aea_header(title='', frame_count=0, channel_count=1):
     h = bytearray(AEA_HEADER_SIZE)
     h[0:4] = AEA_MAGIC

@@ -404,6 +404,7 @@ int build_table_fields(const c1_encode_options &o, C1DevEncOpts *d) {
 constexpr int kTotals = 8;                             // running totals of a context (c1_ctx::d_spec_totals)
 constexpr int64_t kSpecMinUnits = 64;                  // default mode: calls below this many sound units use the exact kernels only
 constexpr int kListHead = 8;                           // uint32 counters in front of the speculative path's lists
+constexpr int64_t kMaxModesBatchFrames = (int64_t)1 << 22;   // c1_encode_modes_batch: one staging buffer for the whole call
 constexpr int64_t kMaxChunkFrames = (int64_t)1 << 27;   // x 2 channels = 2^28 units per chunk < 2^29
 
 struct Timing {
@@ -694,11 +695,31 @@ int check_channels(int channels) {
   return C1_OK;
 }
 
+// The domain of a mode byte is what blockSelectorStage writes (encoder.js:143): low and mid fields 0 or 2, high field 0 or 3,
+// bits 6-7 clear.  The first byte outside it: C1_ERR_ARG naming frame, channel (of two) and field
+int check_mode_bytes(const char *what, const uint8_t *modes, int64_t frames, int channels) {
+  static const char *const kField[3] = {"low", "mid", "high"};
+  for (int64_t i = 0; i < frames * channels; i++) {
+    const int b = modes[i];
+    if ((b & ~0x3a) == 0 && ((b & 0x30) == 0 || (b & 0x30) == 0x30)) continue;
+    char where[64];
+    if (channels == 2) snprintf(where, sizeof where, "frame %lld, channel %d", (long long)(i / 2), (int)(i & 1));
+    else snprintf(where, sizeof where, "frame %lld", (long long)i);
+    for (int k = 0; k < 3; k++) {
+      const int m = (b >> (2 * k)) & 3, other = k == 2 ? 3 : 2;
+      if (m != 0 && m != other)
+        return fail(C1_ERR_ARG, "%s: %s: %s field of mode byte 0x%02x is %d, not 0 or %d", what, where, kField[k], b, m, other);
+    }
+    return fail(C1_ERR_ARG, "%s: %s: bits 6-7 of mode byte 0x%02x are set", what, where, b);
+  }
+  return C1_OK;
+}
+
 // lazy: the call may return with its last tail still unjoined (c1_encode_device on a context that owns its stream: nobody
 // else can enqueue on that stream, and every other entry point joins first)
 int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                        const c1_encode_options *opts, uint8_t *units, float *bands, float *coefs_tap,
-                       uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false) {
+                       uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr) {
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx, false);
   if (rc) return rc;
@@ -713,7 +734,10 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   if ((rc = upload_opts(ctx, opts))) return rc;
   if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
   if (frames == 0) return C1_OK;
-  const bool detect = opts->fixed_block_modes[0] < 0;
+  // given_modes (c1_encode_modes_device): one mode byte per unit on the device instead of the detector's decision.  The call
+  // is laid out like a detection call (bands, mode bytes and unit lists in the detection workspace); of `opts` only the
+  // biased scale factors reach a kernel that runs
+  const bool detect = given_modes || opts->fixed_block_modes[0] < 0;
   const bool taps = coefs_tap || side_tap || alloc_tap;
   const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect);
   if ((rc = ensure_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
@@ -730,7 +754,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   bool speculate = (all_long_modes || all_short_modes) && !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
   bool quantize32 = !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;   // exact coefficients, binary32 quantization with the guard (below)
   static const bool det_spec_env_off = getenv("C1_DETECT_SPEC") && atoi(getenv("C1_DETECT_SPEC")) == 0;   // experiments: exact detector, the rest as usual
-  bool detect_spec = detect && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
+  bool detect_spec = detect && !given_modes && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
   // A call of a few frames (a frame closure, a short streaming push) is bound by the number of launches behind it, and
   // every speculative shortcut adds some (the redo chain, the recheck, the second packing pass): in the default mode such
   // calls take the exact kernels (one mono frame: 159 against 185 us, tools/latency_probe.py).  A rule on the size of
@@ -865,7 +889,10 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
     {
       ScopedTiming t(ctx, K_ANALYSIS, sA);
       if (all_long) c1k_launch_analysis_long(L, sA);
-      else if (detect) {
+      else if (given_modes) {
+        c1k_launch_modes_front(L, given_modes + f0 * channels, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
+        c1k_launch_mdct_bands(L, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
+      } else if (detect) {
         c1k_launch_detect(L, ctx->d_bands[p], ctx->d_feat[p], ctx->d_modes[p], ctx->d_lists[p], detect_spec, nullptr, sA);
         if (detect_spec) c1k_launch_spec_totals(ctx->d_spec_totals, (uint64_t)(n * channels), ctx->d_lists[p] + 2, 2, sA);
         if (L.bands) HIP_TRY(hipMemcpyAsync(L.bands, ctx->d_bands[p] + (size_t)channels * 512, (size_t)n * channels * 512 * sizeof(float),
@@ -1273,6 +1300,13 @@ static int encode_device_joined(c1_ctx *ctx, const float *const *pcm, int channe
                                 const c1_encode_options *opts, uint8_t *units) {
   if (!units && frames > 0) return fail(C1_ERR_ARG, "units is NULL");
   return encode_device_impl(ctx, pcm, channels, frames, halo_frames, opts, units, nullptr, nullptr, nullptr, nullptr, false);
+}
+
+int c1_encode_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                           const c1_encode_options *opts, const uint8_t *modes, uint8_t *units) {
+  if (frames > 0 && (!modes || !units)) return fail(C1_ERR_ARG, "modes or units is NULL");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, opts, units, nullptr, nullptr, nullptr, nullptr, false, frames > 0 ? modes : nullptr);
 }
 
 int c1_encode_stages_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
@@ -2160,6 +2194,37 @@ int c1_encode_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t 
   return C1_OK;
 }
 
+int c1_encode_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                          const c1_encode_options *opts, const uint8_t *modes, uint8_t *units) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if (frames == 0) return C1_OK;
+  if (!pcm || !units || !modes) return fail(C1_ERR_ARG, "pcm, modes or units is NULL");
+  for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  if ((rc = check_mode_bytes("c1_encode_modes_batch", modes, frames, channels))) return rc;   // before any device work
+  // one copy in, the device call, one copy out
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  const size_t unit_bytes = (size_t)frames * channels * C1_UNIT_BYTES, mode_bytes = (size_t)frames * channels;
+  const size_t unit_off = (ch_bytes * channels + 255) & ~(size_t)255, mode_off = (unit_off + unit_bytes + 255) & ~(size_t)255;
+  if ((rc = ensure_io(ctx, mode_off + mode_bytes))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_modes = (uint8_t *)ctx->d_io + mode_off;
+  HIP_TRY(hipMemcpyAsync(d_modes, modes, mode_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_modes_device(ctx, dptr, channels, frames, halo_frames, opts, d_modes, d_units))) return rc;
+  HIP_TRY(hipMemcpyAsync(units, d_units, unit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 int c1_decode_device(c1_ctx *ctx, const uint8_t *units, int channels, int64_t frames, int halo_units,
                      float *const *pcm) {
   CTX_GUARD(ctx);
@@ -2584,6 +2649,7 @@ struct c1_enc_stream {
   float *d_hist;       // channels * 2 frames: the last 1024 PCM samples of each channel
   float *d_buf = nullptr;
   uint8_t *d_units = nullptr;
+  uint8_t *d_given = nullptr;      // mode bytes of a push with given modes (c1_enc_stream_push_modes), cap_frames * channels
   int64_t cap_frames = 0;
   int64_t pushed = 0;              // frames per channel encoded so far
   EncHistory hist = HIST_PREV;     // where the detection history of the next frame lives (same for every channel)
@@ -2800,6 +2866,24 @@ int enc_stream_current_state(c1_enc_stream *s) {
   s->state_live = true;
   return C1_OK;
 }
+
+// detection -> fixed modes on the usual path (nothing left to encode from d_state): the detection history freezes at the last
+// frame detection ran on.  HIST_PREV: that is the last pushed frame; its bands are kept (or there is none: a fresh pool's zeros)
+int enc_stream_freeze_history(c1_enc_stream *s) {
+  if (s->hist != HIST_PREV) return C1_OK;
+  if (s->pushed == 0) { s->hist = HIST_ZEROS; return C1_OK; }
+  int rc = enc_stream_scratch(s);
+  if (rc) return rc;
+  const float *last[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < s->channels; c++) last[c] = s->d_hist + 1024 * c + 512;
+  if ((rc = enc_stream_bands(s, last, 1, 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_stored, s->sw.bands, (size_t)s->channels * 512 * sizeof(float), hipMemcpyDeviceToDevice, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  s->hist = HIST_STORED;
+  return C1_OK;
+}
+
+int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units);
 }  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
@@ -2835,25 +2919,25 @@ int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts) {
     s->opts = *opts;
     return C1_OK;
   }
-  if (opts_detect(s->opts) && !opts_detect(*opts) && s->hist == HIST_PREV) {
-    if (s->pushed > 0) {
-      // detection -> fixed modes: the history freezes at the last pushed frame's magnitudes; keep that frame's bands
-      if ((rc = enc_stream_scratch(s))) return rc;
-      const float *last[C1_MAX_CHANNELS] = {nullptr, nullptr};
-      for (int c = 0; c < s->channels; c++) last[c] = s->d_hist + 1024 * c + 512;
-      if ((rc = enc_stream_bands(s, last, 1, 1))) return rc;
-      HIP_TRY(hipMemcpyAsync(s->d_stored, s->sw.bands, (size_t)s->channels * 512 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      s->hist = HIST_STORED;
-    } else {
-      s->hist = HIST_ZEROS;
-    }
-  }
+  if (opts_detect(s->opts) && !opts_detect(*opts) && (rc = enc_stream_freeze_history(s))) return rc;
   s->opts = *opts;
   return C1_OK;
 }
 
 int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames, uint8_t *units) {
+  return enc_stream_push_impl(s, pcm, frames, nullptr, units);
+}
+
+int c1_enc_stream_push_modes(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units) {
+  if (!modes && frames > 0) return fail(C1_ERR_ARG, "modes is NULL");
+  return enc_stream_push_impl(s, pcm, frames, modes, units);
+}
+
+namespace {
+// modes null: the stream's options decide.  Else the frames behave as if the options had been switched to fixed block modes
+// for them, frame by frame and channel by channel, and back afterwards: the detector does not run, and on a stream under
+// detection its history stays where c1_enc_stream_set_options would have frozen it
+int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units) {
   if (!s) return fail(C1_ERR_ARG, "stream is NULL");
   c1_ctx *ctx = s->ctx;
   CTX_GUARD(ctx);
@@ -2864,7 +2948,9 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   if (!pcm || !units) return fail(C1_ERR_ARG, "pcm or units is NULL");
   for (int c = 0; c < s->channels; c++)
     if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
-  const bool detect = opts_detect(s->opts);
+  if (modes && (rc = check_mode_bytes("c1_enc_stream_push_modes", modes, frames, s->channels))) return rc;   // the stream is as it was
+  if (modes && opts_detect(s->opts) && s->state_frames == 0 && (rc = enc_stream_freeze_history(s))) return rc;
+  const bool detect = !modes && opts_detect(s->opts);
   // frames of this push that are encoded from the explicit state: the first two after a restore, or the first under
   // detection when the detection history is a set of magnitudes only the state holds
   int64_t from_state = std::min<int64_t>(frames, s->state_frames);
@@ -2875,10 +2961,11 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   const bool switch_frame = from_state == 0 && detect && s->hist != HIST_PREV && s->pushed > 0;
   if (switch_frame && (rc = enc_stream_scratch(s))) return rc;
   if (frames > s->cap_frames) {
-    if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); }
-    s->d_buf = nullptr; s->d_units = nullptr; s->cap_frames = 0;
+    if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); hipFree(s->d_given); }
+    s->d_buf = nullptr; s->d_units = nullptr; s->d_given = nullptr; s->cap_frames = 0;
     HIP_TRY(hipMalloc(&s->d_buf, (size_t)s->channels * (frames + 2) * 512 * sizeof(float)));
     HIP_TRY(hipMalloc(&s->d_units, (size_t)s->channels * frames * C1_UNIT_BYTES));
+    HIP_TRY(hipMalloc(&s->d_given, (size_t)s->channels * frames));
     s->cap_frames = frames;
   }
   const size_t stride = (size_t)(s->cap_frames + 2) * 512;
@@ -2889,15 +2976,34 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
     HIP_TRY(hipMemcpyAsync(d + 1024, pcm[c], (size_t)frames * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     dptr[c] = d + 1024;
   }
+  if (modes) HIP_TRY(hipMemcpyAsync(s->d_given, modes, (size_t)frames * s->channels, hipMemcpyHostToDevice, ctx->stream));
+  // the frames that are not encoded from the explicit state: the stream's options, or the given modes in their place
+  auto encode_rest = [&](const float *const *p, int64_t first, int64_t n) {
+    uint8_t *out = s->d_units + (size_t)first * s->channels * C1_UNIT_BYTES;
+    if (!modes) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
+    return encode_device_impl(ctx, p, s->channels, n, 2, &s->opts, out, nullptr, nullptr, nullptr, nullptr, false,
+                              s->d_given + (size_t)first * s->channels);
+  };
   if (from_state > 0) {
-    for (int64_t f = 0; f < from_state; f++)   // frame after frame: each continues the pool the one before left
-      if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
-                                        s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state))) return rc;
+    for (int64_t f = 0; f < from_state; f++) {   // frame after frame: each continues the pool the one before left
+      if (!modes) {
+        if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
+                                          s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state))) return rc;
+        continue;
+      }
+      for (int c = 0; c < s->channels; c++) {    // the from-state kernel takes one triple per launch: a pool at a time
+        c1_encode_options one = s->opts;
+        const int b = modes[f * s->channels + c];
+        one.fixed_block_modes[0] = b & 3; one.fixed_block_modes[1] = (b >> 2) & 3; one.fixed_block_modes[2] = (b >> 4) & 3;
+        if ((rc = encode_from_states_impl(ctx, 1, dptr[c] + f * 512, (int64_t)stride, s->d_state + (size_t)c * kEncStateFloats, &one,
+                                          s->d_units + (size_t)(f * s->channels + c) * C1_UNIT_BYTES,
+                                          s->d_state + (size_t)c * kEncStateFloats))) return rc;
+      }
+    }
     if (frames > from_state) {
       const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
       for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + from_state * 512;
-      if ((rc = encode_device_joined(ctx, rest, s->channels, frames - from_state, 2, &s->opts,
-                                     s->d_units + (size_t)from_state * s->channels * C1_UNIT_BYTES))) return rc;
+      if ((rc = encode_rest(rest, from_state, frames - from_state))) return rc;
     }
   } else if (switch_frame) {
     if ((rc = enc_stream_switch_frame(s, dptr, s->d_units))) return rc;
@@ -2907,7 +3013,7 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
       if ((rc = encode_device_joined(ctx, rest, s->channels, frames - 1, 2, &s->opts, s->d_units + (size_t)s->channels * C1_UNIT_BYTES)))
         return rc;
     }
-  } else if ((rc = encode_device_joined(ctx, dptr, s->channels, frames, 2, &s->opts, s->d_units))) {
+  } else if ((rc = encode_rest(dptr, 0, frames))) {
     return rc;
   }
   for (int c = 0; c < s->channels; c++)   // new history = the last two frames of [history | pushed]
@@ -2926,6 +3032,7 @@ int c1_enc_stream_push(c1_enc_stream *s, const float *const *pcm, int64_t frames
   if (detect) s->hist = HIST_PREV;
   return C1_OK;
 }
+}  // namespace
 
 int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (!s) return C1_OK;
@@ -2934,6 +3041,7 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (s->d_hist) hipFree(s->d_hist);
   if (s->d_buf) hipFree(s->d_buf);
   if (s->d_units) hipFree(s->d_units);
+  if (s->d_given) hipFree(s->d_given);
   if (s->d_sw_block) hipFree(s->d_sw_block);
   if (s->d_state) hipFree(s->d_state);
   delete s;

@@ -13,6 +13,7 @@
 //   c1_k_analysis.hip  k_analysis_fast<ALL_LONG>: fixed block modes; one wave walks 64 consecutive frames of one
 //                      channel carrying QMF delay lines and MDCT overlap like the reference's BufferPool
 //   c1_k_detect.hip    k_detect_features -> k_detect_decide -> k_mdct_bands<LONG>: transient detection
+//   c1_k_modes.hip     k_qmf_bands -> k_modes_lists -> k_mdct_bands<LONG>: block modes given by the caller
 //   c1_k_allocate.hip  k_alloc_first / k_alloc_rest / k_alloc_select: the greedy RDO heaps, one lane per heap
 //   c1_k_pack.hip      k_pack<ALL_LONG>: quantize + MSB-first packing, one wave per sound unit
 //   c1_k_decode.hip    k_decode: unpack, dequantize, IMDCT + overlap-add, QMF synthesis

@@ -251,6 +251,11 @@ constexpr int kFeatureWsDoubles = 20;
 // score_tap (tests): units * 3 * 2 doubles {lo, hi} (speculative) or {score, score}.  L.coefs null: decisions only.
 void c1k_launch_detect(const C1EncodeLaunch &L, float *bands_ws, double *feat_ws, uint8_t *modes_ws, uint32_t *lists_ws,
                        bool speculative, double *score_tap, hipStream_t stream);
+// block modes given by the caller (c1_k_modes.hip): QMF analysis alone into bands_ws (k_qmf_bands), then the caller's mode bytes
+// (one per unit, device memory, any value: masked to blockSelectorStage's domain) into modes_ws and the all-long / mixed lists
+// (k_modes_lists).  Workspaces as for c1k_launch_detect; c1k_launch_mdct_bands takes over from there
+void c1k_launch_modes_front(const C1EncodeLaunch &L, const uint8_t *given_modes, float *bands_ws, uint8_t *modes_ws, uint32_t *lists_ws,
+                            hipStream_t stream);
 // mdctStage + scale factors from stored band samples (k_mdct_bands): bands_ws (units + channels) * 512 floats with slot row 0 =
 // frame -1, modes_ws one byte per unit, lists_ws = {count all-long, count mixed, -, -} then the two unit lists, `units` entries apart
 void c1k_launch_mdct_bands(const C1EncodeLaunch &L, const float *bands_ws, const uint8_t *modes_ws, const uint32_t *lists_ws, hipStream_t stream);

@@ -2,6 +2,7 @@
 #include "c1_device.h"
 #include "c1_detect_bound.h"
 #include "c1_detect_core.h"
+#include "c1_qmf_core.h"
 
 namespace {
 
@@ -219,56 +220,8 @@ __global__ __launch_bounds__(C1_WAVE, SPEC ? 4 : 3) void k_detect_features(C1Enc
     TablesPtr T = tables_for_this_frame(L.tables);
     lane = lane_for_this_frame(lane0);
 
-    // ---------------- qmfAnalysisStage (encoder.js:57-96) ----------------
-    {
-      const v4f a = pre_a, b = pre_b;
-      double *w1 = S.u.q1.w1;
-      if (lane < 46) w1[pidx<3>(lane)] = S.d1[lane];
-      const int e0 = 46 + 4 * lane;
-      *reinterpret_cast<double2 *>(&w1[pidx<3>(e0)]) = make_double2((double)a.x, (double)a.y);
-      *reinterpret_cast<double2 *>(&w1[pidx<3>(e0 + 2)]) = make_double2((double)a.z, (double)a.w);
-      *reinterpret_cast<double2 *>(&w1[pidx<3>(e0 + 256)]) = make_double2((double)b.x, (double)b.y);
-      *reinterpret_cast<double2 *>(&w1[pidx<3>(e0 + 258)]) = make_double2((double)b.z, (double)b.w);
-    }
-    wave_fence();
-    {
-      // the next frame's PCM (the last frame asks for itself again: under a condition the loaded values are copied into the
-      // loop-carried registers behind the load, i.e. waited for on the spot)
-      const v4f *p4 = reinterpret_cast<const v4f *>(pcm + ((f + 1 < f_end) ? f + 1 : f) * 512);
-      pre_a = p4[lane]; pre_b = p4[64 + lane];
-    }
-    {
-      double ev[4], od[4];
-      __builtin_amdgcn_s_setprio(3);   // wave priorities as in k_analysis_fast: QMF cores 3, transient FFT 0, the rest 1
-      if (own_block()) qmf_analysis_core<4, 3>(S.u.q1.w1, lane, T, ev, od); else { for (int d = 0; d < 4; d++) { ev[d] = S.u.q1.w1[lane + d]; od[d] = 1.0; } }
-      double *w2 = S.u.q2.w2;
-      if (lane < 46) { w2[pidx<2>(lane)] = S.d2[lane]; S.d1[lane] = S.u.q1.w1[pidx<3>(512 + lane)]; }
-      float lo[4];
-#pragma unroll
-      for (int d = 0; d < 4; d++) {
-        lo[d] = f32(ev[d] + od[d]);
-        S.hbuf[39 + 4 * lane + d] = f32(ev[d] - od[d]);
-      }
-      *reinterpret_cast<double2 *>(&w2[pidx<2>(46 + 4 * lane)]) = make_double2((double)lo[0], (double)lo[1]);
-      *reinterpret_cast<double2 *>(&w2[pidx<2>(48 + 4 * lane)]) = make_double2((double)lo[2], (double)lo[3]);
-    }
-    wave_fence();
-    {
-      double ev[2], od[2];
-      if (own_block()) qmf_analysis_core<2, 2>(S.u.q2.w2, lane, T, ev, od); else { for (int d = 0; d < 2; d++) { ev[d] = S.u.q2.w2[lane + d]; od[d] = 1.0; } }
-      __builtin_amdgcn_s_setprio(1);
-      *reinterpret_cast<float2 *>(&S.band[2 * lane]) = make_float2(f32(ev[0] + od[0]), f32(ev[1] + od[1]));
-      *reinterpret_cast<float2 *>(&S.band[128 + 2 * lane]) = make_float2(f32(ev[0] - od[0]), f32(ev[1] - od[1]));
-      *reinterpret_cast<float4 *>(&S.band[256 + 4 * lane]) = *reinterpret_cast<const float4 *>(&S.hbuf[4 * lane]);
-      if (lane < 46) S.d2[lane] = S.u.q2.w2[pidx<2>(256 + lane)];
-    }
-    wave_fence();
-    {
-      float keep = 0.0f;
-      if (lane < 39) keep = S.hbuf[256 + lane];
-      wave_fence();
-      if (lane < 39) S.hbuf[lane] = keep;
-    }
+    // ---------------- qmfAnalysisStage (encoder.js:57-96) and the request for the next frame's PCM ----------------
+#include "c1_qmf_frame.inc"
     // The next frame's PCM, requested before the first QMF stage, is taken delivery of here -- at a point every path to the top
     // of the loop passes, and before any store of this frame is issued: a load still pending on ONE path makes the compiler wait
     // at the top of the loop on ALL of them, and there the wait would sit right behind the frame's stores (loads and stores
@@ -313,33 +266,6 @@ __global__ __launch_bounds__(C1_WAVE, SPEC ? 4 : 3) void k_detect_features(C1Enc
     __builtin_amdgcn_s_setprio(1);
     wave_fence();
   }
-}
-
-// two work lists for the MDCT stage: all-long units and units with a short band (lists[0], lists[1] = counts, then
-// `units` entries each), and behind them the units the speculative detector could not decide (lists[2]).  One atomic per
-// 256-thread block and list: the three counters take about 5 ns per atomic whoever issues it, and one per wave (94 k
-// for 2 M units) was 0.56 of the speculative decision kernel's 0.80 ms.
-__device__ __forceinline__ void append_by_mode(bool live, int kind, int64_t unit, int64_t units, uint32_t *__restrict__ lists) {
-  __shared__ uint32_t wave_count[3][4], wave_base[3][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t below = (1ull << lane) - 1ull;
-  uint64_t m[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    m[k] = __ballot(live && kind == k);
-    if (lane == 0) wave_count[k][wave] = (uint32_t)__popcll(m[k]);
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    const uint32_t c0 = wave_count[k][0], c1 = wave_count[k][1], c2 = wave_count[k][2], c3 = wave_count[k][3];
-    const uint32_t total = c0 + c1 + c2 + c3;
-    const uint32_t base = total ? atomicAdd(&lists[k], total) : 0u;
-    wave_base[k][0] = base; wave_base[k][1] = base + c0; wave_base[k][2] = base + c0 + c1; wave_base[k][3] = base + c0 + c1 + c2;
-  }
-  __syncthreads();
-  const uint64_t mine = kind == 0 ? m[0] : (kind == 1 ? m[1] : m[2]);
-  if (live) lists[4 + (int64_t)kind * units + wave_base[kind][wave] + __popcll(mine & below)] = (uint32_t)unit;
 }
 
 // SPEC = false: the reference's decision from its 18 sums.  SPEC = true: the interval of c1_detect_bound.h from the

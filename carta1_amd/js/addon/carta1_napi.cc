@@ -228,6 +228,32 @@ napi_value EncodeBatch(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// encodeBatchModes(ctx, [Float32Array...], haloFrames, options, Uint8Array modes) -> Uint8Array(frames*channels*212):
+// c1_encode_modes_batch, one mode byte per sound unit (frame-major, channels interleaved); of the options only the bias is used
+napi_value EncodeBatchModes(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_modes = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *modes;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o) || !get_typed(env, argv[4], napi_uint8_array, &modes, &n_modes)) return nullptr;
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  if (n_modes != (size_t)frames * ch.size()) { napi_throw_type_error(env, nullptr, "modes: one byte per frame and channel"); return nullptr; }
+  uint8_t *units;
+  napi_value out = make_u8(env, (size_t)frames * ch.size() * C1_UNIT_BYTES, &units);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_modes_batch(ctx, p, (int)ch.size(), frames, halo, &o, static_cast<const uint8_t *>(modes), units);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1026,6 +1052,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", nullptr, CtxCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"allocPinned", nullptr, AllocPinned, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeBatchModes", nullptr, EncodeBatchModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context } from '../native.js'
+import { native, context, encodeBatchModes } from '../native.js'
 
 function padChannels(channels) {
   const longest = Math.max(...channels.map((c) => c.length))
@@ -28,13 +28,22 @@ export async function encodeAeaPcm(channels, options = {}) {
   checkChannels(channels)
   // options.devices (not in the reference): device indices to shard the frame batch over, e.g. [0, 1, 2, 3]; contiguous
   // frame ranges, one context and host thread per entry, no collective -- same bytes as one device
-  const { title = 'encoded by carta1', devices, ...encoderValues } = options
+  // options.blockModes (not in the reference): a Uint8Array of frames * channels mode bytes (m0 | m1 << 2 | m2 << 4, frame-major,
+  // channels interleaved), frames = ceil(length / 512): every frame is encoded as the reference encodes it with fixedBlockModes
+  // set to that frame's modes before the call; the detector does not run and devices is not used
+  const { title = 'encoded by carta1', devices, blockModes, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
+  if (blockModes !== undefined && blockModes !== null &&
+      (!(blockModes instanceof Uint8Array) || blockModes.length !== frames * channels.length)) {
+    throw new TypeError(`blockModes must be a Uint8Array of frames * channels = ${frames * channels.length} mode bytes`)
+  }
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0) {
+  if (frames > 0 && blockModes) {
+    image.set(encodeBatchModes(padded, blockModes, encoderOptions.toNative()), AEA_HEADER_SIZE)
+  } else if (frames > 0) {
     const where = Array.isArray(devices) && devices.length ? devices : context()
     const units = await native().encodeBatchAsync(where, padded, 0, encoderOptions.toNative())
     image.set(units, AEA_HEADER_SIZE)

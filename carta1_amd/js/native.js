@@ -35,3 +35,11 @@ export function deviceCount() {
 export function allocPinnedFloat32Array(length) {
   return new Float32Array(native().allocPinned(length * 4))
 }
+
+// c1_encode_modes_batch on the default context: encode() with the block modes of every frame given.  channels: one or two
+// Float32Arrays of (haloFrames + frames) * 512 samples; modes: Uint8Array of frames * channels bytes m0 | m1 << 2 | m2 << 4
+// (frame-major, channels interleaved; low and mid field 0 or 2, high field 0 or 3); nativeOptions: EncoderOptions.toNative(),
+// of which only the allocation bias is used.  Returns the units, frames * channels * 212 bytes.
+export function encodeBatchModes(channels, modes, nativeOptions, haloFrames = 0, ctx = context()) {
+  return native().encodeBatchModes(ctx, channels, haloFrames, nativeOptions, modes)
+}

@@ -195,6 +195,36 @@ int c1_encode_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t
 int c1_encode_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames,
                     int halo_frames, const c1_encode_options *opts, uint8_t *units);
 
+/* ---- encode with the block modes supplied by the caller: encode() with options.fixedBlockModes set before every frame
+ *      (blockSelectorStage reads it on every call, encoder.js:129-133) -------------------------------------------------------
+ * Frames 0 .. frames-1 of every channel are encoded exactly as the reference's closure encodes them when fixedBlockModes =
+ * the frame's modes is set before each call: the detector does not run (transientDetection is not touched, :130-132), the QMF
+ * delays and the MDCT overlap carry across frames whatever the modes are (functions of the PCM history alone, as under
+ * c1_enc_stream_set_options), and every channel has its own mode per frame.
+ * modes: one byte per sound unit, m0 | m1 << 2 | m2 << 4 (low, mid, high band), unit index = frame * channels + channel --
+ * the bytes c1_detect_stages_device and c1_detect_scores_device write into `modes`, so a tap's output can be edited and fed
+ * straight back.  Domain: what blockSelectorStage produces (:143): low and mid fields 0 or 2, high field 0 or 3, bits 6-7
+ * clear.  Modes cover the call's frames only; halo frames need none.
+ * opts->biased_scale_factors = allocationBias's table (threshold and fixed modes are not read); opts is validated as every
+ * encode call validates it.
+ * The bytes do not depend on the speculation mode (given modes always take the exact analysis; unless speculation is 0 the
+ * quantization runs in binary32 behind its guard, as on the other exact paths), on how the call is cut into chunks
+ * (C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP) or on the run length.  c1_ctx_kernel_ms counts the front end and the MDCT under
+ * "analysis".
+ *
+ * device-resident: pcm[c] (16-byte aligned), modes (any alignment) and units are DEVICE pointers; asynchronous on the context's
+ * stream like c1_encode_device, chunked like it (a transient-detection call's workspace, 4.8 KB per unit); frames 0 .. 2^27 per
+ * channel.  The mode bytes are NOT checked: every byte is brought into the domain before a kernel indexes with its fields
+ * (fields & 2 for low and mid; high 3 when it is 3, else 0), so no access leaves the buffers, and for a byte outside the
+ * domain the unit's content is unspecified. */
+int c1_encode_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                           const c1_encode_options *opts, const uint8_t *modes /* device, frames*channels */, uint8_t *units);
+/* host-resident, synchronous: every mode byte is validated before any device work -- a byte outside the domain returns
+ * C1_ERR_ARG naming the frame, the channel (of two) and the field, and nothing is written -- then one copy in, the device call,
+ * one copy out.  frames 0 .. 2^22 per channel (the three-stream pipeline of c1_encode_batch is not used here). */
+int c1_encode_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                          const c1_encode_options *opts, const uint8_t *modes /* host, frames*channels */, uint8_t *units);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
@@ -245,6 +275,15 @@ int c1_enc_stream_destroy(c1_enc_stream *s);
  * selector follows the reference's Math.max / Math.min, where the encoder's detector clamps, so there it follows the
  * reference.  Setting the options a stream already has changes nothing. */
 int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts);
+/* c1_enc_stream_push with the block modes of the pushed frames given (mode bytes as for c1_encode_modes_batch, validated the
+ * same way: an invalid byte returns C1_ERR_ARG and leaves the stream as it was).  The stream continues bit for bit as the
+ * reference's closure does when fixedBlockModes is set frame by frame for these frames and then put back to what the stream's
+ * options say; the stream's options do not change.  On a stream under detection the frames behave like a temporary switch to
+ * fixed modes: the detection history stays at the last frame detection ran on (c1_enc_stream_get_state: transient_mags is
+ * unchanged by these frames), and the first frame of the next ordinary push is detected against it, by the mechanism described
+ * under c1_enc_stream_set_options.  On a stream under fixed modes the frames simply take the given modes. */
+int c1_enc_stream_push_modes(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
+                             const uint8_t *modes /* host, frames*channels */, uint8_t *units /* host, frames*channels*212 */);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
