@@ -78,6 +78,10 @@ SIGNATURES = {
                                          C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
     'c1_encode_modes_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                         C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p]),
+    'c1_encode_biases_device': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                          C.POINTER(EncodeOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_biases_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                         C.POINTER(EncodeOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_encode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                         C.POINTER(EncodeOptions), C.c_void_p]),
     'c1_decode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,
@@ -87,6 +91,8 @@ SIGNATURES = {
     'c1_enc_stream_create': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EncodeOptions), C.POINTER(C.c_void_p)]),
     'c1_enc_stream_push': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),
     'c1_enc_stream_push_modes': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p]),
+    'c1_enc_stream_push_biases': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(EncodeOptions), C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_enc_stream_destroy': (C.c_int, [C.c_void_p]),
     'c1_enc_stream_set_options': (C.c_int, [C.c_void_p, C.POINTER(EncodeOptions)]),
     'c1_dec_stream_create': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

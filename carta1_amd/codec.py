@@ -222,6 +222,31 @@ class Context:
                                                      m.ctypes.data, units.ctypes.data))
         return units
 
+    def encode_biases(self, channels, biases, modes=None, options=None, halo_frames=0, out=None):
+        """encode() with the allocation bias of every frame given: what the reference's closure produces with
+        options.allocationBias set before each frame.  channels, `out` as for encode(); biases: one value per frame (all
+        channels) or [frames, nch], each in allocationBias's range.  The distinct values (at most MAX_BIAS_PALETTE, else
+        ValueError) become the call's palette, their tables made as EncoderOptions.to_c() makes them.  modes: None (detection
+        or fixed modes as `options` say) or mode bytes as for encode_modes().  The allocationBias of `options` is not used."""
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = n // 512 - halo_frames
+        palette, index = bias_palette(biases, max(frames, 0), len(chans), options)
+        m = None if modes is None else check_block_modes(modes, max(frames, 0), len(chans))
+        if out is None:
+            units = np.zeros((max(frames, 0) * len(chans), 212), dtype=np.uint8)
+        else:
+            units = out
+            if units.dtype != np.uint8 or not units.flags['C_CONTIGUOUS'] or units.size != max(frames, 0) * len(chans) * 212:
+                raise ValueError('out must be a contiguous uint8 array of frames * channels * 212 bytes')
+            units = units.reshape(-1, 212)
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_biases_batch(self._h, ptrs, len(chans), frames, halo_frames, palette, len(palette),
+                                                      index.ctypes.data, None if m is None else m.ctypes.data, units.ctypes.data))
+        return units
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -250,6 +275,15 @@ class Context:
         opts = (options or EncoderOptions()).to_c()
         capi.check(capi.load().c1_encode_modes_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                       C.byref(opts), C.c_void_p(modes_ptr), C.c_void_p(units_ptr)))
+
+    def encode_biases_device(self, pcm_ptrs, frames, palette_options, index_ptr, units_ptr, modes_ptr=None, halo_frames=0):
+        """c1_encode_biases_device: palette_options = 1 .. MAX_BIAS_PALETTE EncoderOptions (an entry may carry its own
+        biased_table); index_ptr = frames * channels palette indices on the device (not checked: a byte outside the palette
+        selects entry 0); modes_ptr = mode bytes on the device as for encode_modes_device, or None."""
+        palette = palette_array([o.to_c() for o in palette_options])
+        capi.check(capi.load().c1_encode_biases_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                       palette, len(palette_options), C.c_void_p(index_ptr),
+                                                       C.c_void_p(modes_ptr) if modes_ptr else None, C.c_void_p(units_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -741,17 +775,25 @@ class EncoderStream:
         opts = (options or EncoderOptions()).to_c()
         capi.check(capi.load().c1_enc_stream_create(ctx._h, channels, C.byref(opts), C.byref(self._h)))
 
-    def push(self, channels, modes=None):
+    def push(self, channels, modes=None, biases=None):
         """modes: None, or the block modes of the pushed frames (uint8 [frames, nch] or flat, as for
         Context.encode_modes): those frames are encoded as the reference encodes them with fixedBlockModes set frame by
-        frame and put back afterwards; the stream's options and its detection history stay as they are."""
+        frame and put back afterwards; the stream's options and its detection history stay as they are.
+        biases: None, or the allocation bias of the pushed frames (one per frame or [frames, nch], as for
+        Context.encode_biases): those frames allocate as the reference does with allocationBias set frame by frame; the
+        stream's options stay as they are."""
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         if len(chans) != self.channels:
             raise ValueError('expected %d channels' % self.channels)
         frames = len(chans[0]) // 512
         units = np.zeros((frames * self.channels, 212), dtype=np.uint8)
         ptrs = capi.ptr_array([c.ctypes.data for c in chans])
-        if modes is None:
+        if biases is not None:
+            palette, index = bias_palette(biases, frames, self.channels, None)
+            m = None if modes is None else check_block_modes(modes, frames, self.channels)
+            capi.check(capi.load().c1_enc_stream_push_biases(self._h, ptrs, frames, palette, len(palette), index.ctypes.data,
+                                                             None if m is None else m.ctypes.data, units.ctypes.data))
+        elif modes is None:
             capi.check(capi.load().c1_enc_stream_push(self._h, ptrs, frames, units.ctypes.data))
         else:
             m = check_block_modes(modes, frames, self.channels)
@@ -868,6 +910,42 @@ def check_block_modes(modes, frames, channels):
                 raise ValueError('%s: %s field of mode byte 0x%02x is %d, not 0 or %d' % (where, name, b, f, other))
         raise ValueError('%s: bits 6-7 of mode byte 0x%02x are set' % (where, b))
     return m
+
+
+# ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----
+MAX_BIAS_PALETTE = 8
+
+
+def palette_array(c_options):
+    """capi.EncodeOptions instances -> the contiguous array c1_encode_biases_* take"""
+    arr = (capi.EncodeOptions * max(len(c_options), 1))()
+    for k, o in enumerate(c_options):
+        C.memmove(C.byref(arr[k]), C.byref(o), C.sizeof(capi.EncodeOptions))
+    return arr
+
+
+def bias_palette(biases, frames, channels, options=None):
+    """biases: `frames` values (every channel of a frame takes the frame's) or frames * channels ([frames, nch] or flat,
+    frame-major) -> (palette array, uint8 index [frames * channels]).  The palette holds the distinct values in ascending
+    order, each an EncoderOptions of `options`' other values with that allocationBias (so each is range-checked as
+    allocationBias is); more than MAX_BIAS_PALETTE distinct values raise ValueError."""
+    b = np.ascontiguousarray(biases, dtype=np.float64).reshape(-1)
+    if b.size == frames and channels != 1:
+        b = np.repeat(b, channels)
+    if b.size != frames * channels:
+        raise ValueError('biases must hold frames = %d or frames * channels = %d values, got %d' % (frames, frames * channels, b.size))
+    if np.isnan(b).any():
+        raise ValueError('biases must not be NaN')
+    values, index = (np.unique(b, return_inverse=True) if b.size else (np.array([1.0]), np.zeros(0, dtype=np.int64)))
+    if len(values) > MAX_BIAS_PALETTE:
+        raise ValueError('at most %d distinct allocation biases per call, got %d' % (MAX_BIAS_PALETTE, len(values)))
+    base = dict(options.values) if options is not None else {}
+    entries = []
+    for v in values:
+        o = EncoderOptions(base)
+        o.set_value('allocationBias', float(v))
+        entries.append(o.to_c())
+    return palette_array(entries), np.ascontiguousarray(index.reshape(-1), dtype=np.uint8)
 
 
 def aea_header(title='', frame_count=0, channel_count=1):

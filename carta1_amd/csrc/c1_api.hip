@@ -453,6 +453,13 @@ struct c1_ctx {
   double *d_feat[2] = {nullptr, nullptr};
   uint8_t *d_modes[2] = {nullptr, nullptr};
   uint32_t *d_lists[2] = {nullptr, nullptr};
+  // allocation bias per unit (c1_encode_biases_device): the palette's tables in device form, the tables uploaded last, and the
+  // unit lists of one chunk ([0, 8) counts, then one list per entry); all allocated on first use
+  C1DevEncOpts *d_palette = nullptr;
+  double pal_tables[C1_MAX_BIAS_PALETTE][64];
+  int pal_n = 0;
+  uint32_t *d_pal_lists = nullptr;
+  int64_t pal_entries = 0;
   // Tail overlap: the exact redo of a speculative chunk -- short lists, latency-bound launches -- runs on
   // s_tail while the next chunk's (or, on a context that owns its stream, the next call's) main kernels run on the
   // context's stream; the two chunks work on different halves of the workspace.  ev_main[p] / ev_tail[p]: main part /
@@ -536,6 +543,9 @@ void free_workspace(c1_ctx *ctx) {
     ctx->d_bands[p] = nullptr; ctx->d_feat[p] = nullptr; ctx->d_modes[p] = nullptr; ctx->d_lists[p] = nullptr;
   }
   ctx->det_units = 0;
+  if (ctx->d_pal_lists) (void)hipFree(ctx->d_pal_lists);
+  ctx->d_pal_lists = nullptr;
+  ctx->pal_entries = 0;
 }
 
 int ensure_detect_workspace(c1_ctx *ctx, int64_t units) {
@@ -638,6 +648,84 @@ int upload_opts(c1_ctx *ctx, const c1_encode_options *opts) {
   return C1_OK;
 }
 
+// One call's palette (c1_encode_biases_*): entries on the device, the index bytes of the call's units (device memory)
+struct PaletteCall {
+  int n;
+  const uint8_t *index;
+};
+
+// The palette's tables in device form.  Of an entry only what derives from its biased scale factors reaches a kernel (the
+// allocation chain reads nothing else), so only the tables are compared with what was uploaded last; a change waits for the
+// kernels that may still read the old ones, as upload_opts does.  An invalid table: C1_ERR_ARG naming the entry
+// host only: the size, every entry's table, and -- call_fields: the entries' threshold and block modes decide (a batch call
+// without given modes) -- those fields of every entry, which must then agree (threshold bit for bit)
+int check_palette(const char *what, const c1_encode_options *palette, int n, bool call_fields) {
+  if (n < 1 || n > C1_MAX_BIAS_PALETTE) return fail(C1_ERR_ARG, "%s: n_palette = %d is outside 1..%d", what, n, C1_MAX_BIAS_PALETTE);
+  if (!palette) return fail(C1_ERR_ARG, "%s: palette is NULL", what);
+  std::unique_ptr<C1DevEncOpts> d(new C1DevEncOpts);
+  for (int k = 0; k < n; k++) {
+    c1_encode_options o = palette[k];
+    if (!call_fields) {
+      o.transient_threshold = 1.0;
+      o.fixed_block_modes[0] = o.fixed_block_modes[1] = o.fixed_block_modes[2] = -1;
+    }
+    const int rc = build_encode_opts(o, d.get());
+    if (rc) { const std::string inner = g_error; return fail(rc, "%s: palette entry %d: %s", what, k, inner.c_str()); }
+    if (call_fields && k > 0) {
+      if (memcmp(&palette[k].transient_threshold, &palette[0].transient_threshold, sizeof(double)) != 0)
+        return fail(C1_ERR_ARG, "%s: palette entry %d: transient_threshold differs from entry 0's, and no modes are given", what, k);
+      if (memcmp(palette[k].fixed_block_modes, palette[0].fixed_block_modes, sizeof palette[0].fixed_block_modes) != 0)
+        return fail(C1_ERR_ARG, "%s: palette entry %d: fixed_block_modes differ from entry 0's, and no modes are given", what, k);
+    }
+  }
+  return C1_OK;
+}
+
+int upload_palette(c1_ctx *ctx, const char *what, const c1_encode_options *palette, int n) {
+  bool same = ctx->d_palette && ctx->pal_n >= n;
+  for (int k = 0; k < n && same; k++) same = memcmp(ctx->pal_tables[k], palette[k].biased_scale_factors, sizeof ctx->pal_tables[k]) == 0;
+  if (same) return C1_OK;
+  std::unique_ptr<C1DevEncOpts[]> h(new C1DevEncOpts[C1_MAX_BIAS_PALETTE]);
+  for (int k = 0; k < n; k++) {
+    c1_encode_options o = palette[k];
+    o.transient_threshold = 1.0;                           // the call fields of an entry never reach a kernel
+    o.fixed_block_modes[0] = o.fixed_block_modes[1] = o.fixed_block_modes[2] = -1;
+    const int rc = build_encode_opts(o, &h[k]);
+    if (rc) { const std::string inner = g_error; return fail(rc, "%s: palette entry %d: %s", what, k, inner.c_str()); }
+  }
+  int jr = join_tail(ctx);
+  if (jr) return jr;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!ctx->d_palette) HIP_TRY(hipMalloc(&ctx->d_palette, C1_MAX_BIAS_PALETTE * sizeof(C1DevEncOpts)));
+  ctx->pal_n = 0;
+  HIP_TRY(hipMemcpy(ctx->d_palette, h.get(), (size_t)n * sizeof(C1DevEncOpts), hipMemcpyHostToDevice));
+  for (int k = 0; k < n; k++) memcpy(ctx->pal_tables[k], palette[k].biased_scale_factors, sizeof ctx->pal_tables[k]);
+  ctx->pal_n = n;
+  return C1_OK;
+}
+
+// unit lists of one chunk: 8 counts, then n lists of `units` entries
+int ensure_palette_lists(c1_ctx *ctx, int64_t units, int n) {
+  const int64_t entries = units * n;
+  if (entries <= ctx->pal_entries) return C1_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  if (ctx->d_pal_lists) (void)hipFree(ctx->d_pal_lists);
+  ctx->d_pal_lists = nullptr; ctx->pal_entries = 0;
+  HIP_TRY(hipMalloc(&ctx->d_pal_lists, ((size_t)entries + 8) * sizeof(uint32_t)));
+  ctx->pal_entries = entries;
+  return C1_OK;
+}
+
+// the first index byte that is not below n: C1_ERR_ARG naming frame and channel (of two)
+int check_index_bytes(const char *what, const uint8_t *index, int64_t frames, int channels, int n) {
+  for (int64_t i = 0; i < frames * channels; i++) {
+    if (index[i] < n) continue;
+    if (channels == 2) return fail(C1_ERR_ARG, "%s: frame %lld, channel %d: bias index %d is not below n_palette = %d", what, (long long)(i / 2), (int)(i & 1), (int)index[i], n);
+    return fail(C1_ERR_ARG, "%s: frame %lld: bias index %d is not below n_palette = %d", what, (long long)i, (int)index[i], n);
+  }
+  return C1_OK;
+}
+
 hipEvent_t take_event(c1_ctx *ctx) {
   if (!ctx->event_pool.empty()) {
     hipEvent_t e = ctx->event_pool.back();
@@ -719,7 +807,8 @@ int check_mode_bytes(const char *what, const uint8_t *modes, int64_t frames, int
 // else can enqueue on that stream, and every other entry point joins first)
 int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                        const c1_encode_options *opts, uint8_t *units, float *bands, float *coefs_tap,
-                       uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr) {
+                       uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr,
+                       const PaletteCall *pal = nullptr) {
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx, false);
   if (rc) return rc;
@@ -742,6 +831,9 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect);
   if ((rc = ensure_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
   if (detect && (rc = ensure_detect_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
+  // pal (c1_encode_biases_device): the allocation of every chunk runs once per palette entry over that entry's units, from
+  // the tables upload_palette left in d_palette; analysis and packing do not read the bias and run as without it
+  if (pal && (rc = ensure_palette_lists(ctx, std::min(frames, chunk) * channels, pal->n))) return rc;
   if (taps && (!coefs_tap || !side_tap || !alloc_tap)) return fail(C1_ERR_ARG, "coefs, side and alloc taps must be given together");
   if (taps && frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "stage taps are not chunked: at most %lld frames per call", (long long)kMaxChunkFrames);
   // Two-stage software pipeline over chunks: the analysis of chunk i+1 (fp64-VALU bound) runs on one
@@ -751,7 +843,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
                               opts->fixed_block_modes[2] == 0 && !getenv("C1_NO_FAST_LONG");
   const bool all_short_modes = !detect && opts->fixed_block_modes[0] != 0 && opts->fixed_block_modes[1] != 0 &&
                                opts->fixed_block_modes[2] != 0;
-  bool speculate = (all_long_modes || all_short_modes) && !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
+  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
   bool quantize32 = !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;   // exact coefficients, binary32 quantization with the guard (below)
   static const bool det_spec_env_off = getenv("C1_DETECT_SPEC") && atoi(getenv("C1_DETECT_SPEC")) == 0;   // experiments: exact detector, the rest as usual
   bool detect_spec = detect && !given_modes && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
@@ -903,7 +995,10 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       HIP_TRY(hipEventRecord(ctx->ev_ana[p], sA));
       HIP_TRY(hipStreamWaitEvent(sB, ctx->ev_ana[p], 0));
     }
-    { ScopedTiming t(ctx, K_ALLOCATE, sB); c1k_launch_allocate(L, sB); }
+    if (pal) {
+      ScopedTiming t(ctx, K_ALLOCATE, sB);
+      c1k_launch_allocate_palette(L, ctx->d_palette, pal->n, pal->index + f0 * channels, ctx->d_pal_lists, ctx->d_pal_lists + 8, n * channels, sB);
+    } else { ScopedTiming t(ctx, K_ALLOCATE, sB); c1k_launch_allocate(L, sB); }
     if (L.units && quantize32) {
       // The coefficients are the reference's, and still the quantization need not be done in binary64: the packing
       // kernel of the speculative path with a bound of zero forms |x| norm + 0.5 in binary32 and accepts a mantissa only
@@ -1149,6 +1244,7 @@ int c1_ctx_destroy(c1_ctx *ctx) {
   for (auto e : ctx->event_pool) hipEventDestroy(e);
   if (ctx->d_tables) hipFree(ctx->d_tables);
   if (ctx->d_opts) hipFree(ctx->d_opts);
+  if (ctx->d_palette) hipFree(ctx->d_palette);
   if (ctx->d_spec_totals) hipFree(ctx->d_spec_totals);
   (void)hipDeviceSynchronize();
   free_workspace(ctx);
@@ -2225,6 +2321,65 @@ int c1_encode_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, in
   return C1_OK;
 }
 
+int c1_encode_biases_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                            const c1_encode_options *palette, int n_palette, const uint8_t *bias_index, const uint8_t *modes,
+                            uint8_t *units) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_palette("c1_encode_biases_device", palette, n_palette, modes == nullptr))) return rc;
+  if (frames > 0 && (!bias_index || !units)) return fail(C1_ERR_ARG, "bias_index or units is NULL");
+  if ((rc = upload_palette(ctx, "c1_encode_biases_device", palette, n_palette))) return rc;
+  // what analysis and packing read of the options: entry 0's (with given modes neither threshold nor fixed modes are read)
+  c1_encode_options base = palette[0];
+  if (modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  const PaletteCall pc = {n_palette, bias_index};
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            frames > 0 ? modes : nullptr, &pc);
+}
+
+int c1_encode_biases_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                           const c1_encode_options *palette, int n_palette, const uint8_t *bias_index, const uint8_t *modes,
+                           uint8_t *units) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_palette("c1_encode_biases_batch", palette, n_palette, modes == nullptr))) return rc;
+  if (frames == 0) return C1_OK;
+  if (!pcm || !units || !bias_index) return fail(C1_ERR_ARG, "pcm, bias_index or units is NULL");
+  for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  if ((rc = check_index_bytes("c1_encode_biases_batch", bias_index, frames, channels, n_palette))) return rc;   // before any device work
+  if (modes && (rc = check_mode_bytes("c1_encode_biases_batch", modes, frames, channels))) return rc;
+  // one copy in, the device call, one copy out
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  const size_t unit_bytes = (size_t)frames * channels * C1_UNIT_BYTES, byte_bytes = (size_t)frames * channels;
+  const size_t unit_off = (ch_bytes * channels + 255) & ~(size_t)255, index_off = (unit_off + unit_bytes + 255) & ~(size_t)255,
+               mode_off = (index_off + byte_bytes + 255) & ~(size_t)255;
+  if ((rc = ensure_io(ctx, mode_off + byte_bytes))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_index = (uint8_t *)ctx->d_io + index_off, *d_modes = (uint8_t *)ctx->d_io + mode_off;
+  HIP_TRY(hipMemcpyAsync(d_index, bias_index, byte_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, byte_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_biases_device(ctx, dptr, channels, frames, halo_frames, palette, n_palette, d_index, modes ? d_modes : nullptr, d_units))) return rc;
+  HIP_TRY(hipMemcpyAsync(units, d_units, unit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 int c1_decode_device(c1_ctx *ctx, const uint8_t *units, int channels, int64_t frames, int halo_units,
                      float *const *pcm) {
   CTX_GUARD(ctx);
@@ -2650,6 +2805,7 @@ struct c1_enc_stream {
   float *d_buf = nullptr;
   uint8_t *d_units = nullptr;
   uint8_t *d_given = nullptr;      // mode bytes of a push with given modes (c1_enc_stream_push_modes), cap_frames * channels
+  uint8_t *d_bias = nullptr;       // bias index bytes of a push with a palette (c1_enc_stream_push_biases), cap_frames * channels
   int64_t cap_frames = 0;
   int64_t pushed = 0;              // frames per channel encoded so far
   EncHistory hist = HIST_PREV;     // where the detection history of the next frame lives (same for every channel)
@@ -2713,7 +2869,8 @@ int enc_stream_bands(c1_enc_stream *s, const float *const *pcm, int64_t frames, 
 // frames of history before it.  The reference's stages on the device, channel by channel: bands of t-1 and t (halo 1),
 // blockSelectorStage against the stored bands or a fresh pool's zeros, mdctStage with t-1's bands as the overlap,
 // quantizationStage, serializeFrame -> units[c * 212].
-int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *units) {
+// per_channel: when not null, channel c's allocation runs under per_channel[c] (the stream's options with another bias table)
+int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *units, const c1_encode_options *per_channel = nullptr) {
   c1_ctx *ctx = s->ctx;
   EncSwitchScratch &w = s->sw;
   const int C = s->channels;
@@ -2747,6 +2904,7 @@ int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *
     L.work_count = w.work1;
     L.work_list = w.work1 + 4;
     L.sel_list = w.work1 + 4 + 7;
+    if (per_channel && (rc = upload_opts(ctx, &per_channel[c]))) return rc;
     c1k_launch_allocate(L, ctx->stream);
     c1k_launch_stage_fields(ctx->d_tables, w.coef1, modes, w.side1, w.alloc1, 1, w.nbfu, w.sfi, w.wl, w.q, ctx->stream);
     c1k_launch_pack_units(w.nbfu, modes, w.sfi, w.wl, w.q, 1, units + (size_t)c * C1_UNIT_BYTES, ctx->stream);
@@ -2883,7 +3041,8 @@ int enc_stream_freeze_history(c1_enc_stream *s) {
   return C1_OK;
 }
 
-int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units);
+int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
+                         const c1_encode_options *palette = nullptr, int n_palette = 0, const uint8_t *bias_index = nullptr);
 }  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
@@ -2933,11 +3092,22 @@ int c1_enc_stream_push_modes(c1_enc_stream *s, const float *const *pcm, int64_t 
   return enc_stream_push_impl(s, pcm, frames, modes, units);
 }
 
+int c1_enc_stream_push_biases(c1_enc_stream *s, const float *const *pcm, int64_t frames, const c1_encode_options *palette,
+                              int n_palette, const uint8_t *bias_index, const uint8_t *modes, uint8_t *units) {
+  int rc = check_palette("c1_enc_stream_push_biases", palette, n_palette, false);
+  if (rc) return rc;
+  if (!bias_index && frames > 0) return fail(C1_ERR_ARG, "bias_index is NULL");
+  return enc_stream_push_impl(s, pcm, frames, modes, units, palette, n_palette, bias_index);
+}
+
 namespace {
 // modes null: the stream's options decide.  Else the frames behave as if the options had been switched to fixed block modes
 // for them, frame by frame and channel by channel, and back afterwards: the detector does not run, and on a stream under
-// detection its history stays where c1_enc_stream_set_options would have frozen it
-int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units) {
+// detection its history stays where c1_enc_stream_set_options would have frozen it.
+// palette non-null (c1_enc_stream_push_biases): unit u allocates under the table of palette[bias_index[u]] instead of the
+// stream's; nothing else of the entries is read, and the stream's options and state are as after the same push without it
+int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
+                         const c1_encode_options *palette, int n_palette, const uint8_t *bias_index) {
   if (!s) return fail(C1_ERR_ARG, "stream is NULL");
   c1_ctx *ctx = s->ctx;
   CTX_GUARD(ctx);
@@ -2948,7 +3118,9 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   if (!pcm || !units) return fail(C1_ERR_ARG, "pcm or units is NULL");
   for (int c = 0; c < s->channels; c++)
     if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
-  if (modes && (rc = check_mode_bytes("c1_enc_stream_push_modes", modes, frames, s->channels))) return rc;   // the stream is as it was
+  if (palette && (rc = check_index_bytes("c1_enc_stream_push_biases", bias_index, frames, s->channels, n_palette))) return rc;
+  if (modes && (rc = check_mode_bytes(palette ? "c1_enc_stream_push_biases" : "c1_enc_stream_push_modes", modes, frames, s->channels))) return rc;   // the stream is as it was
+  if (palette && (rc = upload_palette(ctx, "c1_enc_stream_push_biases", palette, n_palette))) return rc;
   if (modes && opts_detect(s->opts) && s->state_frames == 0 && (rc = enc_stream_freeze_history(s))) return rc;
   const bool detect = !modes && opts_detect(s->opts);
   // frames of this push that are encoded from the explicit state: the first two after a restore, or the first under
@@ -2961,11 +3133,12 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   const bool switch_frame = from_state == 0 && detect && s->hist != HIST_PREV && s->pushed > 0;
   if (switch_frame && (rc = enc_stream_scratch(s))) return rc;
   if (frames > s->cap_frames) {
-    if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); hipFree(s->d_given); }
-    s->d_buf = nullptr; s->d_units = nullptr; s->d_given = nullptr; s->cap_frames = 0;
+    if (s->d_buf) { hipFree(s->d_buf); hipFree(s->d_units); hipFree(s->d_given); hipFree(s->d_bias); }
+    s->d_buf = nullptr; s->d_units = nullptr; s->d_given = nullptr; s->d_bias = nullptr; s->cap_frames = 0;
     HIP_TRY(hipMalloc(&s->d_buf, (size_t)s->channels * (frames + 2) * 512 * sizeof(float)));
     HIP_TRY(hipMalloc(&s->d_units, (size_t)s->channels * frames * C1_UNIT_BYTES));
     HIP_TRY(hipMalloc(&s->d_given, (size_t)s->channels * frames));
+    HIP_TRY(hipMalloc(&s->d_bias, (size_t)s->channels * frames));
     s->cap_frames = frames;
   }
   const size_t stride = (size_t)(s->cap_frames + 2) * 512;
@@ -2977,24 +3150,35 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
     dptr[c] = d + 1024;
   }
   if (modes) HIP_TRY(hipMemcpyAsync(s->d_given, modes, (size_t)frames * s->channels, hipMemcpyHostToDevice, ctx->stream));
+  if (palette) HIP_TRY(hipMemcpyAsync(s->d_bias, bias_index, (size_t)frames * s->channels, hipMemcpyHostToDevice, ctx->stream));
+  // the options frame f of channel c is encoded under where a kernel takes one set per launch: the stream's, with the given
+  // modes and the unit's palette table in their places
+  auto unit_opts = [&](int64_t f, int c) {
+    c1_encode_options one = s->opts;
+    if (modes) {
+      const int b = modes[f * s->channels + c];
+      one.fixed_block_modes[0] = b & 3; one.fixed_block_modes[1] = (b >> 2) & 3; one.fixed_block_modes[2] = (b >> 4) & 3;
+    }
+    if (palette) memcpy(one.biased_scale_factors, palette[bias_index[f * s->channels + c]].biased_scale_factors, sizeof one.biased_scale_factors);
+    return one;
+  };
   // the frames that are not encoded from the explicit state: the stream's options, or the given modes in their place
   auto encode_rest = [&](const float *const *p, int64_t first, int64_t n) {
     uint8_t *out = s->d_units + (size_t)first * s->channels * C1_UNIT_BYTES;
-    if (!modes) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
+    if (!modes && !palette) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
+    const PaletteCall pc = {n_palette, palette ? s->d_bias + (size_t)first * s->channels : nullptr};
     return encode_device_impl(ctx, p, s->channels, n, 2, &s->opts, out, nullptr, nullptr, nullptr, nullptr, false,
-                              s->d_given + (size_t)first * s->channels);
+                              modes ? s->d_given + (size_t)first * s->channels : nullptr, palette ? &pc : nullptr);
   };
   if (from_state > 0) {
     for (int64_t f = 0; f < from_state; f++) {   // frame after frame: each continues the pool the one before left
-      if (!modes) {
+      if (!modes && !palette) {
         if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
                                           s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state))) return rc;
         continue;
       }
       for (int c = 0; c < s->channels; c++) {    // the from-state kernel takes one triple per launch: a pool at a time
-        c1_encode_options one = s->opts;
-        const int b = modes[f * s->channels + c];
-        one.fixed_block_modes[0] = b & 3; one.fixed_block_modes[1] = (b >> 2) & 3; one.fixed_block_modes[2] = (b >> 4) & 3;
+        const c1_encode_options one = unit_opts(f, c);
         if ((rc = encode_from_states_impl(ctx, 1, dptr[c] + f * 512, (int64_t)stride, s->d_state + (size_t)c * kEncStateFloats, &one,
                                           s->d_units + (size_t)(f * s->channels + c) * C1_UNIT_BYTES,
                                           s->d_state + (size_t)c * kEncStateFloats))) return rc;
@@ -3006,12 +3190,12 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
       if ((rc = encode_rest(rest, from_state, frames - from_state))) return rc;
     }
   } else if (switch_frame) {
-    if ((rc = enc_stream_switch_frame(s, dptr, s->d_units))) return rc;
+    const c1_encode_options per_channel[C1_MAX_CHANNELS] = {unit_opts(0, 0), unit_opts(0, s->channels - 1)};
+    if ((rc = enc_stream_switch_frame(s, dptr, s->d_units, palette ? per_channel : nullptr))) return rc;
     if (frames > 1) {
       const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
       for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + 512;
-      if ((rc = encode_device_joined(ctx, rest, s->channels, frames - 1, 2, &s->opts, s->d_units + (size_t)s->channels * C1_UNIT_BYTES)))
-        return rc;
+      if ((rc = encode_rest(rest, 1, frames - 1))) return rc;
     }
   } else if ((rc = encode_rest(dptr, 0, frames))) {
     return rc;
@@ -3042,6 +3226,7 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (s->d_buf) hipFree(s->d_buf);
   if (s->d_units) hipFree(s->d_units);
   if (s->d_given) hipFree(s->d_given);
+  if (s->d_bias) hipFree(s->d_bias);
   if (s->d_sw_block) hipFree(s->d_sw_block);
   if (s->d_state) hipFree(s->d_state);
   delete s;

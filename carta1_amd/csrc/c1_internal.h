@@ -310,6 +310,11 @@ void c1k_launch_libm(int fn, const double *in, double *out, int64_t n, hipStream
 void c1k_launch_log2f_error(uint32_t first, uint64_t count, unsigned long long *out, hipStream_t stream);   // out: 2 x u64 on the device
 void c1k_launch_allocate(const C1EncodeLaunch &L, hipStream_t stream);
 void c1k_launch_alloc_tap(const C1EncodeLaunch &L, double *out, hipStream_t stream);   // test tap: totals and lower bounds of all candidates
+// the allocation bias per unit (c1_k_palette.hip): index = one byte per unit of L (device memory, any value: a byte >= n selects
+// entry 0), palette = n C1DevEncOpts on the device.  The units are sorted by entry into lists + k * stride (stride >= units,
+// counts[k] entries), then c1k_launch_allocate runs once per entry over its list, one chain after the other on `stream`
+void c1k_launch_allocate_palette(const C1EncodeLaunch &L, const C1DevEncOpts *palette, int n, const uint8_t *index, uint32_t *counts,
+                                 uint32_t *lists, int64_t stride, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -254,6 +254,46 @@ napi_value EncodeBatchModes(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// encodeBatchBiases(ctx, [Float32Array...], haloFrames, Float64Array(68 * n) palette, Uint8Array index, Uint8Array modes | null)
+// -> Uint8Array(frames*channels*212): c1_encode_biases_batch, n = 1..8 option sets laid out like `options` one after the other,
+// one palette index and (optionally) one mode byte per sound unit (frame-major, channels interleaved)
+napi_value EncodeBatchBiases(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_index = 0, n_modes = 0, n_pal = 0;
+  int32_t halo = 0;
+  void *index, *modes = nullptr, *pal;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_typed(env, argv[3], napi_float64_array, &pal, &n_pal) || !get_typed(env, argv[4], napi_uint8_array, &index, &n_index)) return nullptr;
+  if (n_pal == 0 || n_pal % 68 || n_pal / 68 > C1_MAX_BIAS_PALETTE) { napi_throw_range_error(env, nullptr, "palette must hold 1 to 8 option sets of 68 doubles"); return nullptr; }
+  napi_valuetype mt;
+  NAPI_OK(napi_typeof(env, argv[5], &mt));
+  const bool have_modes = mt != napi_null && mt != napi_undefined;
+  if (have_modes && !get_typed(env, argv[5], napi_uint8_array, &modes, &n_modes)) return nullptr;
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  if (n_index != (size_t)frames * ch.size() || (have_modes && n_modes != n_index)) { napi_throw_type_error(env, nullptr, "index and modes: one byte per frame and channel"); return nullptr; }
+  std::vector<c1_encode_options> palette(n_pal / 68);
+  const double *p64 = static_cast<const double *>(pal);
+  for (size_t k = 0; k < palette.size(); k++) {
+    memset(&palette[k], 0, sizeof palette[k]);
+    memcpy(palette[k].biased_scale_factors, p64 + 68 * k, 64 * sizeof(double));
+    palette[k].transient_threshold = p64[68 * k + 64];
+    for (int b = 0; b < 3; b++) palette[k].fixed_block_modes[b] = (int32_t)p64[68 * k + 65 + b];
+  }
+  uint8_t *units;
+  napi_value out = make_u8(env, (size_t)frames * ch.size() * C1_UNIT_BYTES, &units);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_biases_batch(ctx, p, (int)ch.size(), frames, halo, palette.data(), (int)palette.size(), static_cast<const uint8_t *>(index),
+                                        have_modes ? static_cast<const uint8_t *>(modes) : nullptr, units);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1053,6 +1093,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"allocPinned", nullptr, AllocPinned, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatchModes", nullptr, EncodeBatchModes, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeBatchBiases", nullptr, EncodeBatchBiases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

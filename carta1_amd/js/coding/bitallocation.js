@@ -12,7 +12,7 @@ const NUM_BFUS = 52
 
 // buildBiasedScaleFactorTable (:46-61) with this engine's Math.pow, as EncoderOptions.toNative builds it
 const biasedTables = new Map()
-function biasedTable(bias) {
+export function biasedTable(bias) {
   if (!biasedTables.has(bias)) {
     biasedTables.set(bias, Float64Array.from(SCALE_FACTORS, (sf) => (bias === 1 ? sf : Math.pow(sf, bias))))
   }

@@ -8,7 +8,8 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases } from '../native.js'
+import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
   const longest = Math.max(...channels.map((c) => c.length))
@@ -31,9 +32,37 @@ export async function encodeAeaPcm(channels, options = {}) {
   // options.blockModes (not in the reference): a Uint8Array of frames * channels mode bytes (m0 | m1 << 2 | m2 << 4, frame-major,
   // channels interleaved), frames = ceil(length / 512): every frame is encoded as the reference encodes it with fixedBlockModes
   // set to that frame's modes before the call; the detector does not run and devices is not used
-  const { title = 'encoded by carta1', devices, blockModes, ...encoderValues } = options
+  // options.allocationBiases (not in the reference): a Float64Array of frames (every channel of a frame takes the frame's) or
+  // frames * channels values (frame-major, channels interleaved): every frame is encoded as the reference encodes it with
+  // allocationBias set to that value before the call.  Each value is range-checked as allocationBias is; at most 8 distinct
+  // values per call (RangeError), their tables from this engine's Math.pow.  Combines with blockModes; devices is not used
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
+  let palette = null
+  let biasIndex = null
+  if (allocationBiases !== undefined && allocationBiases !== null) {
+    const units = frames * channels.length
+    if (!(allocationBiases instanceof Float64Array) || (allocationBiases.length !== frames && allocationBiases.length !== units)) {
+      throw new TypeError(`allocationBiases must be a Float64Array of frames = ${frames} or frames * channels = ${units} values`)
+    }
+    const probe = new EncoderOptions(encoderValues)
+    for (const b of allocationBiases) {
+      if (Number.isNaN(b)) throw new Error('Value for allocationBias must be a number, got NaN')
+      probe.setValue('allocationBias', b)
+    }
+    const values = Array.from(new Set(allocationBiases)).sort((x, y) => x - y)
+    if (values.length > 8) throw new RangeError(`at most 8 distinct allocation biases per call, got ${values.length}`)
+    const slot = new Map(values.map((v, k) => [v, k]))
+    const perFrame = allocationBiases.length === frames && channels.length > 1
+    biasIndex = Uint8Array.from({ length: units }, (_, u) => slot.get(allocationBiases[perFrame ? Math.floor(u / channels.length) : u]))
+    const base = encoderOptions.toNative()
+    palette = new Float64Array(68 * Math.max(values.length, 1))
+    for (let k = 0; k < Math.max(values.length, 1); k++) {
+      palette.set(base, 68 * k)
+      if (k < values.length) palette.set(biasedTable(values[k]), 68 * k)
+    }
+  }
   if (blockModes !== undefined && blockModes !== null &&
       (!(blockModes instanceof Uint8Array) || blockModes.length !== frames * channels.length)) {
     throw new TypeError(`blockModes must be a Uint8Array of frames * channels = ${frames * channels.length} mode bytes`)
@@ -41,7 +70,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && blockModes) {
+  if (frames > 0 && palette) {
+    image.set(encodeBatchBiases(padded, biasIndex, palette, blockModes || null), AEA_HEADER_SIZE)
+  } else if (frames > 0 && blockModes) {
     image.set(encodeBatchModes(padded, blockModes, encoderOptions.toNative()), AEA_HEADER_SIZE)
   } else if (frames > 0) {
     const where = Array.isArray(devices) && devices.length ? devices : context()

@@ -43,3 +43,11 @@ export function allocPinnedFloat32Array(length) {
 export function encodeBatchModes(channels, modes, nativeOptions, haloFrames = 0, ctx = context()) {
   return native().encodeBatchModes(ctx, channels, haloFrames, nativeOptions, modes)
 }
+
+// c1_encode_biases_batch on the default context: encode() with the allocation bias of every frame and channel taken from a
+// palette.  nativePalette: Float64Array(68 * n), n = 1 .. 8 results of EncoderOptions.toNative() one after the other; index:
+// Uint8Array of frames * channels palette indices (frame-major, channels interleaved); modes: null (detection or fixed modes as
+// the palette's entries say, which must then agree) or mode bytes as for encodeBatchModes.  Returns the units.
+export function encodeBatchBiases(channels, index, nativePalette, modes = null, haloFrames = 0, ctx = context()) {
+  return native().encodeBatchBiases(ctx, channels, haloFrames, nativePalette, index, modes)
+}

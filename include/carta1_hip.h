@@ -225,6 +225,43 @@ int c1_encode_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, i
 int c1_encode_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                           const c1_encode_options *opts, const uint8_t *modes /* host, frames*channels */, uint8_t *units);
 
+/* ---- encode with the allocation bias supplied per frame and channel: encode() with options.allocationBias set before every
+ *      frame (quantizationStage reads it on every call, encoder.js:393) -----------------------------------------------------
+ * palette: n_palette (1 .. C1_MAX_BIAS_PALETTE) option sets in HOST memory; bias_index: one byte per sound unit, unit index =
+ * frame * channels + channel.  Unit u is encoded exactly as the reference's closure for that channel encodes the frame when
+ * options.allocationBias was set, before that call, to the bias behind palette[bias_index[u]].biased_scale_factors.  The bias
+ * reaches the bit allocation alone (analysis does not read it, and quantize uses SCALE_FACTORS), so nothing is carried from
+ * frame to frame by it: everything else is as in c1_encode_modes_* (modes given) or c1_encode_device (modes NULL).  Every
+ * table an encode call accepts is accepted in every entry; an invalid one returns C1_ERR_ARG naming the entry.  Eight entries
+ * are what the host keeps derived tables for, so a repeated palette rebuilds nothing.
+ * modes non-NULL: the bytes and the domain of c1_encode_modes_*; the entries' transient_threshold and fixed_block_modes are
+ * not read.  modes NULL: transient detection or fixed modes as the entries say -- all entries must then agree in
+ * fixed_block_modes and in the bit pattern of transient_threshold (else C1_ERR_ARG naming the first entry that differs), and
+ * are validated as every encode call validates them.
+ * The call always takes the exact analysis (given modes: the front end of c1_encode_modes_device; else the exact kernels of
+ * c1_encode_device, the detector as there); unless speculation is 0 the quantization runs in binary32 behind its guard.  The
+ * bytes do not depend on the speculation mode, the run length or on how the call is cut into chunks (C1_CHUNK_FRAMES,
+ * C1_PIPELINE, C1_OVERLAP).  The units of a chunk are sorted by entry into lists (4 bytes per unit and entry of workspace) and
+ * the allocation kernels run once per entry over its list, one chain after the other; c1_ctx_kernel_ms counts the sorting and
+ * all chains under "allocate".
+ *
+ * device-resident: pcm[c] (16-byte aligned), bias_index, modes and units are DEVICE pointers; asynchronous on the context's
+ * stream like c1_encode_device and chunked like c1_encode_modes_device; frames 0 .. 2^27 per channel.  A palette whose tables
+ * differ from the ones uploaded last synchronises the stream on the host, as a change of options does.  The index bytes are
+ * NOT checked: a byte >= n_palette selects entry 0, so no access leaves the buffers; for such a byte the unit's content is
+ * unspecified and every other unit is unaffected.  Mode bytes as for c1_encode_modes_device. */
+#define C1_MAX_BIAS_PALETTE 8
+int c1_encode_biases_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                            const c1_encode_options *palette /* HOST, n_palette entries */, int n_palette,
+                            const uint8_t *bias_index /* device, frames*channels */,
+                            const uint8_t *modes /* device, frames*channels, or NULL */, uint8_t *units);
+/* host-resident, synchronous: the palette, every index byte (< n_palette) and every mode byte are validated before any device
+ * work -- a bad byte returns C1_ERR_ARG naming the frame and the channel (of two), and nothing is written -- then one copy in,
+ * the device call, one copy out.  frames 0 .. 2^22 per channel. */
+int c1_encode_biases_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                           const c1_encode_options *palette, int n_palette, const uint8_t *bias_index /* host */,
+                           const uint8_t *modes /* host, or NULL */, uint8_t *units /* host */);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
@@ -284,6 +321,15 @@ int c1_enc_stream_set_options(c1_enc_stream *s, const c1_encode_options *opts);
  * under c1_enc_stream_set_options.  On a stream under fixed modes the frames simply take the given modes. */
 int c1_enc_stream_push_modes(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
                              const uint8_t *modes /* host, frames*channels */, uint8_t *units /* host, frames*channels*212 */);
+/* c1_enc_stream_push (modes NULL) or c1_enc_stream_push_modes (modes given) with the allocation bias of every pushed unit taken
+ * from a palette, as in c1_encode_biases_batch and validated the same way (an invalid call leaves the stream as it was).  Of
+ * the entries only biased_scale_factors is read: with modes NULL the stream's own options decide threshold and block modes.
+ * The stream's options do not change, and the bias is not state: c1_enc_stream_get_state afterwards is what it is after the
+ * same push without a palette.  The frames a stream encodes one at a time (the first two after c1_enc_stream_set_state, the
+ * first after a switch back to detection) allocate under their own unit's entry too. */
+int c1_enc_stream_push_biases(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
+                              const c1_encode_options *palette, int n_palette, const uint8_t *bias_index /* host, frames*channels */,
+                              const uint8_t *modes /* host, frames*channels, or NULL */, uint8_t *units /* host */);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
