@@ -247,6 +247,31 @@ class Context:
                                                       index.ctypes.data, None if m is None else m.ctypes.data, units.ctypes.data))
         return units
 
+    def encode_best_bias(self, channels, biases, modes=None, options=None, halo_frames=0, return_distortion=False):
+        """encode() with the allocation bias of every sound unit chosen among `biases` by least coding error: the sum over the
+        unit's 512 MDCT coefficients of (c - d)^2, d what the decoder's dequantizationStage makes of the unit (c1_encode_best_bias_batch).
+        biases: 1 .. MAX_BIAS_PALETTE distinct values in the caller's order (choice indexes it), or EncoderOptions that carry
+        explicit tables (candidate_palette).  modes, options, halo_frames as for encode_biases().  Returns (units, choice uint8
+        [units]), and with return_distortion (units, choice, distortion float64 [units, n], energy float64 [units]); units of
+        one candidate are what encode() / encode_modes() give under it."""
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = max(n // 512 - halo_frames, 0)
+        palette, count = candidate_palette(biases, options)
+        m = None if modes is None else check_block_modes(modes, frames, len(chans))
+        units = np.zeros((frames * len(chans), 212), dtype=np.uint8)
+        choice = np.zeros(frames * len(chans), dtype=np.uint8)
+        dist = np.zeros((frames * len(chans), count), dtype=np.float64) if return_distortion else None
+        energy = np.zeros(frames * len(chans), dtype=np.float64) if return_distortion else None
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_best_bias_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, palette, count,
+                                                         None if m is None else m.ctypes.data, units.ctypes.data, choice.ctypes.data,
+                                                         None if dist is None else dist.ctypes.data,
+                                                         None if energy is None else energy.ctypes.data))
+        return (units, choice, dist, energy) if return_distortion else (units, choice)
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -284,6 +309,17 @@ class Context:
         capi.check(capi.load().c1_encode_biases_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                        palette, len(palette_options), C.c_void_p(index_ptr),
                                                        C.c_void_p(modes_ptr) if modes_ptr else None, C.c_void_p(units_ptr)))
+
+    def encode_best_bias_device(self, pcm_ptrs, frames, palette_options, units_ptr=None, choice_ptr=None, distortion_ptr=None,
+                                energy_ptr=None, modes_ptr=None, halo_frames=0):
+        """c1_encode_best_bias_device: palette_options = 1 .. MAX_BIAS_PALETTE EncoderOptions; outputs on the device, each may be
+        None (units_ptr None: measure only), not all; distortion is float64 [units, n], energy float64 [units], choice uint8
+        [units]; modes_ptr = mode bytes on the device as for encode_modes_device, or None."""
+        palette = palette_array([o.to_c() for o in palette_options])
+        vp = lambda p: C.c_void_p(p) if p else None
+        capi.check(capi.load().c1_encode_best_bias_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                          palette, len(palette_options), vp(modes_ptr), vp(units_ptr), vp(choice_ptr),
+                                                          vp(distortion_ptr), vp(energy_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -946,6 +982,32 @@ def bias_palette(biases, frames, channels, options=None):
         o.set_value('allocationBias', float(v))
         entries.append(o.to_c())
     return palette_array(entries), np.ascontiguousarray(index.reshape(-1), dtype=np.uint8)
+
+
+def candidate_palette(biases, options=None):
+    """the candidates of Context.encode_best_bias -> (palette array, count).  biases: 1 .. MAX_BIAS_PALETTE entries in the
+    caller's order, each a number (an EncoderOptions of `options`' other values with that allocationBias, range-checked as
+    allocationBias is) or an EncoderOptions (taken as it is: it may carry an explicit table).  ValueError for none, for more
+    than MAX_BIAS_PALETTE, for NaN and for a numeric bias given twice."""
+    items = list(biases)
+    if not 1 <= len(items) <= MAX_BIAS_PALETTE:
+        raise ValueError('between 1 and %d candidate biases per call, got %d' % (MAX_BIAS_PALETTE, len(items)))
+    base = dict(options.values) if options is not None else {}
+    entries, seen = [], set()
+    for v in items:
+        if isinstance(v, EncoderOptions):
+            entries.append(v.to_c())
+            continue
+        v = float(v)
+        if v != v:
+            raise ValueError('candidate biases must not be NaN')
+        if v in seen:
+            raise ValueError('candidate bias %r is given twice' % v)
+        seen.add(v)
+        o = EncoderOptions(base)
+        o.set_value('allocationBias', v)
+        entries.append(o.to_c())
+    return palette_array(entries), len(entries)
 
 
 def aea_header(title='', frame_count=0, channel_count=1):

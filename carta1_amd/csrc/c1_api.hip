@@ -411,8 +411,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_CHOOSE, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts", "choose"};
 
 }  // namespace
 
@@ -460,6 +460,10 @@ struct c1_ctx {
   int pal_n = 0;
   uint32_t *d_pal_lists = nullptr;
   int64_t pal_entries = 0;
+  // the bias chosen per unit (c1_encode_best_bias_device): one allocation record per unit and palette entry of one chunk, entry
+  // k's records at d_trial + k * trial_units * kAllocBytes; allocated on first use
+  uint8_t *d_trial = nullptr;
+  int64_t trial_units = 0, trial_n = 0;
   // Tail overlap: the exact redo of a speculative chunk -- short lists, latency-bound launches -- runs on
   // s_tail while the next chunk's (or, on a context that owns its stream, the next call's) main kernels run on the
   // context's stream; the two chunks work on different halves of the workspace.  ev_main[p] / ev_tail[p]: main part /
@@ -546,6 +550,9 @@ void free_workspace(c1_ctx *ctx) {
   if (ctx->d_pal_lists) (void)hipFree(ctx->d_pal_lists);
   ctx->d_pal_lists = nullptr;
   ctx->pal_entries = 0;
+  if (ctx->d_trial) (void)hipFree(ctx->d_trial);
+  ctx->d_trial = nullptr;
+  ctx->trial_units = ctx->trial_n = 0;
 }
 
 int ensure_detect_workspace(c1_ctx *ctx, int64_t units) {
@@ -594,15 +601,19 @@ int ensure_workspace(c1_ctx *ctx, int64_t units) {
 // buffers; a workspace that is already large enough is used as it is.
 constexpr size_t kWsBytesPerUnit = 512 * sizeof(float) + kSideBytes + kAllocBytes + kCandidateBytes + 8 * sizeof(uint32_t) + kEpsFloats * sizeof(float) + 4 * sizeof(uint32_t);
 constexpr size_t kDetectWsBytesPerUnit = 512 * sizeof(float) + kFeatureWsDoubles * sizeof(double) + 1 + 3 * sizeof(uint32_t);
-int64_t chunk_for_call(c1_ctx *ctx, int64_t frames, int channels, bool detect) {
+// trial_n > 0 (c1_encode_best_bias_device): that many trial allocation records per unit on top (one set: only the second half
+// of the pipeline touches them)
+int64_t chunk_for_call(c1_ctx *ctx, int64_t frames, int channels, bool detect, int trial_n = 0) {
   const int64_t want = std::min(frames, ctx->chunk_frames);
-  if (want * channels <= ctx->ws_units && (!detect || want * channels <= ctx->det_units)) return want;
+  const bool trial_fits = trial_n == 0 || (want * channels <= ctx->trial_units && trial_n <= ctx->trial_n);
+  if (want * channels <= ctx->ws_units && (!detect || want * channels <= ctx->det_units) && trial_fits) return want;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return std::min<int64_t>(want, 1048576); }
   const size_t sets = (ctx->pipeline || ctx->overlap) ? 2 : 1, det_sets = ctx->pipeline ? 2 : 1;
   size_t avail = free_b + (size_t)ctx->ws_units * kWsBytesPerUnit * sets;          // the present workspace is freed before it grows
   size_t per_unit = kWsBytesPerUnit * sets;
   if (detect) { avail += (size_t)ctx->det_units * kDetectWsBytesPerUnit * det_sets; per_unit += kDetectWsBytesPerUnit * det_sets; }
+  if (trial_n > 0) { avail += (size_t)ctx->trial_units * ctx->trial_n * kAllocBytes; per_unit += (size_t)trial_n * kAllocBytes; }
   const int64_t fit = (int64_t)((double)avail * 0.9 / (double)per_unit) / channels;
   return std::max<int64_t>(16, std::min(want, fit));
 }
@@ -716,6 +727,25 @@ int ensure_palette_lists(c1_ctx *ctx, int64_t units, int n) {
   return C1_OK;
 }
 
+// trial allocation records of one chunk: n planes of `units` records
+int ensure_trial_allocs(c1_ctx *ctx, int64_t units, int n) {
+  if (units <= ctx->trial_units && n <= ctx->trial_n) return C1_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  if (ctx->d_trial) (void)hipFree(ctx->d_trial);
+  ctx->d_trial = nullptr; ctx->trial_units = ctx->trial_n = 0;
+  const int64_t u = std::max(units, ctx->trial_units), planes = std::max<int64_t>(n, ctx->trial_n);
+  HIP_TRY(hipMalloc(&ctx->d_trial, (size_t)u * planes * kAllocBytes));
+  ctx->trial_units = u; ctx->trial_n = planes;
+  return C1_OK;
+}
+
+// One call of c1_encode_best_bias_device: the palette's size and the call's outputs (device memory, each may be null)
+struct BestBiasCall {
+  int n;
+  uint8_t *choice;
+  double *distortion, *energy;
+};
+
 // the first index byte that is not below n: C1_ERR_ARG naming frame and channel (of two)
 int check_index_bytes(const char *what, const uint8_t *index, int64_t frames, int channels, int n) {
   for (int64_t i = 0; i < frames * channels; i++) {
@@ -808,7 +838,7 @@ int check_mode_bytes(const char *what, const uint8_t *modes, int64_t frames, int
 int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                        const c1_encode_options *opts, uint8_t *units, float *bands, float *coefs_tap,
                        uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr,
-                       const PaletteCall *pal = nullptr) {
+                       const PaletteCall *pal = nullptr, const BestBiasCall *best = nullptr) {
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx, false);
   if (rc) return rc;
@@ -828,12 +858,15 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   // biased scale factors reach a kernel that runs
   const bool detect = given_modes || opts->fixed_block_modes[0] < 0;
   const bool taps = coefs_tap || side_tap || alloc_tap;
-  const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect);
+  const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect, best ? best->n : 0);
   if ((rc = ensure_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
   if (detect && (rc = ensure_detect_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
   // pal (c1_encode_biases_device): the allocation of every chunk runs once per palette entry over that entry's units, from
   // the tables upload_palette left in d_palette; analysis and packing do not read the bias and run as without it
   if (pal && (rc = ensure_palette_lists(ctx, std::min(frames, chunk) * channels, pal->n))) return rc;
+  // best (c1_encode_best_bias_device): the allocation of every chunk runs once per palette entry over ALL its units into that
+  // entry's trial records; k_choose_bias measures every (unit, entry) and leaves the winner's record where packing reads it
+  if (best && (rc = ensure_trial_allocs(ctx, std::min(frames, chunk) * channels, best->n))) return rc;
   if (taps && (!coefs_tap || !side_tap || !alloc_tap)) return fail(C1_ERR_ARG, "coefs, side and alloc taps must be given together");
   if (taps && frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "stage taps are not chunked: at most %lld frames per call", (long long)kMaxChunkFrames);
   // Two-stage software pipeline over chunks: the analysis of chunk i+1 (fp64-VALU bound) runs on one
@@ -843,7 +876,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
                               opts->fixed_block_modes[2] == 0 && !getenv("C1_NO_FAST_LONG");
   const bool all_short_modes = !detect && opts->fixed_block_modes[0] != 0 && opts->fixed_block_modes[1] != 0 &&
                                opts->fixed_block_modes[2] != 0;
-  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
+  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && !best && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
   bool quantize32 = !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;   // exact coefficients, binary32 quantization with the guard (below)
   static const bool det_spec_env_off = getenv("C1_DETECT_SPEC") && atoi(getenv("C1_DETECT_SPEC")) == 0;   // experiments: exact detector, the rest as usual
   bool detect_spec = detect && !given_modes && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
@@ -995,7 +1028,22 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       HIP_TRY(hipEventRecord(ctx->ev_ana[p], sA));
       HIP_TRY(hipStreamWaitEvent(sB, ctx->ev_ana[p], 0));
     }
-    if (pal) {
+    if (best) {
+      const int64_t trial_stride = ctx->trial_units * kAllocBytes;
+      {
+        ScopedTiming t(ctx, K_ALLOCATE, sB);
+        for (int k = 0; k < best->n; k++) {                      // one chain after the other: they share the candidate and work-list scratch
+          C1EncodeLaunch A = L;
+          A.opts = ctx->d_palette + k;
+          A.alloc = ctx->d_trial + (size_t)k * trial_stride;
+          c1k_launch_allocate(A, sB);
+        }
+      }
+      ScopedTiming t(ctx, K_CHOOSE, sB);
+      c1k_launch_choose_bias(L, ctx->d_trial, trial_stride, best->n, all_long, best->choice ? best->choice + f0 * channels : nullptr,
+                             best->distortion ? best->distortion + f0 * channels * best->n : nullptr,
+                             best->energy ? best->energy + f0 * channels : nullptr, sB);
+    } else if (pal) {
       ScopedTiming t(ctx, K_ALLOCATE, sB);
       c1k_launch_allocate_palette(L, ctx->d_palette, pal->n, pal->index + f0 * channels, ctx->d_pal_lists, ctx->d_pal_lists + 8, n * channels, sB);
     } else { ScopedTiming t(ctx, K_ALLOCATE, sB); c1k_launch_allocate(L, sB); }
@@ -2376,6 +2424,79 @@ int c1_encode_biases_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
   if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, byte_bytes, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = c1_encode_biases_device(ctx, dptr, channels, frames, halo_frames, palette, n_palette, d_index, modes ? d_modes : nullptr, d_units))) return rc;
   HIP_TRY(hipMemcpyAsync(units, d_units, unit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_encode_best_bias_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                               const c1_encode_options *palette, int n_palette, const uint8_t *modes, uint8_t *units,
+                               uint8_t *choice, double *distortion, double *energy) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_palette("c1_encode_best_bias_device", palette, n_palette, modes == nullptr))) return rc;
+  if (!units && !choice && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_best_bias_device: units, choice, distortion and energy are all NULL");
+  if ((rc = upload_palette(ctx, "c1_encode_best_bias_device", palette, n_palette))) return rc;
+  // what analysis and packing read of the options: entry 0's (with given modes neither threshold nor fixed modes are read)
+  c1_encode_options base = palette[0];
+  if (modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  const BestBiasCall bc = {n_palette, choice, distortion, energy};
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            frames > 0 ? modes : nullptr, nullptr, &bc);
+}
+
+int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                              const c1_encode_options *palette, int n_palette, const uint8_t *modes, uint8_t *units,
+                              uint8_t *choice, double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_palette("c1_encode_best_bias_batch", palette, n_palette, modes == nullptr))) return rc;
+  if (!units && !choice && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_best_bias_batch: units, choice, distortion and energy are all NULL");
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if (modes && (rc = check_mode_bytes("c1_encode_best_bias_batch", modes, frames, channels))) return rc;
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "c1_encode_best_bias_batch: no HIP device available; this library has no CPU path"); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), mode_off = up256(unit_off + n_units * C1_UNIT_BYTES), choice_off = up256(mode_off + n_units),
+               dist_off = up256(choice_off + n_units), energy_off = up256(dist_off + n_units * n_palette * sizeof(double));
+  if ((rc = ensure_io(ctx, energy_off + n_units * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_modes = (uint8_t *)ctx->d_io + mode_off, *d_choice = (uint8_t *)ctx->d_io + choice_off;
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off);
+  if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, n_units, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_best_bias_device(ctx, dptr, channels, frames, halo_frames, palette, n_palette, modes ? d_modes : nullptr,
+                                       units ? d_units : nullptr, choice ? d_choice : nullptr, distortion ? d_dist : nullptr,
+                                       energy ? d_energy : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_palette * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }

@@ -315,6 +315,14 @@ void c1k_launch_alloc_tap(const C1EncodeLaunch &L, double *out, hipStream_t stre
 // counts[k] entries), then c1k_launch_allocate runs once per entry over its list, one chain after the other on `stream`
 void c1k_launch_allocate_palette(const C1EncodeLaunch &L, const C1DevEncOpts *palette, int n, const uint8_t *index, uint32_t *counts,
                                  uint32_t *lists, int64_t stride, hipStream_t stream);
+// the allocation bias chosen per unit by least coding error (c1_k_choose.hip): trial = n_palette allocation records per unit of L,
+// entry k's at trial + k * trial_stride + unit * kAllocBytes (trial_stride >= units * kAllocBytes), as c1k_launch_allocate left
+// them with L.alloc pointed there.  Per unit: D(u, k) = sum (c - dequantize(quantize(c)))^2 and E(u) = sum c^2 in binary64 over
+// the 512 coefficients, choice = the smallest k of least D (a NaN never wins; all NaN: 0), and that entry's record copied to
+// L.alloc, where the packing kernels read it.  choice (units), distortion (units * n_palette, unit-major) and energy (units)
+// may each be null.  all_long: every unit has modes [0,0,0] (the side records' mode byte is not read)
+void c1k_launch_choose_bias(const C1EncodeLaunch &L, const uint8_t *trial, int64_t trial_stride, int n_palette, bool all_long,
+                            uint8_t *choice, double *distortion, double *energy, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

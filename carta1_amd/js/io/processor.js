@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -36,9 +36,37 @@ export async function encodeAeaPcm(channels, options = {}) {
   // frames * channels values (frame-major, channels interleaved): every frame is encoded as the reference encodes it with
   // allocationBias set to that value before the call.  Each value is range-checked as allocationBias is; at most 8 distinct
   // values per call (RangeError), their tables from this engine's Math.pow.  Combines with blockModes; devices is not used
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, ...encoderValues } = options
+  // options.allocationBiasCandidates (not in the reference): an array of 1 to 8 distinct allocationBias values: every sound unit
+  // is encoded under the candidate that leaves the least coding error, the sum over its 512 MDCT coefficients of the squared
+  // difference between the coefficient and what the decoder dequantizes (c1_encode_best_bias_batch).  Each value is
+  // range-checked as allocationBias is, their tables from this engine's Math.pow.  Combines with blockModes; mutually
+  // exclusive with allocationBiases (TypeError); devices is not used
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
+  const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
+  if (haveCandidates && allocationBiases !== undefined && allocationBiases !== null) {
+    throw new TypeError('allocationBiases and allocationBiasCandidates are mutually exclusive: give the bias of every frame, or the candidates to choose among')
+  }
+  let candidates = null
+  if (haveCandidates) {
+    const values = Array.from(allocationBiasCandidates)
+    if (!(Array.isArray(allocationBiasCandidates) || allocationBiasCandidates instanceof Float64Array) || values.length < 1 || values.length > 8) {
+      throw new RangeError(`allocationBiasCandidates must hold 1 to 8 values, got ${values.length}`)
+    }
+    const probe = new EncoderOptions(encoderValues)
+    for (const b of values) {
+      if (typeof b !== 'number' || Number.isNaN(b)) throw new Error(`Value for allocationBias must be a number, got ${b}`)
+      probe.setValue('allocationBias', b)
+    }
+    if (new Set(values).size !== values.length) throw new RangeError('allocationBiasCandidates must be distinct')
+    const base = encoderOptions.toNative()
+    candidates = new Float64Array(68 * values.length)
+    values.forEach((b, k) => {
+      candidates.set(base, 68 * k)
+      candidates.set(biasedTable(b), 68 * k)
+    })
+  }
   let palette = null
   let biasIndex = null
   if (allocationBiases !== undefined && allocationBiases !== null) {
@@ -70,7 +98,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && palette) {
+  if (frames > 0 && candidates) {
+    image.set(encodeBestBias(padded, candidates, blockModes || null).units, AEA_HEADER_SIZE)
+  } else if (frames > 0 && palette) {
     image.set(encodeBatchBiases(padded, biasIndex, palette, blockModes || null), AEA_HEADER_SIZE)
   } else if (frames > 0 && blockModes) {
     image.set(encodeBatchModes(padded, blockModes, encoderOptions.toNative()), AEA_HEADER_SIZE)

@@ -51,3 +51,21 @@ export function encodeBatchModes(channels, modes, nativeOptions, haloFrames = 0,
 export function encodeBatchBiases(channels, index, nativePalette, modes = null, haloFrames = 0, ctx = context()) {
   return native().encodeBatchBiases(ctx, channels, haloFrames, nativePalette, index, modes)
 }
+
+// c1_encode_best_bias_batch on the default context: encode() with the allocation bias of every sound unit chosen among the
+// option sets by least coding error -- the sum over the unit's 512 MDCT coefficients of (c - d)^2, d what the decoder's
+// dequantizationStage makes of the unit.  optionSets: 1 .. 8 results of EncoderOptions.toNative() (an array of them, or one
+// Float64Array(68 * n)); modes: null (detection or fixed modes as the sets say, which must then agree) or mode bytes as for
+// encodeBatchModes.  Returns { units, choice: Uint8Array(frames * channels) indexing optionSets, distortion:
+// Float64Array(frames * channels * n) unit-major, energy: Float64Array(frames * channels) }.
+export function encodeBestBias(channels, optionSets, modes = null, haloFrames = 0, ctx = context()) {
+  let palette = optionSets
+  if (Array.isArray(optionSets)) {
+    palette = new Float64Array(68 * optionSets.length)
+    optionSets.forEach((set, k) => {
+      if (!(set instanceof Float64Array) || set.length !== 68) throw new TypeError('optionSets: results of EncoderOptions.toNative()')
+      palette.set(set, 68 * k)
+    })
+  }
+  return native().encodeBestBias(ctx, channels, haloFrames, palette, modes)
+}

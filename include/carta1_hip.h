@@ -129,7 +129,7 @@ int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stre
 int c1_ctx_destroy(c1_ctx *ctx);
 int c1_ctx_synchronize(c1_ctx *ctx);
 /* milliseconds the device spent in the named kernel during the most recent *_device call on this
- * context ("analysis", "allocate", "pack", "decode", "redo", or "total"), in the most recent c1_pack_units call
+ * context ("analysis", "allocate", "pack", "decode", "redo", "choose", or "total"), in the most recent c1_pack_units call
  * ("pack_units"), or in the most recent decode from frame fields -- c1_decode_fields_*, c1_dec_stream_push_fields or a
  * unit push that follows one ("decode_fields") -- or in the from-state kernel of the most recent c1_*_frames_from_states*
  * call ("from_state") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
@@ -261,6 +261,43 @@ int c1_encode_biases_device(c1_ctx *ctx, const float *const *pcm, int channels, 
 int c1_encode_biases_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                            const c1_encode_options *palette, int n_palette, const uint8_t *bias_index /* host */,
                            const uint8_t *modes /* host, or NULL */, uint8_t *units /* host */);
+
+/* ---- encode with the allocation bias of every sound unit chosen from a palette by least coding error ----------------------
+ * The reference's allocator (bitallocation.js:74-190) minimises a model of the distortion, biased[sfi] * 2^-bits * size, and
+ * never sees the mantissas quantize produces.  This call measures them: one analysis, one allocation per palette entry over
+ * every unit, and per (unit u, entry k), in binary64,
+ *     D(u,k) = sum_i (c[i] - d_k[i])^2        E(u) = sum_i c[i]^2        i = 0 .. 511
+ * where c are the Float32 MDCT coefficients as quantizationStage receives them (encoder.js:365; the exact kernels', whatever
+ * the speculation mode) and d_k the Float32 coefficients dequantizationStage (decoder.js:52-98) produces from the sound unit
+ * the reference writes for u with allocationBias = entry k's bias: Float32((q * SCALE_FACTORS[sfi]) / range)
+ * (quantization.js:65-78) of the mantissas q of quantization.js:34-56, zero where a BFU is at or above the unit's amount or
+ * has word length 0.  choice[u] is the smallest k with D(u,k) <= D(u,j) for all j, on the values computed: a NaN never wins,
+ * and if every entry's D is NaN the choice is 0.  The order of the sums is fixed (a lane's 8 slots in order, then one tree
+ * over the 64 lanes), so the same inputs give the same bits run after run, and entries with identical tables give identical
+ * D: the lower index wins.  units[u] are exactly the bytes of c1_encode_biases_* with bias_index[u] = choice[u], packed by
+ * the same kernels.  Nothing is carried from frame to frame by the bias or the choice.
+ * palette, modes, their validation, the limits on frames, alignment, chunking and the caller's-stream contract are those of
+ * c1_encode_biases_device / _batch: modes NULL makes all entries agree in threshold and fixed modes; mode bytes are checked by
+ * the batch call and brought into the domain on the device by the device call.  Each output may be NULL (units NULL: measure
+ * only, no packing runs); all four NULL is C1_ERR_ARG.  distortion is unit-major: D(u,k) at [u * n_palette + k].  With one
+ * entry the call is the report "how well was this coded".  The call always takes the exact analysis; no output depends on
+ * the speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP or the halo.  Workspace: 32 bytes per unit
+ * and entry on top of an encode call's.  c1_ctx_kernel_ms counts the trial allocations under "allocate" and the measuring
+ * kernel under "choose". */
+int c1_encode_best_bias_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                               const c1_encode_options *palette /* HOST, n_palette entries */, int n_palette,
+                               const uint8_t *modes /* device, frames*channels, or NULL */,
+                               uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                               uint8_t *choice /* device, frames*channels, or NULL */,
+                               double *distortion /* device, frames*channels*n_palette (unit-major), or NULL */,
+                               double *energy /* device, frames*channels, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The palette, the outputs and every mode byte are validated before the
+ * context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a device the
+ * call then returns C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per channel. */
+int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                              const c1_encode_options *palette, int n_palette, const uint8_t *modes /* host, or NULL */,
+                              uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
+                              double *distortion /* host, or NULL */, double *energy /* host, or NULL */);
 
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
