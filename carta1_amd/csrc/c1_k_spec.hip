@@ -24,28 +24,47 @@ namespace {
 // soon as every read of its previous content has been issued):
 //   R1 = mem[0, 840)      stage-1 work buffer (blocks of 8 samples padded to 12 floats: conflict-free 16-byte
 //                         window reads at "lane base + immediate")  ->  in2 (512, from mem[1]: a lane's four high-band
-//                         outputs then start a 16-byte group)  ->  FFT points z (320 float2)
+//                         outputs then start a 16-byte group)  ->  FFT points z (320 float2, below mem[640))
 // The zero padding of the long-block MDCT inputs is never materialised: the pre-twiddle knows which of its operands
 // fall into it (a lane-constant predicate) and takes 0 instead of reading.
-//   R2 = mem[840, 1416)   stage-2 work buffer (302)  ->  in0 | in1 (256 each)  ->  coefficients (512)
+//   R2 = mem[840, 1352)   in0 / in1 (256 each, interleaved in blocks of 32: in01())  ->  coefficients (512)
+//   W2 = mem[1160, 1464)  stage-2 work buffer (304); its first 256 floats overlay the upper part of R2
+// Both work buffers hold sample i at POSITION i + 2.  A lane's window then starts two floats early (one pair it does
+// not use), and what a lane produces for the buffer -- four PCM samples, four stage-1 outputs -- is one aligned
+// 16-byte group at position 48 + 4 lane: one ds_write_b128, eight lanes to 32 consecutive banks.
+// The 46-sample delay lines are the buffers' own tails: positions 512..559 of the stage-1 buffer (mem[768, 840)) and
+// 256..303 of the stage-2 buffer (mem[1416, 1464)) are overwritten by nothing else in a frame, so the next frame
+// starts by copying them to positions 0..47 -- one read and one write each, no delay arrays of their own.
 // With short blocks (SHORT) the MDCT inputs are staged per band as E[s] = W[s & 31] x[s] behind the previous frame's
 // 32 overlap values, and H[s] = x[s] W[31 - (s & 31)]: block q of a band is E[32 (q-1) ..) | H[32 q ..) (encoder.js:269-307).
 //   band 2: E at mem[0, 288), H at mem[288, 544);   band 0: E at R2 + 0 (160), H at R2 + 160 (128);   band 1: R2 + 288, R2 + 448
 constexpr int kR2 = 840;
-constexpr int kMemFloats = kR2 + 576;
+constexpr int kW2 = kR2 + 320;
+constexpr int kMemFloats = kW2 + 304;
+constexpr int kW1Tail = 768;        // mem index of position 512 of the stage-1 work buffer (64 blocks of 12 floats)
 constexpr int kIn2 = 1;             // in2[i] = mem[kIn2 + i]
 struct alignas(16) SpecLds {
   alignas(16) float mem[kMemFloats];
-  alignas(16) float d1[48];          // stage-1 delay line (46)
-  alignas(16) float d2[48];          // stage-2 delay line (46)
   alignas(16) float pre2[76];        // what the next frame's band-2 MDCT input starts with: windowed overlap (32), then the 39 delayed samples;
                                      // logical entry k lives at pre2[k + 1]: the tail lanes' four consecutive entries then start a 16-byte group
   alignas(4) uint8_t sfi[64];
-  // lane-only values of the END of a frame (where the coefficients go, the post-twiddle pair, the scale-factor scan), read
-  // back once per frame instead of being carried in registers through the whole loop: the register allocator spilled four
-  // such values to scratch, and a scratch reload waits on the same counter as the coefficient stores issued just before it
-  uint32_t geo[3][64];
 };
+// Lane-only values of the END of a frame (where the coefficients go, the post-twiddle pairs, the scale-factor scan), read
+// back once per frame (one 16-byte read) instead of being carried in registers through the whole loop: the register
+// allocator spilled four such values to scratch, and a scratch reload waits on the same counter as the coefficient
+// stores issued just before it.  x = F | S << 16, y = P | PD << 16, z = (U & 0xffff) | T << 16, w = scale-factor word:
+// byte offsets into the wave's coefficients of -o.x (F) and o.y (S) of the lane's first final point; the other three
+// points go to F + {U, T, U + T} and S - {U, T, U + T}; P, PD = byte offsets into `tab` of the post-twiddle pairs of
+// points 0 and 1 (points 2, 3 are 256 bytes further on).  Every value is relative to the wave's own buffers or to the
+// tables, so ONE copy serves the four waves of a workgroup (k_analysis_spec: geo[64]).
+typedef uint4 SpecGeo;
+static_assert(sizeof(SpecLds) % 16 == 0 && (kW2 + 48) % 4 == 0, "16-byte groups of every wave's buffers stay aligned");
+// MDCT inputs of bands 0 and 1: sample i of band b at mem[in01(b, i)].  Blocks of 32 samples, band 0's then band 1's:
+// the four points of a lane are 32 samples apart = 64 floats, the same stride as band 2's 64 samples in in2, so the
+// pre-twiddle reads its four a's (and c's) at one lane address plus immediates for all three bands.  Band 1's pairs
+// are swapped ((i & 31) ^ 1): where band 0's sixteen lanes read odd samples = odd banks, band 1's read even banks.
+__host__ __device__ constexpr int in01(int b, int i) { return kR2 + 64 * (i >> 5) + 32 * b + ((i & 31) ^ b); }
+
 // The binary32 tables every frame reads with lane-varying indices -- WINDOW_SHORT, the MDCT (cos, sin) pairs, the radix-4
 // rounds' twiddles: C1DevTables::win32 .. r2d, contiguous, 2 784 bytes -- are kept in LDS, ONE copy per workgroup of
 // kSpecWaves waves (the waves share nothing else and never meet again after the copy).  Read through the cache they were
@@ -58,7 +77,11 @@ constexpr int kSpecTabBase = (int)offsetof(C1DevTables, win32);
 constexpr int kSpecTabFloats = ((int)offsetof(C1DevTables, r2d) + (int)sizeof(((C1DevTables *)nullptr)->r2d) - kSpecTabBase) / 4;
 static_assert(offsetof(C1DevTables, pre32_64) > offsetof(C1DevTables, win32) && offsetof(C1DevTables, r2d) > offsetof(C1DevTables, r4c) &&
               offsetof(C1DevTables, norm32) == offsetof(C1DevTables, r2d) + sizeof(((C1DevTables *)nullptr)->r2d), "win32 .. r2d are one contiguous block");
-static_assert(kSpecWaves * sizeof(SpecLds) + kSpecTabFloats * 4 + 27 * 16 <= 32768, "speculative analysis: 5 workgroups of 4 waves per CU");
+// The CU hands out its 160 KB of LDS in 128 blocks of 1 280 bytes: five workgroups per CU (5 waves per SIMD) need a
+// workgroup within 25 blocks = 32 000 bytes, not 32 768.  (At 32 736 bytes -- 26 blocks -- the counters showed four
+// workgroups per CU: SQ_WAVE_CYCLES / SQ_BUSY_CU_CYCLES 3.8 instead of 4.7.)
+constexpr int kSpecLdsBytes = kSpecWaves * (int)sizeof(SpecLds) + 64 * (int)sizeof(SpecGeo) + kSpecTabFloats * 4 + 28 * 16 + 64 * 8;
+static_assert((kSpecLdsBytes + 1279) / 1280 <= 25, "speculative analysis: 5 workgroups of 4 waves per CU = at most 25 LDS blocks of 1 280 bytes each");
 constexpr int kE2 = 0, kH2 = 288, kE0 = kR2, kH0 = kR2 + 160, kE1 = kR2 + 288, kH1 = kR2 + 448;
 
 __device__ __forceinline__ int w1_phys(int v) { return __mul24(12, v >> 3) + (v & 7); }   // 24-bit multiply: v_mul_lo_u32 issues at a quarter of the rate
@@ -73,43 +96,47 @@ __device__ __forceinline__ int w1_phys(int v) { return __mul24(12, v >> 3) + (v 
 //   P1 = (odd B-chain m = 23..13 , even A-chain j = 0..10)      P2 = (odd A-chain m = 0..10 , even B-chain j = 23..13)
 // then the two terms with tap 11 (a packed FMA whose other half multiplies by 0: x + 0 * w is exact), P1 + P2, and
 // the centre taps as two plain FMAs.
-template <int D, int NP>
-__device__ __forceinline__ void qmf_core_f32(const v2f (&W)[NP], TablesPtr T, float (&lo)[D], float (&hi)[D]) {
+// The lane's registers hold its window from pair OFF on (OFF = 1: the buffers are read from two floats early).
+template <int D, int NP, int OFF>
+__device__ __forceinline__ void qmf_core_f32(const v2f (&Wr)[NP], TablesPtr T, float (&lo)[D], float (&hi)[D]) {
+  static_assert(OFF + D - 1 + 23 < NP, "the window registers cover every tap");
   v2f tp[26];                                            // wave-uniform: aligned SGPR pairs, straight into the packed FMAs
 #pragma unroll
   for (int j = 0; j < 26; j++) tp[j] = *reinterpret_cast<const __attribute__((address_space(4))) v2f *>(T->tap_pair[j]);
   const float e12 = T->tap32[12];
 #pragma unroll
   for (int d = 0; d < D; d++) {
-    v2f p1 = W[d + 23] * tp[0];
+    v2f p1 = Wr[OFF + d + 23] * tp[0];
 #pragma unroll
-    for (int j = 1; j <= 10; j++) p1 = pk_fma(W[d + 23 - j], tp[j], p1);
-    v2f p2 = W[d] * tp[23];
+    for (int j = 1; j <= 10; j++) p1 = pk_fma(Wr[OFF + d + 23 - j], tp[j], p1);
+    v2f p2 = Wr[OFF + d] * tp[23];
 #pragma unroll
-    for (int j = 22; j >= 13; j--) p2 = pk_fma(W[d + 23 - j], tp[j], p2);
-    p1 = pk_fma(W[d + 12], tp[24], p1);           // even j = 11: w[2 d + 25]
-    p2 = pk_fma(W[d + 11], tp[25], p2);           // odd  m = 11: w[2 d + 22]
+    for (int j = 22; j >= 13; j--) p2 = pk_fma(Wr[OFF + d + 23 - j], tp[j], p2);
+    p1 = pk_fma(Wr[OFF + d + 12], tp[24], p1);           // even j = 11: w[2 d + 25]
+    p2 = pk_fma(Wr[OFF + d + 11], tp[25], p2);           // odd  m = 11: w[2 d + 22]
     const v2f sum = p1 + p2;                             // (odd B + odd A, even A + even B)
-    const float ev = __builtin_fmaf(e12, W[d + 11].y, sum.y);   // w[2 d + 23]
-    const float od = __builtin_fmaf(e12, W[d + 12].x, sum.x);   // w[2 d + 24]
+    const float ev = __builtin_fmaf(e12, Wr[OFF + d + 11].y, sum.y);   // w[2 d + 23]
+    const float od = __builtin_fmaf(e12, Wr[OFF + d + 12].x, sum.x);   // w[2 d + 24]
     lo[d] = ev + od;
     hi[d] = ev - od;
   }
 }
 
 // lane-only geometry of the long-block core (same ownership as mdct_long_r4: lanes 0..15 band 0, 16..31 band 1,
-// 32..63 band 2, four FFT points per lane), with the MDCT inputs at mem[kR2] (in0), mem[kR2 + 256] (in1), mem[0] (in2).
+// 32..63 band 2, four FFT points per lane), with the MDCT inputs at in01(0, .), in01(1, .) and mem[kIn2] (in2).
 // Only a few base values stay in registers across the frame loop; the 40-odd addresses of a frame are one add or
 // multiply-add away from them (the register file, not the VALU, limits how many waves this kernel keeps in flight).
 struct SpecBase {
-  int ia0, ic0;      // float index of operands a, c of the lane's first point (position 4g)
-  int q2;            // 2 * (points per quarter): the four points of a lane are 2 q2 input samples apart
+  int ia3, ic0;      // float index of operand a of the lane's LAST point (position 4g + 3) and of c of its first: the points
+                     // at positions 4g + 1, 2, 3 have theirs 128, 64, 192 floats below a of the first = above a of the last
+  int q2;            // 2 * (points per quarter): the pre-twiddle pairs of a lane's points are 4 q2 bytes apart
   int ib, id;        // float index of the one (b, d) operand pair of the lane that is not zero padding (if any)
   int pt0;           // byte offset of the pre-twiddle pair of the first point
   int za, zb, zc, zd;
   int g;
   int e0, e1;        // coefficient indices 2 i and n2 - 1 - 2 i of the lane's first final point (band offset included)
   int po0;           // byte offset of its post-twiddle pair
+  int d1;            // the lane's second final point is d1 points from its first (the third 32, the fourth d1 + 32)
   bool band0, band2, use_lo, use_hi;
 };
 __device__ __forceinline__ SpecBase spec_base(int lane) {
@@ -118,18 +145,19 @@ __device__ __forceinline__ SpecBase spec_base(int lane) {
   const int g = lane - (band == 0 ? 0 : (band == 1 ? 16 : 32));
   const int n4 = band == 2 ? 128 : 64, q = n4 / 4;
   const int r = bitrev(g, band == 2 ? 5 : 4);
-  const int in_base = band == 0 ? kR2 : (band == 1 ? kR2 + 256 : kIn2);
+  // float index of input sample i of the lane's band
+  auto in = [band](int i) { return band == 2 ? kIn2 + i : in01(band, i); };
   const int tab_base = band == 2 ? (int)offsetof(C1DevTables, pre32_512) : (int)offsetof(C1DevTables, pre32_256);
-  B.ia0 = in_base + 3 * n4 - 1 - 2 * r;
-  B.ic0 = in_base + n4 + 2 * r;
+  B.ia3 = in(3 * n4 - 1 - 2 * r) - 192;
+  B.ic0 = in(n4 + 2 * r);
   B.q2 = 2 * q;
   // Long-block inputs are zero outside [ws, ws + 32 + band length).  Of a lane's four points only position 0 (first
   // half of the pre-twiddle, mdct.js:76-89) and position 3 (second half, :91-105) have operands b, d at all inside
   // the 2 N/4 outer samples, and they are non-zero for r < 8 (position 0) or r >= n4/4 - 8 (position 3) only.
   B.use_lo = r < 8;
   B.use_hi = r >= q - 8;
-  B.ib = B.use_lo ? in_base + 3 * n4 + 2 * r : in_base + 2 * r + 2 * q;
-  B.id = B.use_lo ? in_base + n4 - 1 - 2 * r : in_base + 14 * q - 1 - 2 * r;
+  B.ib = B.use_lo ? in(3 * n4 + 2 * r) : in(2 * r + 2 * q);
+  B.id = B.use_lo ? in(n4 - 1 - 2 * r) : in(14 * q - 1 - 2 * r);
   B.pt0 = tab_base + 8 * r;
   const int pbase = band == 0 ? 0 : (band == 1 ? 64 : 128);
   B.za = zslot(pbase + 4 * g);
@@ -141,14 +169,38 @@ __device__ __forceinline__ SpecBase spec_base(int lane) {
   B.e0 = cbase + 2 * g;
   B.e1 = cbase + n2 - 1 - 2 * g;
   B.po0 = tab_base + 8 * g;
+  B.d1 = band == 2 ? 64 : 16;
   B.band0 = band == 0;
   B.band2 = band == 2;
   return B;
 }
 
+// Products whose one sign rides on the operand (neg_lo / neg_hi of the packed instruction) instead of being made by a
+// product with (1, -1) first: x (-w) is the very operation the two-step form ends with, on the very same values, so the
+// results are the same bits, signed zeros included.  Inline: the compiler folds the swaps into op_sel but negates a
+// single half with an instruction of its own.
+__device__ __forceinline__ v2f pk_mul_yy_nyx(v2f x, v2f w) {   // (x.y (-w.y), x.y w.x)
+  v2f r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(x), "v"(w));
+  return r;
+}
+__device__ __forceinline__ v2f pk_mul_yx_yny(v2f x, v2f t) {   // (x.y t.y, x.x (-t.y))
+  v2f r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(t));
+  return r;
+}
+// cmul32 (c1_device.h) in that form
+__device__ __forceinline__ v2f cmul32n(v2f x, v2f w) {
+  const v2f t = pk_mul_yy_nyx(x, w);                     // (-(x.y w.y), x.y w.x)
+  return pk_fma(x.xx, w, t);
+}
+// One 8-byte LDS read that stays one: the compiler pairs two of them that share a base into ds_read2_b64, which the LDS
+// serves at half the rate of two ds_read_b64 (16-lane groups over 32 banks instead of 32-lane groups over 64).
+// (volatile keeps the pair apart; the cast names the address space, which is not inferred for a volatile access)
+__device__ __forceinline__ v2f lds_f2(const v2f *p) { return *(const volatile __attribute__((address_space(3))) v2f *)p; }
 // one radix-4 round over two reference stages: x1, x2, x3 times wa, wb, wa*wb, then the 4-point butterfly
 __device__ __forceinline__ void radix4_round(v2f (&x)[4], v2f wa, v2f wb, v2f wab) {
-  const v2f y1 = cmul32(x[1], wa), y2 = cmul32(x[2], wb), y3 = cmul32(x[3], wab);
+  const v2f y1 = cmul32n(x[1], wa), y2 = cmul32n(x[2], wb), y3 = cmul32n(x[3], wab);
   const v2f t0 = x[0] + y1, t1 = x[0] - y1, t2 = y2 + y3, t3 = y2 - y3;
   x[0] = t0 + t2;
   x[2] = t0 - t2;
@@ -222,7 +274,11 @@ template <bool SHORT>
 __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1EncodeLaunch L) {
   __shared__ SpecLds Sw[kSpecWaves];
   __shared__ alignas(16) float tab[kSpecTabFloats];
-  __shared__ alignas(16) float tail_w[27][4];               // band-2 tail weights of lanes 46..54 (this frame's input) and 46..63 (next frame's)
+  // Every LDS instruction is charged all its lane groups, whatever lanes are active (tools/lds_model_spec.py): a store that
+  // only the tail lanes window costs less as ONE store of all lanes with weights of 1 elsewhere (a product with 1 is exact)
+  __shared__ alignas(16) float tail_w[28][4];               // band-2 weights: [0] ones (lanes ..45), [1..9] lanes 46..54 (this frame's input), [10..27] lanes 46..63 (next frame's)
+  __shared__ alignas(8) float out_w[64][2];                 // bands 0, 1: (W[31 - k], W[30 - k]) of lane 48 + k / 2 (the last 32 samples), ones below
+  __shared__ alignas(16) SpecGeo geo[64];                   // lane geometry of a frame's end, the same for every wave (SpecGeo)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   SpecLds &S = Sw[wave];
   const int lane0 = threadIdx.x & 63;
@@ -230,17 +286,31 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
   {
     const float *src = reinterpret_cast<const float *>(reinterpret_cast<const char *>(L.tables) + kSpecTabBase);
     for (int i = threadIdx.x; i < kSpecTabFloats; i += C1_WAVE * kSpecWaves) tab[i] = src[i];
-    if (threadIdx.x < 27 * 4) {
+    if (threadIdx.x < 28 * 4) {
       const int idx = threadIdx.x >> 2, j = threadIdx.x & 3;
-      const bool input = idx < 9;                              // W[31 - k] x: positions 224..255 of this frame's input
-      const int k = 4 * (input ? idx : idx - 9) - 1 + j;      // k = position - 224 of element j of lane 46 + ...
+      const bool input = idx < 10;                             // W[31 - k] x: positions 224..255 of this frame's input
+      const int k = 4 * (input ? idx - 1 : idx - 10) - 1 + j; // k = position - 224 of element j of lane 46 + ... (entry 0: k < 0)
       tail_w[idx][j] = (k >= 0 && k < 32) ? src[input ? 31 - k : k] : 1.0f;     // src[0 .. 31] = fl32(WINDOW_SHORT)
+    }
+    if (threadIdx.x >= 128 && threadIdx.x < 128 + 64) {
+      const int l = threadIdx.x - 128, k = 2 * (l - 48);
+      out_w[l][0] = l >= 48 ? src[31 - k] : 1.0f;
+      out_w[l][1] = l >= 48 ? src[30 - k] : 1.0f;
+    }
+    if (!SHORT && threadIdx.x >= 192) {
+      const int l = threadIdx.x - 192;
+      const SpecBase G = spec_base(l);
+      const SfLong F = sf_long_geometry(l);
+      const int po = G.po0 - kSpecTabBase, u = G.band0 ? 8 * G.d1 : -8 * G.d1, t = G.band0 ? 256 : -256;   // bands 1 and 2 are stored reversed (utils.js:42-48)
+      geo[l] = make_uint4((uint32_t)(4 * (G.band0 ? G.e0 : G.e1)) | ((uint32_t)(4 * (G.band0 ? G.e1 : G.e0)) << 16),
+                          (uint32_t)po | ((uint32_t)(po + 8 * G.d1) << 16), ((uint32_t)u & 0xffffu) | ((uint32_t)t << 16),
+                          (uint32_t)(F.src & ~3) | ((uint32_t)F.b << 9) | (F.wide ? 1u << 15 : 0u) | (F.store ? 1u << 16 : 0u));
     }
   }
   __syncthreads();                                          // the only time the waves of a workgroup meet
   const float *win = tab;                                   // fl32(WINDOW_SHORT) = the first 32 floats
   auto table_f2 = [&](int /*unused resource*/, int byte_offset) -> v2f {
-    return *reinterpret_cast<const v2f *>(reinterpret_cast<const char *>(tab) + (byte_offset - kSpecTabBase));
+    return lds_f2(reinterpret_cast<const v2f *>(reinterpret_cast<const char *>(tab) + (byte_offset - kSpecTabBase)));
   };
   const uint32_t n_slots = (uint32_t)((L.frames + L.run_frames - 1) / L.run_frames) * (uint32_t)L.channels;
   // the bijection moves whole workgroups: the four waves of one take four consecutive (run, channel) pairs, i.e. the same
@@ -254,17 +324,13 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
   const float *__restrict__ pcm = L.pcm[ch];
   float *mem = S.mem;
 
-  for (int i = lane; i < 48; i += 64) { S.d1[i] = 0.0f; S.d2[i] = 0.0f; }
+  for (int i = lane; i < 72; i += 64) mem[kW1Tail + i] = 0.0f;     // the delay lines = the work buffers' tails
+  if (lane < 48) mem[kW2 + 256 + lane] = 0.0f;
   float ov0a = 0.0f, ov0b = 0.0f, ov1a = 0.0f, ov1b = 0.0f;   // lanes 48..63: windowed overlap of bands 0, 1 for the next frame
   for (int i = lane; i < 76; i += 64) S.pre2[i] = 0.0f;
   if (lane < 16) reinterpret_cast<uint32_t *>(S.sfi)[lane] = 0u;
   SpecBase B0 = spec_base(lane0);              // not const: passed through an opaque asm in place, once per frame (below)
   const SfLong SFL0 = SHORT ? sf_geometry(lane0, 2, 2, 3) : sf_long_geometry(lane0);
-  if constexpr (!SHORT) {
-    S.geo[0][lane0] = (uint32_t)(SFL0.src & ~3) | ((uint32_t)SFL0.b << 9) | (SFL0.wide ? 1u << 15 : 0u) | (SFL0.store ? 1u << 16 : 0u);
-    S.geo[1][lane0] = (uint32_t)(B0.band0 ? B0.e0 : B0.e1) | ((uint32_t)(B0.band0 ? B0.e1 : B0.e0) << 16);
-    S.geo[2][lane0] = (uint32_t)B0.po0;
-  }
   if (SHORT && lane == 0) S.sfi[52] = (uint8_t)((L.opts->modes[0] & 3) | ((L.opts->modes[1] & 3) << 2) | ((L.opts->modes[2] & 3) << 4));
   // short blocks: lane = (band, block, r) with four points of one 16-point transform
   const int s_band = lane0 < 16 ? 0 : (lane0 < 32 ? 1 : 2);
@@ -299,7 +365,7 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
       // the MDCT's base values pass through an opaque asm once per frame (see there) -- HERE, where every path through the
       // frame passes: on the emitting path alone the loop header saw two versions of them (the warm-up frame's untouched
       // ones) and the emitting path paid 23 register moves a frame to keep them apart
-      asm volatile("" : "+v"(B0.ia0), "+v"(B0.ic0), "+v"(B0.q2), "+v"(B0.ib), "+v"(B0.id), "+v"(B0.pt0));
+      asm volatile("" : "+v"(B0.ia3), "+v"(B0.ic0), "+v"(B0.q2), "+v"(B0.ib), "+v"(B0.id), "+v"(B0.pt0));
       asm volatile("" : "+v"(B0.za), "+v"(B0.zb), "+v"(B0.zc), "+v"(B0.zd), "+v"(B0.g));
     }
 
@@ -307,19 +373,17 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
     float P;
     {
       const v4f a = pre_a, b = pre_b;
-      // sample 4 lane + j of the frame sits at work index 46 + 4 lane + j: shifted by two samples against the lanes'
-      // 16-byte groups.  Each lane takes the last two samples of its left neighbour (DPP wave shift) and writes
-      // whole groups; the delay line is written afterwards and covers the two slots lane 0 filled with junk.
+      // sample 4 lane + j of the frame has work index 46 + 4 lane + j = position 48 + 4 lane + j: the lane's own 16-byte
+      // group, half a block of 8 (padded to 12 floats).  First the delay line: positions 512..559, which the previous
+      // frame left, move to positions 0..47 -- the same place in blocks 64 further down -- before b overwrites them.
       {
-        const float pz = dpp_read<0x138>(a.z), pw = dpp_read<0x138>(a.w);          // wave_shr:1
-        const float qz0 = dpp_read<0x138>(b.z), qw0 = dpp_read<0x138>(b.w);
-        const float az63 = lane_value(a.z, 63), aw63 = lane_value(a.w, 63);
-        const float qz = lane == 0 ? az63 : qz0, qw = lane == 0 ? aw63 : qw0;
-        const int v = 44 + 4 * lane;
-        *reinterpret_cast<float4 *>(&mem[w1_phys(v)]) = make_float4(pz, pw, a.x, a.y);
-        *reinterpret_cast<float4 *>(&mem[w1_phys(v + 256)]) = make_float4(qz, qw, b.x, b.y);
-        if (lane == 63) *reinterpret_cast<float2 *>(&mem[w1_phys(556)]) = make_float2(b.z, b.w);
-        if (lane < 46) mem[w1_phys(lane)] = S.d1[lane];
+        const int p = w1_phys(lane);
+        float dl = 0.0f;
+        if (lane < 48) dl = mem[kW1Tail + p];
+        const int s = __mul24(6, lane) - 2 * (lane & 1);                             // w1_phys(48 + 4 lane) - 72
+        *reinterpret_cast<v4f *>(&mem[72 + s]) = a;
+        *reinterpret_cast<v4f *>(&mem[72 + 384 + s]) = b;
+        if (lane < 48) mem[p] = dl;
       }
       v2f p2 = V2(a.x, a.y) * V2(a.x, a.y);
       p2 = pk_fma(V2(a.z, a.w), V2(a.z, a.w), p2);
@@ -334,14 +398,17 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
     {
       float lo[4], hi[4];
       if (own_block()) {
-        v2f W[28];
+        v2f W[28];                                           // positions 8 lane ..: the window starts at pair 1
         const float4 *src = reinterpret_cast<const float4 *>(mem + __mul24(12, lane));
 #pragma unroll
         for (int k = 0; k < 14; k++) {
-          const float4 t = src[3 * (k >> 1) + (k & 1)];      // floats 12 (k >> 1) + 4 (k & 1): blocks of 8 padded to 12
+          v4f t = *reinterpret_cast<const v4f *>(&src[3 * (k >> 1) + (k & 1)]);      // floats 12 (k >> 1) + 4 (k & 1): blocks of 8 padded to 12
+          // (the first group whole, although its first pair is not used: without it the compiler re-pairs the reads from
+          // the third float on, 8 bytes off the groups: ds_read2_b64, at half the rate of ds_read_b128)
+          if (k == 0) asm volatile("" : "+v"(t));
           W[2 * k] = V2(t.x, t.y); W[2 * k + 1] = V2(t.z, t.w);
         }
-        qmf_core_f32<4>(W, T, lo, hi);
+        qmf_core_f32<4, 28, 1>(W, T, lo, hi);
       } else { for (int d = 0; d < 4; d++) { lo[d] = mem[lane + d]; hi[d] = 1.0f; } }
       {
         // the next frame's PCM: requested once the window registers are free, used a frame later.  Unconditional (the
@@ -350,9 +417,9 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
         const v4f *p4 = reinterpret_cast<const v4f *>(pcm + ((f + 1 < f_end) ? f + 1 : f) * 512);
         pre_a = p4[lane]; pre_b = p4[64 + lane];
       }
-      if (lane < 46) { S.d1[lane] = mem[w1_phys(512 + lane)]; mem[kR2 + lane] = S.d2[lane]; }
-      *reinterpret_cast<float2 *>(&mem[kR2 + 46 + 4 * lane]) = make_float2(lo[0], lo[1]);
-      *reinterpret_cast<float2 *>(&mem[kR2 + 48 + 4 * lane]) = make_float2(lo[2], lo[3]);
+      // the stage-2 delay line (positions 256..303 of the previous frame -> 0..47), then this frame's outputs behind it
+      if (lane < 48) mem[kW2 + lane] = mem[kW2 + 256 + lane];
+      *reinterpret_cast<float4 *>(&mem[kW2 + 48 + 4 * lane]) = make_float4(lo[0], lo[1], lo[2], lo[3]);
       v2f q2 = V2(lo[0], lo[1]) * V2(lo[0], lo[1]);
       q2 = pk_fma(V2(lo[2], lo[3]), V2(lo[2], lo[3]), q2);
       const float q = q2.x + q2.y;
@@ -360,24 +427,24 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
       // band 2 = the high band behind its 39-sample delay (encoder.js:84-90): what the previous frame left (overlap,
       // 39 samples), then this frame's outputs; the last 32 samples of the band are windowed (encoder.js:309-316)
       if constexpr (!SHORT) {
-      if (emit) for (int i = lane; i < 71; i += 64) mem[kIn2 + 112 + i] = S.pre2[1 + i];
-      if (lane <= 45) {                                     // positions 39 + 4 lane .. + 3 < 224: plain samples, one 16-byte group
-        if (emit) *reinterpret_cast<float4 *>(&mem[kIn2 + 183 + 4 * lane]) = make_float4(hi[0], hi[1], hi[2], hi[3]);
-      } else {
-        // Lanes 46..63 hold positions 223..294: the band's last 32 samples (224..255) are windowed both ways -- W[31 - k] x
-        // into this frame's input, W[k] x as the next frame's overlap (k = position - 224) -- and positions >= 256 are the
-        // next frame's delayed samples.  Branch-free: a lane's four weights of either kind come from a table (tail_w: 1
-        // outside the windowed stretch; the product with 1 is exact), its four results are one 16-byte store each.  (Per
-        // element, with three-way branches, this cost 5 % of the kernel.)
-        const float4 wl = *reinterpret_cast<const float4 *>(tail_w[9 + lane - 46]);
+      // (pairs: pre2[0], which no logical entry owns, lands in the input's zero padding, which is never read)
+      if (emit && lane < 36) *reinterpret_cast<float2 *>(&mem[kIn2 + 111 + 2 * lane]) = *reinterpret_cast<const float2 *>(&S.pre2[2 * lane]);
+      // Lanes 0..54 hold positions 39..258 of this frame's input, one 16-byte group each: plain samples up to position 223
+      // (lane 45), then the band's last 32 samples (224..255) windowed W[31 - k] x (k = position - 224); lane 54's last three
+      // land in the input's zero padding, which is never read.  Lanes 46..63 also keep W[k] x as the next frame's overlap,
+      // and the positions >= 256, the next frame's delayed samples, as they are.  Branch-free: a lane's four weights of either
+      // kind come from a table (tail_w: 1 outside the windowed stretch; the product with 1 is exact), its four results are
+      // one 16-byte store each.  (Per element, with three-way branches, this cost 5 % of the kernel.)
+      {
+        const int wi = min(max(lane - 45, 0), 10);                  // lanes 55..: any entry, not stored
+        const float4 wh = *reinterpret_cast<const float4 *>(tail_w[wi]);
+        const v2f h01 = V2(hi[0], hi[1]) * V2(wh.x, wh.y), h23 = V2(hi[2], hi[3]) * V2(wh.z, wh.w);
+        if (emit && lane <= 54) *reinterpret_cast<float4 *>(&mem[kIn2 + 183 + 4 * lane]) = make_float4(h01.x, h01.y, h23.x, h23.y);
+      }
+      if (lane >= 46) {
+        const float4 wl = *reinterpret_cast<const float4 *>(tail_w[10 + lane - 46]);
         const v2f l01 = V2(hi[0], hi[1]) * V2(wl.x, wl.y), l23 = V2(hi[2], hi[3]) * V2(wl.z, wl.w);
         *reinterpret_cast<float4 *>(&S.pre2[4 * (lane - 46)]) = make_float4(l01.x, l01.y, l23.x, l23.y);   // logical entries 4 (lane - 46) - 1 ..
-        if (lane <= 54) {
-          // positions < 256 go into this frame's input; lane 54's last three land in the input's zero padding, which is never read
-          const float4 wh = *reinterpret_cast<const float4 *>(tail_w[lane - 46]);
-          const v2f h01 = V2(hi[0], hi[1]) * V2(wh.x, wh.y), h23 = V2(hi[2], hi[3]) * V2(wh.z, wh.w);
-          if (emit) *reinterpret_cast<float4 *>(&mem[kIn2 + 183 + 4 * lane]) = make_float4(h01.x, h01.y, h23.x, h23.y);
-        }
       }
       } else {
         // short blocks: every sample enters twice, E = W[pos & 31] x (second half of block q-1's... first half of the
@@ -407,37 +474,38 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
     {
       float lo[2], hi[2];
       if (own_block()) {
-        v2f W[26];
-        const float4 *src = reinterpret_cast<const float4 *>(mem + kR2 + 4 * lane);
+        v2f W[26];                                           // positions 4 lane ..: the window starts at pair 1
+        const float4 *src = reinterpret_cast<const float4 *>(mem + kW2 + 4 * lane);
 #pragma unroll
         for (int k = 0; k < 13; k++) {
-          const float4 t = src[k];
+          v4f t = *reinterpret_cast<const v4f *>(&src[k]);
+          if (k == 0) asm volatile("" : "+v"(t));            // (as in the first stage)
           W[2 * k] = V2(t.x, t.y); W[2 * k + 1] = V2(t.z, t.w);
         }
-        qmf_core_f32<2>(W, T, lo, hi);
+        qmf_core_f32<2, 26, 1>(W, T, lo, hi);
       } else { for (int d = 0; d < 2; d++) { lo[d] = mem[lane + d]; hi[d] = 1.0f; } }
-      {
-        // (a lane index of its own: from `lane` the compiler derives this 4-byte-stride address as the window's 16-byte-stride
-        // one minus 12 lane -- a 64-bit multiply-add at a quarter of the issue rate)
-        const int ld = lane_for_this_frame(lane0);
-        if (ld < 46) S.d2[ld] = mem[kR2 + 256 + ld];
-      }
       if constexpr (!SHORT) {
-      if (lane < 48) {
+      // samples 80 + 2 lane, + 1 of both bands: pair u = 40 + lane of band 0 at in01(0, 2 u) = kR2 + 2 (u + (u & ~15)), band 1's
+      // 32 floats further on with its halves swapped (in01)
+      const int u = lane + 40, at = kR2 + 2 * (u + (u & ~15));
+      // the last 32 samples of bands 0, 1 (lanes 48..63; encoder.js:309-316) are windowed into this frame's input -- all lanes
+      // multiply, by 1 below lane 48 (out_w) -- and, with the mirrored window, kept in registers as the next frame's
+      // overlap, which these same lanes write then
+      {
+        const v2f wh = *reinterpret_cast<const v2f *>(out_w[lane]);
+        const v2f o0 = V2(lo[0], lo[1]) * wh, o1 = V2(hi[1], hi[0]) * wh.yx;
         if (emit) {
-          *reinterpret_cast<float2 *>(&mem[kR2 + 80 + 2 * lane]) = make_float2(lo[0], lo[1]);
-          *reinterpret_cast<float2 *>(&mem[kR2 + 256 + 80 + 2 * lane]) = make_float2(hi[0], hi[1]);
+          *reinterpret_cast<v2f *>(&mem[at]) = o0;
+          *reinterpret_cast<v2f *>(&mem[at + 32]) = o1;
         }
-      } else {
-        // the last 32 samples of bands 0, 1 (encoder.js:309-316): windowed into this frame's input, and, with the
-        // mirrored window, kept in registers as the next frame's overlap, which these same lanes write then
+      }
+      if (lane >= 48) {
         const int k = 2 * (lane - 48);
-        const float wl0 = win[k], wl1 = win[k + 1], wh0 = win[31 - k], wh1 = win[30 - k];
+        const float wl0 = win[k], wl1 = win[k + 1];
         if (emit) {
-          *reinterpret_cast<float2 *>(&mem[kR2 + 48 + k]) = make_float2(ov0a, ov0b);
-          *reinterpret_cast<float2 *>(&mem[kR2 + 256 + 48 + k]) = make_float2(ov1a, ov1b);
-          *reinterpret_cast<float2 *>(&mem[kR2 + 80 + 2 * lane]) = make_float2(lo[0] * wh0, lo[1] * wh1);
-          *reinterpret_cast<float2 *>(&mem[kR2 + 256 + 80 + 2 * lane]) = make_float2(hi[0] * wh0, hi[1] * wh1);
+          const int uo = lane - 24, ato = kR2 + 2 * (uo + (uo & ~15));             // samples 48 + k, + 1: pair 24 + k / 2
+          *reinterpret_cast<float2 *>(&mem[ato]) = make_float2(ov0a, ov0b);
+          *reinterpret_cast<float2 *>(&mem[ato + 32]) = make_float2(ov1b, ov1a);
         }
         ov0a = wl0 * lo[0]; ov0b = wl1 * lo[1];
         ov1a = wl0 * hi[0]; ov1b = wl1 * hi[1];
@@ -474,6 +542,7 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
 
     v2f x[4];
     float zrow;
+    uint32_t gw_sf = 0;                                      // the scale-factor word of SpecGeo
     if constexpr (!SHORT) {
     // ---------------- long-block MDCT in binary32 ----------------
     // position 4g + j of the lane holds point k_j = r + q * bitrev2(j): j = 1 -> 2q, j = 2 -> q, j = 3 -> 3q
@@ -485,11 +554,11 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
       const int qb = 4 * B.q2;                               // bytes between the pre-twiddle pairs of points q apart
       const v2f t0 = table_f2(RT, B.pt0), t1 = table_f2(RT, B.pt0 + 2 * qb);
       const v2f t2 = table_f2(RT, B.pt0 + qb), t3 = table_f2(RT, B.pt0 + __mul24(3, qb));
-      const float a0 = mem[B.ia0], c0 = mem[B.ic0];
-      const float a1 = mem[B.ia0 - 2 * B.q2], c1 = mem[B.ic0 + 2 * B.q2];
-      const float a2 = mem[B.ia0 - B.q2], c2 = mem[B.ic0 + B.q2];
-      const int q3 = __mul24(3, B.q2);
-      const float a3 = mem[B.ia0 - q3], c3 = mem[B.ic0 + q3];
+      // the lane's points are 64 floats apart in every band (in01): one address and immediates
+      const float a0 = mem[B.ia3 + 192], c0 = mem[B.ic0];
+      const float a1 = mem[B.ia3 + 64], c1 = mem[B.ic0 + 128];
+      const float a2 = mem[B.ia3 + 128], c2 = mem[B.ic0 + 64];
+      const float a3 = mem[B.ia3], c3 = mem[B.ic0 + 192];
       const float bb = mem[B.ib], dd = mem[B.id];             // the lane's one pair outside the zero padding (or unused)
       const float b0 = B.use_lo ? bb : 0.0f, d0 = B.use_lo ? dd : 0.0f;
       const float b3 = B.use_hi ? bb : 0.0f, d3 = B.use_hi ? dd : 0.0f;
@@ -497,7 +566,7 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
       // (:91-105); for positions 1, 2 the operands b, d are the zero padding.  Then (r c + m s, m c - r s).
       const v2f rm0 = pk_fma(V2(b0, d0), PMN, V2(a0, c0)), rm3 = pk_fma(V2(b3, d3), PNM, V2(a3, c3));
       const v2f rm1 = V2(a1, c1), rm2 = V2(a2, c2);
-      auto twiddle = [](v2f rm, v2f t) { const v2f u = rm.yx * (t.yy * PMN); return pk_fma(rm, t.xx, u); };   // u = (m s, -(r s))
+      auto twiddle = [](v2f rm, v2f t) { const v2f u = pk_mul_yx_yny(rm, t); return pk_fma(rm, t.xx, u); };   // u = (m s, r (-s))
       x[0] = twiddle(rm0, t0); x[1] = twiddle(rm1, t1); x[2] = twiddle(rm2, t2); x[3] = twiddle(rm3, t3);
       v2f en2 = x[0] * x[0];
 #pragma unroll
@@ -521,7 +590,7 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
     wave_fence();
     {
       v2f *p = z + B.zb;
-      x[0] = p[0]; x[1] = p[4]; x[2] = p[8]; x[3] = p[12];
+      x[0] = lds_f2(p); x[1] = lds_f2(p + 4); x[2] = lds_f2(p + 8); x[3] = lds_f2(p + 12);
       radix4_round(x, wBa, wBb, wBc);
       p[0] = x[0]; p[4] = x[1]; p[8] = x[2]; p[12] = x[3];
     }
@@ -531,36 +600,37 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
     wave_fence();
     {
       v2f *p = z + B.zc;
-      x[0] = p[0]; x[1] = p[20]; x[2] = p[40]; x[3] = p[60];
+      x[0] = lds_f2(p); x[1] = lds_f2(p + 20); x[2] = lds_f2(p + 40); x[3] = lds_f2(p + 60);
       radix4_round(x, wCa, wCb, wCc);
       if (B.band2) { p[0] = x[0]; p[20] = x[1]; p[40] = x[2]; p[60] = x[3]; }
     }
     // final points: bands 0/1 hold g + 16 j after round C; band 2 holds g, g + 64, g + 32, g + 96 after round D
-    const int d1 = B.band2 ? 64 : 16, d2 = 32, d3 = B.band2 ? 96 : 48;
-    const int po0 = (int)S.geo[2][lane];
-    const uint32_t ew = S.geo[1][lane];                      // where -o.x and o.y of the first final point go (band 0: 2 i and n2 - 1 - 2 i; bands 1, 2 reversed)
-    const v2f p0 = table_f2(RT, po0), p1 = table_f2(RT, po0 + 8 * d1);
-    const v2f p2 = table_f2(RT, po0 + 8 * d2), p3 = table_f2(RT, po0 + 8 * d3);
+    const SpecGeo gw = geo[lane];                            // where the lane's final points go and what they are multiplied by (SpecGeo)
+    const int po0 = kSpecTabBase + (int)(gw.y & 0xffffu), po1 = kSpecTabBase + (int)(gw.y >> 16);
+    const v2f p0 = table_f2(RT, po0), p1 = table_f2(RT, po1);
+    const v2f p2 = table_f2(RT, po0 + 256), p3 = table_f2(RT, po1 + 256);
     wave_fence();
     if (B.band2) {
       const v2f *p = z + B.zd;
-      x[0] = p[0]; x[1] = p[80]; x[2] = p[40]; x[3] = p[120];
-      const v2f y1 = cmul32(x[1], wDa), y3 = cmul32(x[3], wDb);
+      x[0] = lds_f2(p); x[1] = lds_f2(p + 80); x[2] = lds_f2(p + 40); x[3] = lds_f2(p + 120);
+      const v2f y1 = cmul32n(x[1], wDa), y3 = cmul32n(x[3], wDb);
       const v2f e0 = x[0], e2 = x[2];
       x[0] = e0 + y1; x[1] = e0 - y1; x[2] = e2 + y3; x[3] = e2 - y3;
     }
-    float *coefw = mem + kR2;
+    char *coefw = reinterpret_cast<char *>(mem + kR2);
+    const int cf = (int)(gw.x & 0xffffu), cs = (int)(gw.x >> 16);
+    const int su = (int)(gw.z << 16) >> 16, st = (int)gw.z >> 16, sut = su + st;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const v2f t = j == 0 ? p0 : (j == 1 ? p1 : (j == 2 ? p2 : p3));
-      const int dj = j == 0 ? 0 : (j == 1 ? d1 : (j == 2 ? d2 : d3));
-      const int step = B.band0 ? 2 * dj : -2 * dj;           // bands 1 and 2 are stored reversed (utils.js:42-48)
+      const int step = j == 0 ? 0 : (j == 1 ? su : (j == 2 ? st : sut));      // bytes; negative in bands 1 and 2
       // mdct.js:110-119: out[2 i] = -(re c + im s), out[n2 - 1 - 2 i] = im c - re s
-      const v2f u = x[j].yx * (t.yy * PMN);                  // (im s, -(re s))
+      const v2f u = pk_mul_yx_yny(x[j], t);                  // (im s, re (-s))
       const v2f o = pk_fma(x[j], t.xx, u);
-      coefw[(int)(ew & 0xffffu) + step] = -o.x;
-      coefw[(int)(ew >> 16) - step] = o.y;
+      *reinterpret_cast<float *>(coefw + (cf + step)) = -o.x;
+      *reinterpret_cast<float *>(coefw + (cs - step)) = o.y;
     }
+    gw_sf = gw.w;
     wave_fence();
 
     }
@@ -664,7 +734,7 @@ __global__ __launch_bounds__(C1_WAVE * kSpecWaves, 5) void k_analysis_spec(C1Enc
 #pragma unroll
         for (int j = 0; j < 12; j++) mx = fmaxf(mx, fabsf(src[j < SFL.cnt ? j : SFL.cnt - 1]));
       } else {
-        const uint32_t sw = S.geo[0][lane];
+        const uint32_t sw = gw_sf;
         SFL.b = (int)((sw >> 9) & 63u);
         SFL.wide = ((sw >> 15) & 1u) != 0u;
         SFL.store = ((sw >> 16) & 1u) != 0u;
