@@ -272,6 +272,35 @@ class Context:
                                                          None if energy is None else energy.ctypes.data))
         return (units, choice, dist, energy) if return_distortion else (units, choice)
 
+    def encode_best_modes(self, channels, candidates, options=None, halo_frames=0, return_distortion=False):
+        """encode() with the block modes of every sound unit chosen among `candidates` by least coding error: the sum over the
+        unit's 512 MDCT coefficients of W * (c - d)^2, d what the decoder's dequantizationStage makes of the unit and W the
+        transform's scaling (1 long, 1/4 low or mid short, 1/2 high short), so that candidates compare as their PCM error does
+        (c1_encode_best_modes_batch).  candidates: 1 .. MAX_MODE_CANDIDATES distinct mode bytes or triples as
+        pack_block_modes() takes them, in the caller's order (choice indexes it); ValueError for a duplicate or a candidate
+        outside the domain of encode_modes().  Of `options` only the allocation bias (or biased table) is used.  Returns
+        (units, choice uint8 [units], modes uint8 [units]), and with return_distortion also distortion and energy, float64
+        [units, n]; units are what encode_modes() gives under `modes`."""
+        opts = (options or EncoderOptions()).to_c()
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = max(n // 512 - halo_frames, 0)
+        cand = mode_candidates(candidates)
+        count = len(cand)
+        units = np.zeros((frames * len(chans), 212), dtype=np.uint8)
+        choice = np.zeros(frames * len(chans), dtype=np.uint8)
+        modes = np.zeros(frames * len(chans), dtype=np.uint8)
+        dist = np.zeros((frames * len(chans), count), dtype=np.float64) if return_distortion else None
+        energy = np.zeros((frames * len(chans), count), dtype=np.float64) if return_distortion else None
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_best_modes_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts),
+                                                          cand.ctypes.data, count, units.ctypes.data, choice.ctypes.data, modes.ctypes.data,
+                                                          None if dist is None else dist.ctypes.data,
+                                                          None if energy is None else energy.ctypes.data))
+        return (units, choice, modes, dist, energy) if return_distortion else (units, choice, modes)
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -320,6 +349,18 @@ class Context:
         capi.check(capi.load().c1_encode_best_bias_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                           palette, len(palette_options), vp(modes_ptr), vp(units_ptr), vp(choice_ptr),
                                                           vp(distortion_ptr), vp(energy_ptr)))
+
+    def encode_best_modes_device(self, pcm_ptrs, frames, candidates, units_ptr=None, choice_ptr=None, modes_ptr=None,
+                                 distortion_ptr=None, energy_ptr=None, options=None, halo_frames=0):
+        """c1_encode_best_modes_device: candidates = 1 .. MAX_MODE_CANDIDATES distinct mode bytes or triples (host; checked by
+        the library: C1_ERR_ARG); outputs on the device, each may be None (units_ptr None: measure only), not all; choice and
+        modes are uint8 [units], distortion and energy float64 [units, n]."""
+        opts = (options or EncoderOptions()).to_c()
+        cand = mode_candidates(candidates, check=False)
+        vp = lambda p: C.c_void_p(p) if p else None
+        capi.check(capi.load().c1_encode_best_modes_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                           C.byref(opts), cand.ctypes.data, len(cand), vp(units_ptr), vp(choice_ptr),
+                                                           vp(modes_ptr), vp(distortion_ptr), vp(energy_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -946,6 +987,39 @@ def check_block_modes(modes, frames, channels):
                 raise ValueError('%s: %s field of mode byte 0x%02x is %d, not 0 or %d' % (where, name, b, f, other))
         raise ValueError('%s: bits 6-7 of mode byte 0x%02x are set' % (where, b))
     return m
+
+
+# ---- the block modes per sound unit chosen among candidates (c1_encode_best_modes_*) ------------------------------------
+MAX_MODE_CANDIDATES = 8
+
+
+def mode_candidates(candidates, check=True):
+    """the candidates of Context.encode_best_modes -> uint8 mode bytes in the caller's order.  An entry is a mode byte or a
+    triple as pack_block_modes() takes it.  check: ValueError for none, for more than MAX_MODE_CANDIDATES, for an entry
+    outside the domain of encode_modes() (naming it) and for a byte given twice; without it the library's own check decides."""
+    out = []
+    for v in list(candidates):
+        if isinstance(v, (int, np.integer)):
+            if not 0 <= int(v) <= 255:
+                raise ValueError('mode bytes must be 0..255')
+            out.append(int(v))
+        else:
+            out.append(int(pack_block_modes(v)[0]) if np.asarray(v).size == 3 else -1)
+            if out[-1] < 0:
+                raise ValueError('a candidate must be a mode byte or a triple of block modes')
+    if check:
+        if not 1 <= len(out) <= MAX_MODE_CANDIDATES:
+            raise ValueError('between 1 and %d candidate block modes per call, got %d' % (MAX_MODE_CANDIDATES, len(out)))
+        for i, b in enumerate(out):
+            for k, name in enumerate(_MODE_FIELDS):
+                f, other = (b >> (2 * k)) & 3, 3 if k == 2 else 2
+                if f not in (0, other):
+                    raise ValueError('candidate %d: %s field of mode byte 0x%02x is %d, not 0 or %d' % (i, name, b, f, other))
+            if b & 0xC0:
+                raise ValueError('candidate %d: bits 6-7 of mode byte 0x%02x are set' % (i, b))
+            if b in out[:i]:
+                raise ValueError('candidate %d: mode byte 0x%02x is given twice' % (i, b))
+    return np.ascontiguousarray(out, dtype=np.uint8).reshape(-1)
 
 
 # ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----

@@ -464,6 +464,11 @@ struct c1_ctx {
   // k's records at d_trial + k * trial_units * kAllocBytes; allocated on first use
   uint8_t *d_trial = nullptr;
   int64_t trial_units = 0, trial_n = 0;
+  // the block modes chosen per unit (c1_encode_best_modes_device): the coefficients and side records of one chunk's second
+  // (all-short) analysis and the side records composed for one candidate at a time; allocated on first use
+  float *d_bm_coefs = nullptr;
+  uint8_t *d_bm_side = nullptr, *d_bm_cand_side = nullptr;
+  int64_t bm_units = 0;
   // Tail overlap: the exact redo of a speculative chunk -- short lists, latency-bound launches -- runs on
   // s_tail while the next chunk's (or, on a context that owns its stream, the next call's) main kernels run on the
   // context's stream; the two chunks work on different halves of the workspace.  ev_main[p] / ev_tail[p]: main part /
@@ -553,6 +558,11 @@ void free_workspace(c1_ctx *ctx) {
   if (ctx->d_trial) (void)hipFree(ctx->d_trial);
   ctx->d_trial = nullptr;
   ctx->trial_units = ctx->trial_n = 0;
+  if (ctx->d_bm_coefs) (void)hipFree(ctx->d_bm_coefs);
+  if (ctx->d_bm_side) (void)hipFree(ctx->d_bm_side);
+  if (ctx->d_bm_cand_side) (void)hipFree(ctx->d_bm_cand_side);
+  ctx->d_bm_coefs = nullptr; ctx->d_bm_side = nullptr; ctx->d_bm_cand_side = nullptr;
+  ctx->bm_units = 0;
 }
 
 int ensure_detect_workspace(c1_ctx *ctx, int64_t units) {
@@ -603,10 +613,14 @@ constexpr size_t kWsBytesPerUnit = 512 * sizeof(float) + kSideBytes + kAllocByte
 constexpr size_t kDetectWsBytesPerUnit = 512 * sizeof(float) + kFeatureWsDoubles * sizeof(double) + 1 + 3 * sizeof(uint32_t);
 // trial_n > 0 (c1_encode_best_bias_device): that many trial allocation records per unit on top (one set: only the second half
 // of the pipeline touches them)
-int64_t chunk_for_call(c1_ctx *ctx, int64_t frames, int channels, bool detect, int trial_n = 0) {
+// best_modes (c1_encode_best_modes_device): the second analysis' coefficients and side records and one candidate's side records
+// on top (one set: such a call is not pipelined)
+constexpr size_t kBestModesWsBytesPerUnit = 512 * sizeof(float) + 2 * kSideBytes;
+int64_t chunk_for_call(c1_ctx *ctx, int64_t frames, int channels, bool detect, int trial_n = 0, bool best_modes = false) {
   const int64_t want = std::min(frames, ctx->chunk_frames);
   const bool trial_fits = trial_n == 0 || (want * channels <= ctx->trial_units && trial_n <= ctx->trial_n);
-  if (want * channels <= ctx->ws_units && (!detect || want * channels <= ctx->det_units) && trial_fits) return want;
+  if (want * channels <= ctx->ws_units && (!detect || want * channels <= ctx->det_units) && trial_fits &&
+      (!best_modes || want * channels <= ctx->bm_units)) return want;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return std::min<int64_t>(want, 1048576); }
   const size_t sets = (ctx->pipeline || ctx->overlap) ? 2 : 1, det_sets = ctx->pipeline ? 2 : 1;
@@ -614,6 +628,7 @@ int64_t chunk_for_call(c1_ctx *ctx, int64_t frames, int channels, bool detect, i
   size_t per_unit = kWsBytesPerUnit * sets;
   if (detect) { avail += (size_t)ctx->det_units * kDetectWsBytesPerUnit * det_sets; per_unit += kDetectWsBytesPerUnit * det_sets; }
   if (trial_n > 0) { avail += (size_t)ctx->trial_units * ctx->trial_n * kAllocBytes; per_unit += (size_t)trial_n * kAllocBytes; }
+  if (best_modes) { avail += (size_t)ctx->bm_units * kBestModesWsBytesPerUnit; per_unit += kBestModesWsBytesPerUnit; }
   const int64_t fit = (int64_t)((double)avail * 0.9 / (double)per_unit) / channels;
   return std::max<int64_t>(16, std::min(want, fit));
 }
@@ -739,6 +754,30 @@ int ensure_trial_allocs(c1_ctx *ctx, int64_t units, int n) {
   return C1_OK;
 }
 
+// the second analysis' planes and one candidate's side records of one chunk (c1_encode_best_modes_device)
+int ensure_best_modes_planes(c1_ctx *ctx, int64_t units) {
+  if (units <= ctx->bm_units) return C1_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  if (ctx->d_bm_coefs) (void)hipFree(ctx->d_bm_coefs);
+  if (ctx->d_bm_side) (void)hipFree(ctx->d_bm_side);
+  if (ctx->d_bm_cand_side) (void)hipFree(ctx->d_bm_cand_side);
+  ctx->d_bm_coefs = nullptr; ctx->d_bm_side = nullptr; ctx->d_bm_cand_side = nullptr; ctx->bm_units = 0;
+  HIP_TRY(hipMalloc(&ctx->d_bm_coefs, (size_t)units * 512 * sizeof(float)));
+  HIP_TRY(hipMalloc(&ctx->d_bm_side, (size_t)units * kSideBytes));
+  HIP_TRY(hipMalloc(&ctx->d_bm_cand_side, (size_t)units * kSideBytes));
+  ctx->bm_units = units;
+  return C1_OK;
+}
+
+// One call of c1_encode_best_modes_device: the candidates (host memory, in the domain, distinct) and the call's outputs (device
+// memory, each may be null)
+struct BestModesCall {
+  int n;
+  const uint8_t *cand;
+  uint8_t *choice, *modes_out;
+  double *distortion, *energy;
+};
+
 // One call of c1_encode_best_bias_device: the palette's size and the call's outputs (device memory, each may be null)
 struct BestBiasCall {
   int n;
@@ -838,7 +877,7 @@ int check_mode_bytes(const char *what, const uint8_t *modes, int64_t frames, int
 int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                        const c1_encode_options *opts, uint8_t *units, float *bands, float *coefs_tap,
                        uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr,
-                       const PaletteCall *pal = nullptr, const BestBiasCall *best = nullptr) {
+                       const PaletteCall *pal = nullptr, const BestBiasCall *best = nullptr, const BestModesCall *bm = nullptr) {
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx, false);
   if (rc) return rc;
@@ -856,9 +895,9 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   // given_modes (c1_encode_modes_device): one mode byte per unit on the device instead of the detector's decision.  The call
   // is laid out like a detection call (bands, mode bytes and unit lists in the detection workspace); of `opts` only the
   // biased scale factors reach a kernel that runs
-  const bool detect = given_modes || opts->fixed_block_modes[0] < 0;
+  const bool detect = given_modes || bm || opts->fixed_block_modes[0] < 0;
   const bool taps = coefs_tap || side_tap || alloc_tap;
-  const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect, best ? best->n : 0);
+  const int64_t chunk = taps ? ctx->chunk_frames : chunk_for_call(ctx, frames, channels, detect, best ? best->n : (bm ? bm->n : 0), bm != nullptr);
   if ((rc = ensure_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
   if (detect && (rc = ensure_detect_workspace(ctx, (taps ? frames : std::min(frames, chunk)) * channels))) return rc;
   // pal (c1_encode_biases_device): the allocation of every chunk runs once per palette entry over that entry's units, from
@@ -867,6 +906,17 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   // best (c1_encode_best_bias_device): the allocation of every chunk runs once per palette entry over ALL its units into that
   // entry's trial records; k_choose_bias measures every (unit, entry) and leaves the winner's record where packing reads it
   if (best && (rc = ensure_trial_allocs(ctx, std::min(frames, chunk) * channels, best->n))) return rc;
+  // bm (c1_encode_best_modes_device): the front end of given_modes under a constant byte, at most twice (all long into the
+  // chunk's workspace, all short into planes of its own); per candidate its side record composed from the two and the allocation
+  // run over all units into the candidate's trial records; k_choose_modes measures every (unit, candidate) and leaves the
+  // winner's coefficients, side record and allocation where packing reads them.  One workspace half: not pipelined
+  if (bm && (rc = ensure_trial_allocs(ctx, std::min(frames, chunk) * channels, bm->n))) return rc;
+  if (bm && (rc = ensure_best_modes_planes(ctx, std::min(frames, chunk) * channels))) return rc;
+  bool bm_long = false, bm_short = false;                     // some candidate codes a band long / short
+  for (int k = 0; bm && k < bm->n; k++) {
+    if ((bm->cand[k] & 0x3f) != 0x3a) bm_long = true;
+    if ((bm->cand[k] & 0x3f) != 0) bm_short = true;
+  }
   if (taps && (!coefs_tap || !side_tap || !alloc_tap)) return fail(C1_ERR_ARG, "coefs, side and alloc taps must be given together");
   if (taps && frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "stage taps are not chunked: at most %lld frames per call", (long long)kMaxChunkFrames);
   // Two-stage software pipeline over chunks: the analysis of chunk i+1 (fp64-VALU bound) runs on one
@@ -876,10 +926,10 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
                               opts->fixed_block_modes[2] == 0 && !getenv("C1_NO_FAST_LONG");
   const bool all_short_modes = !detect && opts->fixed_block_modes[0] != 0 && opts->fixed_block_modes[1] != 0 &&
                                opts->fixed_block_modes[2] != 0;
-  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && !best && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
+  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && !best && !bm && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
   bool quantize32 = !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;   // exact coefficients, binary32 quantization with the guard (below)
   static const bool det_spec_env_off = getenv("C1_DETECT_SPEC") && atoi(getenv("C1_DETECT_SPEC")) == 0;   // experiments: exact detector, the rest as usual
-  bool detect_spec = detect && !given_modes && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
+  bool detect_spec = detect && !given_modes && !bm && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
   // A call of a few frames (a frame closure, a short streaming push) is bound by the number of launches behind it, and
   // every speculative shortcut adds some (the redo chain, the recheck, the second packing pass): in the default mode such
   // calls take the exact kernels (one mono frame: 159 against 185 us, tools/latency_probe.py).  A rule on the size of
@@ -893,7 +943,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   // turns every shortcut off for a stream that is known to defeat them; the bytes are the same either way.
   const bool overlap = speculate && ctx->overlap && ctx->s_tail != nullptr;
   if (!overlap && (rc = join_tail(ctx))) return rc;       // every other path works on the context's stream alone
-  const bool piped = ctx->pipeline && !taps && frames > chunk && !speculate;
+  const bool piped = ctx->pipeline && !taps && frames > chunk && !speculate && !bm;
   hipStream_t sA = piped ? ctx->s_ana : ctx->stream, sB = piped ? ctx->s_rest : ctx->stream;
   if (piped) {
     HIP_TRY(hipEventRecord(ctx->ev_in, ctx->stream));
@@ -1014,7 +1064,20 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
     {
       ScopedTiming t(ctx, K_ANALYSIS, sA);
       if (all_long) c1k_launch_analysis_long(L, sA);
-      else if (given_modes) {
+      else if (bm) {
+        // the band samples once; the all-long analysis into the chunk's planes and the all-short one into the call's own.  The
+        // constant bytes of the front end's input lie in the candidate side plane, which is composed only after this
+        C1EncodeLaunch S2 = L;
+        S2.coefs = ctx->d_bm_coefs;
+        S2.side = ctx->d_bm_side;
+        HIP_TRY(hipMemsetAsync(ctx->d_bm_cand_side, bm_long ? 0 : 0x3a, (size_t)n * channels, sA));
+        c1k_launch_modes_front(L, ctx->d_bm_cand_side, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
+        c1k_launch_mdct_bands(bm_long ? L : S2, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
+        if (bm_long && bm_short) {
+          c1k_launch_const_mode_lists(0x3a, n * channels, ctx->d_modes[p], ctx->d_lists[p], sA);
+          c1k_launch_mdct_bands(S2, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
+        }
+      } else if (given_modes) {
         c1k_launch_modes_front(L, given_modes + f0 * channels, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
         c1k_launch_mdct_bands(L, ctx->d_bands[p], ctx->d_modes[p], ctx->d_lists[p], sA);
       } else if (detect) {
@@ -1028,7 +1091,22 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       HIP_TRY(hipEventRecord(ctx->ev_ana[p], sA));
       HIP_TRY(hipStreamWaitEvent(sB, ctx->ev_ana[p], 0));
     }
-    if (best) {
+    if (bm) {
+      const int64_t trial_stride = ctx->trial_units * kAllocBytes;
+      for (int k = 0; k < bm->n; k++) {                          // one chain after the other: they share the side plane and the scratch
+        { ScopedTiming t(ctx, K_ANALYSIS, sB); c1k_launch_compose_side(L.side, ctx->d_bm_side, n * channels, bm->cand[k], ctx->d_bm_cand_side, sB); }
+        ScopedTiming t(ctx, K_ALLOCATE, sB);
+        C1EncodeLaunch A = L;
+        A.side = ctx->d_bm_cand_side;
+        A.alloc = ctx->d_trial + (size_t)k * trial_stride;
+        c1k_launch_allocate(A, sB);
+      }
+      ScopedTiming t(ctx, K_CHOOSE, sB);
+      c1k_launch_choose_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, L.units != nullptr,
+                              bm->choice ? bm->choice + f0 * channels : nullptr, bm->modes_out ? bm->modes_out + f0 * channels : nullptr,
+                              bm->distortion ? bm->distortion + f0 * channels * bm->n : nullptr,
+                              bm->energy ? bm->energy + f0 * channels * bm->n : nullptr, sB);
+    } else if (best) {
       const int64_t trial_stride = ctx->trial_units * kAllocBytes;
       {
         ScopedTiming t(ctx, K_ALLOCATE, sB);
@@ -2497,6 +2575,107 @@ int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels
   if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
   if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_palette * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// host only: the number of candidates, every byte's domain (as check_mode_bytes), no byte twice
+static int check_mode_candidates(const char *what, const uint8_t *cand, int n) {
+  static const char *const kField[3] = {"low", "mid", "high"};
+  if (n < 1 || n > C1_MAX_MODE_CANDIDATES) return fail(C1_ERR_ARG, "%s: n_cand = %d is outside 1..%d", what, n, C1_MAX_MODE_CANDIDATES);
+  if (!cand) return fail(C1_ERR_ARG, "%s: cand_modes is NULL", what);
+  for (int i = 0; i < n; i++) {
+    const int b = cand[i];
+    for (int k = 0; k < 3; k++) {
+      const int m = (b >> (2 * k)) & 3, other = k == 2 ? 3 : 2;
+      if (m != 0 && m != other)
+        return fail(C1_ERR_ARG, "%s: candidate %d: %s field of mode byte 0x%02x is %d, not 0 or %d", what, i, kField[k], b, m, other);
+    }
+    if (b & 0xc0) return fail(C1_ERR_ARG, "%s: candidate %d: bits 6-7 of mode byte 0x%02x are set", what, i, b);
+    for (int j = 0; j < i; j++)
+      if (cand[j] == b) return fail(C1_ERR_ARG, "%s: candidate %d: mode byte 0x%02x is candidate %d's", what, i, b, j);
+  }
+  return C1_OK;
+}
+
+int c1_encode_best_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, uint8_t *units,
+                                uint8_t *choice, uint8_t *modes_out, double *distortion, double *energy) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_mode_candidates("c1_encode_best_modes_device", cand_modes, n_cand))) return rc;
+  if (!units && !choice && !modes_out && !distortion && !energy)
+    return fail(C1_ERR_ARG, "c1_encode_best_modes_device: units, choice, modes_out, distortion and energy are all NULL");
+  if (!opts) return fail(C1_ERR_ARG, "options are NULL");
+  c1_encode_options base = *opts;                              // of the options only the biased scale factors are read
+  base.transient_threshold = 1.0;
+  base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  BestModesCall mc = {n_cand, nullptr, choice, modes_out, distortion, energy};
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's array may change once the call has returned
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  mc.cand = cand;
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            nullptr, nullptr, nullptr, &mc);
+}
+
+int c1_encode_best_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                               const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, uint8_t *units,
+                               uint8_t *choice, uint8_t *modes_out, double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_mode_candidates("c1_encode_best_modes_batch", cand_modes, n_cand))) return rc;
+  if (!units && !choice && !modes_out && !distortion && !energy)
+    return fail(C1_ERR_ARG, "c1_encode_best_modes_batch: units, choice, modes_out, distortion and energy are all NULL");
+  if (!opts) return fail(C1_ERR_ARG, "options are NULL");
+  {
+    c1_encode_options base = *opts;
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+    std::unique_ptr<C1DevEncOpts> d(new C1DevEncOpts);
+    if ((rc = build_encode_opts(base, d.get()))) return rc;
+  }
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "c1_encode_best_modes_batch: no HIP device available; this library has no CPU path"); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), choice_off = up256(unit_off + n_units * C1_UNIT_BYTES), modes_off = up256(choice_off + n_units),
+               dist_off = up256(modes_off + n_units), energy_off = up256(dist_off + n_units * n_cand * sizeof(double));
+  if ((rc = ensure_io(ctx, energy_off + n_units * n_cand * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_choice = (uint8_t *)ctx->d_io + choice_off, *d_modes = (uint8_t *)ctx->d_io + modes_off;
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off);
+  if ((rc = c1_encode_best_modes_device(ctx, dptr, channels, frames, halo_frames, opts, cand_modes, n_cand, units ? d_units : nullptr,
+                                        choice ? d_choice : nullptr, modes_out ? d_modes : nullptr, distortion ? d_dist : nullptr,
+                                        energy ? d_energy : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (modes_out) HIP_TRY(hipMemcpyAsync(modes_out, d_modes, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }

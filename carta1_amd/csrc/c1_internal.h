@@ -323,6 +323,21 @@ void c1k_launch_allocate_palette(const C1EncodeLaunch &L, const C1DevEncOpts *pa
 // may each be null.  all_long: every unit has modes [0,0,0] (the side records' mode byte is not read)
 void c1k_launch_choose_bias(const C1EncodeLaunch &L, const uint8_t *trial, int64_t trial_stride, int n_palette, bool all_long,
                             uint8_t *choice, double *distortion, double *energy, hipStream_t stream);
+// the block modes chosen per unit by least coding error (c1_k_choose_modes.hip).  Every unit under one mode byte: the byte into
+// modes_ws and the unit into k_mdct_bands' all-long (byte 0) or mixed list, as k_modes_lists would leave them
+void c1k_launch_const_mode_lists(int byte, int64_t units, uint8_t *modes_ws, uint32_t *lists_ws, hipStream_t stream);
+// out = per unit the side record of mode byte `byte`: the scale-factor indices of a band from side_short where the byte codes it
+// short, else from side_long (the records of the all-short and the all-long analysis), and the byte itself
+void c1k_launch_compose_side(const uint8_t *side_long, const uint8_t *side_short, int64_t units, int byte, uint8_t *out, hipStream_t stream);
+// L.coefs / L.side: the all-long analysis, coefs_short / side_short: the all-short one (a plane no candidate needs is not read);
+// trial as for c1k_launch_choose_bias, entry k allocated from candidate k's composed side record; cand: n_cand (1 ..
+// C1_MAX_MODE_CANDIDATES) HOST bytes of the domain.  Per unit D(u, k) and E(u, k) (weighted, include/carta1_hip.h), choice = the
+// smallest k of least D, modes_out = its byte; finalize: the winner's allocation, side record and coefficients are left in
+// L.alloc, L.side and L.coefs, where the packing kernels read them.  choice, modes_out (units), distortion and energy (units *
+// n_cand, unit-major) may each be null
+void c1k_launch_choose_modes(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
+                             int64_t trial_stride, const uint8_t *cand, int n_cand, bool finalize, uint8_t *choice, uint8_t *modes_out,
+                             double *distortion, double *energy, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -348,6 +348,49 @@ napi_value EncodeBestBias(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// encodeBestModes(ctx, [Float32Array...], haloFrames, options, Uint8Array candidates)
+// -> { units: Uint8Array(frames*channels*212), choice, modes: Uint8Array(frames*channels), distortion, energy:
+// Float64Array(frames*channels*n) (unit-major) }: c1_encode_best_modes_batch, n = 1..8 distinct mode bytes; of the options only
+// the bias is used
+napi_value EncodeBestModes(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_cand = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *cand;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o) || !get_typed(env, argv[4], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  if (n_cand < 1 || n_cand > C1_MAX_MODE_CANDIDATES) { napi_throw_range_error(env, nullptr, "candidates must hold 1 to 8 mode bytes"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  uint8_t *units, *choice, *modes;
+  napi_value out_units = make_u8(env, n_units * C1_UNIT_BYTES, &units), out_choice = make_u8(env, n_units, &choice), out_modes = make_u8(env, n_units, &modes);
+  if (!out_units || !out_choice || !out_modes) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  napi_value ab_d, ab_e, out_dist, out_energy;
+  void *dist, *energy;
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * sizeof(double), &dist, &ab_d));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand, ab_d, 0, &out_dist));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * sizeof(double), &energy, &ab_e));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand, ab_e, 0, &out_energy));
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_best_modes_batch(ctx, p, (int)ch.size(), frames, halo, &o, static_cast<const uint8_t *>(cand), (int)n_cand, units, choice,
+                                            modes, static_cast<double *>(dist), static_cast<double *>(energy));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_set_named_property(env, obj, "units", out_units));
+  NAPI_OK(napi_set_named_property(env, obj, "choice", out_choice));
+  NAPI_OK(napi_set_named_property(env, obj, "modes", out_modes));
+  NAPI_OK(napi_set_named_property(env, obj, "distortion", out_dist));
+  NAPI_OK(napi_set_named_property(env, obj, "energy", out_energy));
+  return obj;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1149,6 +1192,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeBatchModes", nullptr, EncodeBatchModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatchBiases", nullptr, EncodeBatchBiases, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBestBias", nullptr, EncodeBestBias, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeBestModes", nullptr, EncodeBestModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -41,12 +41,33 @@ export async function encodeAeaPcm(channels, options = {}) {
   // difference between the coefficient and what the decoder dequantizes (c1_encode_best_bias_batch).  Each value is
   // range-checked as allocationBias is, their tables from this engine's Math.pow.  Combines with blockModes; mutually
   // exclusive with allocationBiases (TypeError); devices is not used
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, ...encoderValues } = options
+  // options.blockModeCandidates (not in the reference): an array or Uint8Array of 1 to 8 distinct mode bytes (or triples [low,
+  // mid, high]): every sound unit is encoded under the candidate that leaves the least coding error, the squared differences
+  // weighted by the transform's scaling so that long and short blocks compare as their PCM error does
+  // (c1_encode_best_modes_batch).  The detector does not run; mutually exclusive with blockModes and with
+  // allocationBiasCandidates (TypeError), and allocationBiases and devices are not used
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
   if (haveCandidates && allocationBiases !== undefined && allocationBiases !== null) {
     throw new TypeError('allocationBiases and allocationBiasCandidates are mutually exclusive: give the bias of every frame, or the candidates to choose among')
+  }
+  const haveModeCandidates = blockModeCandidates !== undefined && blockModeCandidates !== null
+  if (haveModeCandidates && blockModes !== undefined && blockModes !== null) {
+    throw new TypeError('blockModes and blockModeCandidates are mutually exclusive: give the modes of every frame, or the candidates to choose among')
+  }
+  if (haveModeCandidates && haveCandidates) {
+    throw new TypeError('blockModeCandidates and allocationBiasCandidates are mutually exclusive: one search per call')
+  }
+  if (haveModeCandidates && allocationBiases !== undefined && allocationBiases !== null) {
+    throw new TypeError('blockModeCandidates and allocationBiases are mutually exclusive: the candidates are measured under one allocationBias')
+  }
+  if (haveModeCandidates) {
+    const n = blockModeCandidates.length
+    if (!(Array.isArray(blockModeCandidates) || blockModeCandidates instanceof Uint8Array) || n < 1 || n > 8) {
+      throw new RangeError(`blockModeCandidates must hold 1 to 8 mode bytes, got ${n}`)
+    }
   }
   let candidates = null
   if (haveCandidates) {
@@ -98,7 +119,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && candidates) {
+  if (frames > 0 && haveModeCandidates) {
+    image.set(encodeBestModes(padded, encoderOptions.toNative(), blockModeCandidates).units, AEA_HEADER_SIZE)
+  } else if (frames > 0 && candidates) {
     image.set(encodeBestBias(padded, candidates, blockModes || null).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && palette) {
     image.set(encodeBatchBiases(padded, biasIndex, palette, blockModes || null), AEA_HEADER_SIZE)

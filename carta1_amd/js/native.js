@@ -69,3 +69,22 @@ export function encodeBestBias(channels, optionSets, modes = null, haloFrames = 
   }
   return native().encodeBestBias(ctx, channels, haloFrames, palette, modes)
 }
+
+// c1_encode_best_modes_batch on the default context: encode() with the block modes of every sound unit chosen among the
+// candidates by least coding error -- the sum over the unit's 512 MDCT coefficients of W * (c - d)^2, d what the decoder's
+// dequantizationStage makes of the unit and W the transform's scaling (1 long, 1/4 low or mid short, 1/2 high short).
+// nativeOptions: EncoderOptions.toNative(), of which only the allocation bias is used; candidates: 1 .. 8 distinct mode bytes
+// as for encodeBatchModes (a Uint8Array or an array; an entry may be a triple [low, mid, high]).  Returns { units, choice:
+// Uint8Array(frames * channels) indexing candidates, modes: Uint8Array(frames * channels) the chosen bytes, distortion and
+// energy: Float64Array(frames * channels * n) unit-major }.
+export function encodeBestModes(channels, nativeOptions, candidates, haloFrames = 0, ctx = context()) {
+  const bytes = Uint8Array.from(Array.from(candidates), (c) => {
+    if (Array.isArray(c)) {
+      if (c.length !== 3 || c.some((m) => !Number.isInteger(m) || m < 0 || m > 3)) throw new TypeError('candidates: a triple holds three block modes 0..3')
+      return c[0] | (c[1] << 2) | (c[2] << 4)
+    }
+    if (!Number.isInteger(c) || c < 0 || c > 255) throw new TypeError('candidates: mode bytes 0..255 or triples [low, mid, high]')
+    return c
+  })
+  return native().encodeBestModes(ctx, channels, haloFrames, nativeOptions, bytes)
+}

@@ -299,6 +299,59 @@ int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels
                               uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
                               double *distortion /* host, or NULL */, double *energy /* host, or NULL */);
 
+/* ---- encode with the block modes of every sound unit chosen from candidates by least coding error -------------------------
+ * The reference sets the block modes open loop: its transient detector never sees the coded result, and c1_encode_modes_*
+ * takes them from a caller who must already know them.  This call measures them.  cand_modes: n_cand (1 ..
+ * C1_MAX_MODE_CANDIDATES) distinct mode bytes of the domain of c1_encode_modes_* (low and mid fields 0 or 2, high field 0 or
+ * 3, bits 6-7 clear) in HOST memory, in the caller's order; choice indexes them.  Both calls check the bytes (the array is
+ * host memory in both): a byte outside the domain, a duplicate, or n_cand outside 1..8 returns C1_ERR_ARG naming the entry,
+ * and nothing is written.  Of opts only biased_scale_factors is read; the detector never runs and a stream's detection
+ * history is not involved.  Per (unit u, candidate k), in binary64,
+ *     D(u,k) = sum_i W(band(i), mode_k(band(i))) * (c_k[i] - d_k[i])^2
+ *     E(u,k) = sum_i W(band(i), mode_k(band(i))) * c_k[i]^2                    i = 0 .. 511
+ * where c_k are the Float32 MDCT coefficients quantizationStage receives (encoder.js:365) when fixedBlockModes = candidate k
+ * was set before the frame, d_k what dequantizationStage (decoder.js:52-98) makes of the sound unit the reference writes for
+ * that frame under candidate k and opts' bias (zero where a BFU is at or above the unit's amount or has word length 0), band(i)
+ * is low for i < 128, mid for i < 256 and high otherwise, and W is 1 for a band coded long, 1/4 for the low or mid band coded
+ * short and 1/2 for the high band coded short: the reference's short transforms carry 4 (low, mid) and 2 (high) times the
+ * energy of its long ones for the same signal (mdct.js:215-221), so the weighted error is the PCM error energy up to one
+ * constant and the D of different candidates, and of separate calls, are comparable.  A candidate's coefficients are those of
+ * the frame whatever modes the frames before it took (applyTailWindowing, encoder.js:309-316, saves the same windowed tail
+ * for a long and a short band), so nothing is carried from frame to frame by the choice.  choice[u] is the smallest k with
+ * D(u,k) <= D(u,j) for all j, on the values computed: a NaN never wins, and if every D is NaN the choice is 0.
+ * modes_out[u] = cand_modes[choice[u]].  The order of the sums is fixed (a lane's 8 BFU-major slots in order, the lane's sum
+ * times W -- a power of two, so that is the sum of the weighted terms bit for bit -- then one tree over the 64 lanes), no
+ * fused operation is used, and the same inputs give the same bits run after run.  units[u] are exactly the bytes of
+ * c1_encode_modes_* with modes[u] = modes_out[u] and the same opts, packed by the same kernels.  Each output may be NULL
+ * (units NULL: measure only, no packing runs); all five NULL is C1_ERR_ARG.  distortion and energy are unit-major: D(u,k) at
+ * [u * n_cand + k].  With one candidate the call is c1_encode_modes_* under a constant byte plus its quality report.
+ * Limits, alignment, chunking, asynchrony and the caller's-stream contract are those of c1_encode_best_bias_device; no output
+ * depends on the speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP or the halo.  The device path
+ * runs the exact analysis at most twice (all long, all short: a band's coefficients and scale-factor indices depend on that
+ * band's mode only), one allocation per candidate, and one measuring kernel.  Workspace: 2.2 KB per unit (the second
+ * analysis) and 32 bytes per unit and candidate on top of a c1_encode_modes_device call's.  c1_ctx_kernel_ms counts the
+ * analyses and the composing of the candidates' side records under "analysis", the trial allocations under "allocate" and
+ * the measuring kernel under "choose".
+ * A joint search over modes and biases composes from separate calls, because their weighted D are comparable: one
+ * measure-only call per bias, the least D per unit over all of them, then one c1_encode_biases_* call with the winning
+ * modes and bias_index. */
+#define C1_MAX_MODE_CANDIDATES 8
+int c1_encode_best_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
+                                uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                                uint8_t *choice /* device, frames*channels, or NULL */,
+                                uint8_t *modes_out /* device, frames*channels, or NULL: cand_modes[choice[u]] */,
+                                double *distortion /* device, frames*channels*n_cand (unit-major), or NULL */,
+                                double *energy /* device, frames*channels*n_cand (unit-major), or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The candidates and the outputs are validated before the context is looked
+ * at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a device the call then returns
+ * C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per channel. */
+int c1_encode_best_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                               const c1_encode_options *opts, const uint8_t *cand_modes /* host */, int n_cand,
+                               uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
+                               uint8_t *modes_out /* host, or NULL */, double *distortion /* host, or NULL */,
+                               double *energy /* host, or NULL */);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
