@@ -301,6 +301,33 @@ class Context:
                                                           None if energy is None else energy.ctypes.data))
         return (units, choice, modes, dist, energy) if return_distortion else (units, choice, modes)
 
+    def encode_measured(self, channels, modes=None, options=None, halo_frames=0, return_distortion=False):
+        """encode() with the word lengths of every sound unit allocated by the measured coding error instead of the reference's
+        model of it (c1_encode_measured_batch; opt-in: the units are not the reference encoder's, but ordinary sound units with
+        its block modes and scale factors that its decode() reads).  Per unit a greedy allocation over the W-weighted error of
+        every (BFU, word length) is compared with the reference's own record; taken[u] = 1 where the greedy one codes with less
+        error and was packed, 0 where the unit is byte for byte encode()'s / encode_modes()'s.  modes: None (detection or fixed
+        modes as `options` say) or mode bytes as for encode_modes().  Returns (units, taken uint8 [units]), and with
+        return_distortion (units, taken, distortion float64 [units, 2]: the reference record's error and the greedy one's,
+        energy float64 [units])."""
+        opts = (options or EncoderOptions()).to_c()
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = max(n // 512 - halo_frames, 0)
+        m = None if modes is None else check_block_modes(modes, frames, len(chans))
+        units = np.zeros((frames * len(chans), 212), dtype=np.uint8)
+        taken = np.zeros(frames * len(chans), dtype=np.uint8)
+        dist = np.zeros((frames * len(chans), 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros(frames * len(chans), dtype=np.float64) if return_distortion else None
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_measured_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts),
+                                                        None if m is None else m.ctypes.data, units.ctypes.data, taken.ctypes.data,
+                                                        None if dist is None else dist.ctypes.data,
+                                                        None if energy is None else energy.ctypes.data))
+        return (units, taken, dist, energy) if return_distortion else (units, taken)
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -361,6 +388,17 @@ class Context:
         capi.check(capi.load().c1_encode_best_modes_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                            C.byref(opts), cand.ctypes.data, len(cand), vp(units_ptr), vp(choice_ptr),
                                                            vp(modes_ptr), vp(distortion_ptr), vp(energy_ptr)))
+
+    def encode_measured_device(self, pcm_ptrs, frames, units_ptr=None, taken_ptr=None, distortion_ptr=None, energy_ptr=None,
+                               modes_ptr=None, options=None, halo_frames=0):
+        """c1_encode_measured_device: outputs on the device, each may be None (units_ptr None: measure only), not all; taken is
+        uint8 [units], distortion float64 [units, 2], energy float64 [units]; modes_ptr = mode bytes on the device as for
+        encode_modes_device, or None."""
+        opts = (options or EncoderOptions()).to_c()
+        vp = lambda p: C.c_void_p(p) if p else None
+        capi.check(capi.load().c1_encode_measured_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                         C.byref(opts), vp(modes_ptr), vp(units_ptr), vp(taken_ptr),
+                                                         vp(distortion_ptr), vp(energy_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,

@@ -411,8 +411,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_CHOOSE, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts", "choose"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_CHOOSE, K_MEASURE, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts", "choose", "measure"};
 
 }  // namespace
 
@@ -707,6 +707,21 @@ int check_palette(const char *what, const c1_encode_options *palette, int n, boo
   return C1_OK;
 }
 
+// host only: the options of a measured-allocation call, as upload_opts will judge them (call_fields false: modes are given, and
+// neither the threshold nor the fixed modes are read)
+int check_measured_opts(const char *what, const c1_encode_options *opts, bool call_fields) {
+  if (!opts) return fail(C1_ERR_ARG, "%s: options are NULL", what);
+  std::unique_ptr<C1DevEncOpts> d(new C1DevEncOpts);
+  c1_encode_options o = *opts;
+  if (!call_fields) {
+    o.transient_threshold = 1.0;
+    o.fixed_block_modes[0] = o.fixed_block_modes[1] = o.fixed_block_modes[2] = -1;
+  }
+  const int rc = build_encode_opts(o, d.get());
+  if (rc) { const std::string inner = g_error; return fail(rc, "%s: %s", what, inner.c_str()); }
+  return C1_OK;
+}
+
 int upload_palette(c1_ctx *ctx, const char *what, const c1_encode_options *palette, int n) {
   bool same = ctx->d_palette && ctx->pal_n >= n;
   for (int k = 0; k < n && same; k++) same = memcmp(ctx->pal_tables[k], palette[k].biased_scale_factors, sizeof ctx->pal_tables[k]) == 0;
@@ -782,6 +797,12 @@ struct BestModesCall {
 struct BestBiasCall {
   int n;
   uint8_t *choice;
+  double *distortion, *energy;
+};
+
+// One call of c1_encode_measured_device: the call's outputs (device memory, each may be null)
+struct MeasuredCall {
+  uint8_t *taken;
   double *distortion, *energy;
 };
 
@@ -877,7 +898,8 @@ int check_mode_bytes(const char *what, const uint8_t *modes, int64_t frames, int
 int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                        const c1_encode_options *opts, uint8_t *units, float *bands, float *coefs_tap,
                        uint8_t *side_tap, uint8_t *alloc_tap, bool lazy = false, const uint8_t *given_modes = nullptr,
-                       const PaletteCall *pal = nullptr, const BestBiasCall *best = nullptr, const BestModesCall *bm = nullptr) {
+                       const PaletteCall *pal = nullptr, const BestBiasCall *best = nullptr, const BestModesCall *bm = nullptr,
+                       const MeasuredCall *mc = nullptr) {
   CTX_GUARD(ctx);
   int rc = ctx_bind(ctx, false);
   if (rc) return rc;
@@ -926,7 +948,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
                               opts->fixed_block_modes[2] == 0 && !getenv("C1_NO_FAST_LONG");
   const bool all_short_modes = !detect && opts->fixed_block_modes[0] != 0 && opts->fixed_block_modes[1] != 0 &&
                                opts->fixed_block_modes[2] != 0;
-  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && !best && !bm && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
+  bool speculate = (all_long_modes || all_short_modes) && !taps && !pal && !best && !bm && !mc && units && ctx->spec_tables_ok && ctx->spec_mode != 0;
   bool quantize32 = !taps && units && ctx->spec_tables_ok && ctx->spec_mode != 0;   // exact coefficients, binary32 quantization with the guard (below)
   static const bool det_spec_env_off = getenv("C1_DETECT_SPEC") && atoi(getenv("C1_DETECT_SPEC")) == 0;   // experiments: exact detector, the rest as usual
   bool detect_spec = detect && !given_modes && !bm && !taps && ctx->spec_tables_ok && ctx->spec_mode != 0 && !det_spec_env_off;   // binary32 transient detector with a score interval
@@ -1125,6 +1147,14 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       ScopedTiming t(ctx, K_ALLOCATE, sB);
       c1k_launch_allocate_palette(L, ctx->d_palette, pal->n, pal->index + f0 * channels, ctx->d_pal_lists, ctx->d_pal_lists + 8, n * channels, sB);
     } else { ScopedTiming t(ctx, K_ALLOCATE, sB); c1k_launch_allocate(L, sB); }
+    if (mc) {
+      // mc (c1_encode_measured_device): the allocation chain above left the reference's record of every unit; k_measured_alloc
+      // builds the unit's error table, allocates greedily by it, and replaces the record where that codes with less error
+      ScopedTiming t(ctx, K_MEASURE, sB);
+      c1k_launch_measured_alloc(L, all_long, L.units != nullptr, mc->taken ? mc->taken + f0 * channels : nullptr,
+                                mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
+                                mc->energy ? mc->energy + f0 * channels : nullptr, sB);
+    }
     if (L.units && quantize32) {
       // The coefficients are the reference's, and still the quantization need not be done in binary64: the packing
       // kernel of the speculative path with a bound of zero forms |x| norm + 0.5 in binary32 and accepts a mantissa only
@@ -2574,6 +2604,77 @@ int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels
   if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
   if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_palette * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_encode_measured_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                              const c1_encode_options *opts, const uint8_t *modes, uint8_t *units, uint8_t *taken,
+                              double *distortion, double *energy) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_device", opts, modes == nullptr))) return rc;
+  if (!units && !taken && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_measured_device: units, taken, distortion and energy are all NULL");
+  // with given modes neither threshold nor fixed modes are read
+  c1_encode_options base = *opts;
+  if (modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  const MeasuredCall mc = {taken, distortion, energy};
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            frames > 0 ? modes : nullptr, nullptr, nullptr, nullptr, &mc);
+}
+
+int c1_encode_measured_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                             const c1_encode_options *opts, const uint8_t *modes, uint8_t *units, uint8_t *taken,
+                             double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_batch", opts, modes == nullptr))) return rc;
+  if (!units && !taken && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_measured_batch: units, taken, distortion and energy are all NULL");
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if (modes && (rc = check_mode_bytes("c1_encode_measured_batch", modes, frames, channels))) return rc;
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "c1_encode_measured_batch: no HIP device available; this library has no CPU path"); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), mode_off = up256(unit_off + n_units * C1_UNIT_BYTES), taken_off = up256(mode_off + n_units),
+               dist_off = up256(taken_off + n_units), energy_off = up256(dist_off + n_units * 2 * sizeof(double));
+  if ((rc = ensure_io(ctx, energy_off + n_units * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_modes = (uint8_t *)ctx->d_io + mode_off, *d_taken = (uint8_t *)ctx->d_io + taken_off;
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off);
+  if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, n_units, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_measured_device(ctx, dptr, channels, frames, halo_frames, opts, modes ? d_modes : nullptr, units ? d_units : nullptr,
+                                      taken ? d_taken : nullptr, distortion ? d_dist : nullptr, energy ? d_energy : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;

@@ -338,6 +338,14 @@ void c1k_launch_compose_side(const uint8_t *side_long, const uint8_t *side_short
 void c1k_launch_choose_modes(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
                              int64_t trial_stride, const uint8_t *cand, int n_cand, bool finalize, uint8_t *choice, uint8_t *modes_out,
                              double *distortion, double *energy, hipStream_t stream);
+// the word lengths allocated by the measured coding error (c1_k_measured.hip; the definition is include/carta1_hip.h's).  L.coefs,
+// L.side: the analysis' planes; L.alloc: the record c1k_launch_allocate left for every unit.  Per unit the table e(b, w), the
+// greedy allocation for each of the eight amounts, T_ref over the record and T(n*) over the best greedy one; taken = T(n*) <
+// T_ref.  finalize: a taken unit's greedy record replaces the one in L.alloc, where the packing kernels read it; otherwise
+// L.alloc is left alone.  taken (units), distortion (units * 2: T_ref, T(n*)) and energy (units) may each be null.  all_long:
+// every unit has modes [0,0,0] (the side records' mode byte is not read)
+void c1k_launch_measured_alloc(const C1EncodeLaunch &L, bool all_long, bool finalize, uint8_t *taken, double *distortion, double *energy,
+                               hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

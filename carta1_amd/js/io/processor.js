@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -46,7 +46,11 @@ export async function encodeAeaPcm(channels, options = {}) {
   // weighted by the transform's scaling so that long and short blocks compare as their PCM error does
   // (c1_encode_best_modes_batch).  The detector does not run; mutually exclusive with blockModes and with
   // allocationBiasCandidates (TypeError), and allocationBiases and devices are not used
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, ...encoderValues } = options
+  // options.measuredAllocation (not in the reference): true allocates every sound unit's word lengths by the measured coding
+  // error instead of the reference's model of it, and keeps the reference's allocation where that codes better
+  // (c1_encode_measured_batch).  The units are not the reference encoder's, but decode() reads them.  Alone or with blockModes;
+  // mutually exclusive with allocationBiases, allocationBiasCandidates and blockModeCandidates (TypeError); devices is not used
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
@@ -67,6 +71,16 @@ export async function encodeAeaPcm(channels, options = {}) {
     const n = blockModeCandidates.length
     if (!(Array.isArray(blockModeCandidates) || blockModeCandidates instanceof Uint8Array) || n < 1 || n > 8) {
       throw new RangeError(`blockModeCandidates must hold 1 to 8 mode bytes, got ${n}`)
+    }
+  }
+  if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
+    throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
+  }
+  if (measuredAllocation) {
+    for (const [name, value] of [['allocationBiases', allocationBiases], ['allocationBiasCandidates', allocationBiasCandidates], ['blockModeCandidates', blockModeCandidates]]) {
+      if (value !== undefined && value !== null) {
+        throw new TypeError(`measuredAllocation and ${name} are mutually exclusive: the measured allocation replaces the search over the reference's options`)
+      }
     }
   }
   let candidates = null
@@ -119,7 +133,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && haveModeCandidates) {
+  if (frames > 0 && measuredAllocation) {
+    image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null).units, AEA_HEADER_SIZE)
+  } else if (frames > 0 && haveModeCandidates) {
     image.set(encodeBestModes(padded, encoderOptions.toNative(), blockModeCandidates).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && candidates) {
     image.set(encodeBestBias(padded, candidates, blockModes || null).units, AEA_HEADER_SIZE)

@@ -88,3 +88,14 @@ export function encodeBestModes(channels, nativeOptions, candidates, haloFrames 
   })
   return native().encodeBestModes(ctx, channels, haloFrames, nativeOptions, bytes)
 }
+
+// c1_encode_measured_batch on the default context: encode() with the word lengths of every sound unit allocated by the
+// measured coding error instead of the reference's model of it (opt-in: the units are not the reference encoder's, but ordinary
+// sound units with its block modes and scale factors that decode() reads).  nativeOptions: EncoderOptions.toNative(); modes:
+// null (detection or fixed modes as the options say) or mode bytes as for encodeBatchModes.  Returns { units, taken:
+// Uint8Array(frames * channels), 1 where the greedy allocation coded with less error than the reference's record and was packed,
+// 0 where the unit is byte for byte the plain encode's, distortion: Float64Array(frames * channels * 2), per unit the reference
+// record's weighted error and the greedy allocation's, energy: Float64Array(frames * channels) }.
+export function encodeMeasured(channels, nativeOptions, modes = null, haloFrames = 0, ctx = context()) {
+  return native().encodeMeasured(ctx, channels, haloFrames, nativeOptions, modes)
+}

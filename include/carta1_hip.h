@@ -334,7 +334,10 @@ int c1_encode_best_bias_batch(c1_ctx *ctx, const float *const *pcm, int channels
  * the measuring kernel under "choose".
  * A joint search over modes and biases composes from separate calls, because their weighted D are comparable: one
  * measure-only call per bias, the least D per unit over all of them, then one c1_encode_biases_* call with the winning
- * modes and bias_index. */
+ * modes and bias_index.  No entry point does it in one call, on purpose: on the CPU model the exhaustive 8 x 8 minimum
+ * beats the two-call sequence (best modes at bias 1, then the best bias under them) by 0.15 dB on pink noise with transients,
+ * 0.12 dB on white noise and 0.09 dB on a tonal and noise mix, which is not worth sixty-four allocation chains per unit.
+ * The larger lever is c1_encode_measured_* below. */
 #define C1_MAX_MODE_CANDIDATES 8
 int c1_encode_best_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                                 const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
@@ -351,6 +354,56 @@ int c1_encode_best_modes_batch(c1_ctx *ctx, const float *const *pcm, int channel
                                uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
                                uint8_t *modes_out /* host, or NULL */, double *distortion /* host, or NULL */,
                                double *energy /* host, or NULL */);
+
+/* ---- encode with the word lengths of every sound unit allocated by the measured coding error ------------------------------
+ * allocateBits (bitallocation.js:74-281) spends the 1696 - 40 - 10 nBfu mantissa bits of a unit by a model of the distortion,
+ * biased[sfi] * 2^-bits * size, and never sees the mantissas quantize produces; the bias only bends that model.  This call
+ * allocates by the error measured.  OPT-IN, and a new kind of output: the units are NOT those the reference's encoder writes.
+ * They are ordinary sound units all the same -- the reference's block modes and scale-factor indices, mantissas that are what
+ * quantize (quantization.js:34-56) gives at the chosen word lengths, serializeFrame's layout -- and the reference's decode()
+ * reads them.  Every other entry point stays bit-identical to the reference.
+ * Definition.  Take unit u with its block modes: modes[u] when given (as for c1_encode_modes_*), else the detector's or the
+ * fixed modes of opts.  x are the Float32 MDCT coefficients quantizationStage receives (encoder.js:365; the exact kernels',
+ * whatever the speculation mode).  BFU b has SPECS_PER_BFU[b] coefficients x_b[j] at BFU_START_LONG[b] + j, or at
+ * BFU_START_SHORT[b] + j when b's band is coded short; sfi[b] = findScaleFactor(x_b), the side record's value; W_b is 1 for a
+ * band coded long, 1/4 for the low or mid band coded short and 1/2 for the high band coded short (as for
+ * c1_encode_best_modes_*); bits(w) = WORD_LENGTH_BITS[w], w = 0 .. 15.
+ *   Error table, in binary64 with no fused operation:
+ *     e(b,w) = W_b * sum_j (x_b[j] - d_j)^2, j ascending,  d_j = Float32((q_j * SCALE_FACTORS[sfi[b]]) / range),
+ *     q_j from quantize at bits(w); d_j = 0 when w = 0 or sfi[b] = 0.
+ *   Greedy for an amount n of BFU_AMOUNTS = 20, 28, .., 52:  budget = 1696 - 40 - 10 n, all wl[b] = 0, used = 0.  A BFU b < n
+ *     is eligible when sfi[b] != 0, wl[b] < 15 and cost_b = (bits(wl[b] + 1) - bits(wl[b])) * size_b <= budget - used; its gain
+ *     is g_b = (e(b,wl[b]) - e(b,wl[b] + 1)) / cost_b.  Take the eligible b with the largest g_b > 0, the smallest b on a tie,
+ *     raise wl[b] by one level and add cost_b to used; stop when no eligible BFU has a positive gain (at most 52 * 15 steps,
+ *     whatever the data).  T(n) = sum_{b<n} e(b,wl[b]) + sum_{b>=n} e(b,0), summed in BFU order.  n* is the first amount with
+ *     the least T; a NaN never wins.
+ *   Fallback to the reference:  (n_R, wl_R) is the reference's record for u under opts (the allocation chain of
+ *     c1_encode_device, run once) and T_ref the same sum over it; if that record is allocateBits' own fallback (:132-139: every
+ *     scale-factor index written as 0) T_ref = sum_b e(b,0).  taken[u] = 1 if T(n*) < T_ref, else 0 (also when every T is NaN).
+ *     The unit is packed from the greedy record when taken, else from the reference's, untouched: T_final <= T_ref for every
+ *     unit by construction, and where taken[u] = 0 the bytes are exactly those of c1_encode_modes_* or c1_encode_device.
+ * Outputs: distortion[2u] = T_ref, distortion[2u + 1] = T(n*); energy[u] = sum_b W_b sum_j x_b[j]^2 (= sum_b e(b,0) in BFU
+ * order); with all-long modes it is c1_encode_best_bias_*'s E within rounding, under a constant byte c1_encode_best_modes_*'s.
+ * Each output may be NULL (units NULL: measure only, no packing runs and no record is replaced); all four NULL is C1_ERR_ARG.
+ * The same inputs give the same bits run after run.  The call always takes the exact analysis; no output depends on the
+ * speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP or the halo.  Mode bytes, limits on frames,
+ * alignment, chunking, asynchrony and the caller's-stream contract are those of c1_encode_best_bias_device.  No workspace on
+ * top of an encode call's.  c1_ctx_kernel_ms counts the new kernel under "measure".
+ * Not done: steps of several levels at once (on the CPU model another 0.3 dB at several times the steps), changing scale
+ * factors or block modes by this error, perceptual weights. */
+int c1_encode_measured_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                              const c1_encode_options *opts, const uint8_t *modes /* device, frames*channels, or NULL */,
+                              uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                              uint8_t *taken /* device, frames*channels, or NULL */,
+                              double *distortion /* device, frames*channels*2: T_ref, T(n*), or NULL */,
+                              double *energy /* device, frames*channels, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The options, the outputs and every mode byte are validated before the
+ * context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a device the
+ * call then returns C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per channel. */
+int c1_encode_measured_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                             const c1_encode_options *opts, const uint8_t *modes /* host, or NULL */,
+                             uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                             double *distortion /* host, or NULL */, double *energy /* host, or NULL */);
 
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
