@@ -96,6 +96,12 @@ SIGNATURES = {
                                             C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_encode_measured_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                            C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_measured_sf_device': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                               C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    'c1_encode_measured_sf_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
+                                              C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     'c1_encode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_int,
                                         C.POINTER(EncodeOptions), C.c_void_p]),
     'c1_decode_batch_multi': (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,

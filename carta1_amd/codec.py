@@ -301,7 +301,8 @@ class Context:
                                                           None if energy is None else energy.ctypes.data))
         return (units, choice, modes, dist, energy) if return_distortion else (units, choice, modes)
 
-    def encode_measured(self, channels, modes=None, options=None, halo_frames=0, return_distortion=False):
+    def encode_measured(self, channels, modes=None, options=None, halo_frames=0, return_distortion=False, scale_factor_offsets=None,
+                        return_shifts=False):
         """encode() with the word lengths of every sound unit allocated by the measured coding error instead of the reference's
         model of it (c1_encode_measured_batch; opt-in: the units are not the reference encoder's, but ordinary sound units with
         its block modes and scale factors that its decode() reads).  Per unit a greedy allocation over the W-weighted error of
@@ -309,7 +310,12 @@ class Context:
         error and was packed, 0 where the unit is byte for byte encode()'s / encode_modes()'s.  modes: None (detection or fixed
         modes as `options` say) or mode bytes as for encode_modes().  Returns (units, taken uint8 [units]), and with
         return_distortion (units, taken, distortion float64 [units, 2]: the reference record's error and the greedy one's,
-        energy float64 [units])."""
+        energy float64 [units]).
+        scale_factor_offsets (c1_encode_measured_sf_batch): 1 to 8 distinct offsets within -8..8, the first 0, e.g.
+        SCALE_FACTOR_OFFSETS.  Every BFU's scale-factor index is then chosen, per word length, among findScaleFactor's plus
+        each offset by the same error, and a taken unit carries the chosen indices.  None: the call above, untouched.
+        return_shifts (needs the offsets): shifts int8 [units, 52], the offset written per BFU and 0 where none was, follows
+        taken in the result."""
         opts = (options or EncoderOptions()).to_c()
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         n = len(chans[0])
@@ -317,11 +323,24 @@ class Context:
             raise ValueError('channels must have equal length, a multiple of 512')
         frames = max(n // 512 - halo_frames, 0)
         m = None if modes is None else check_block_modes(modes, frames, len(chans))
+        if return_shifts and scale_factor_offsets is None:
+            raise ValueError('return_shifts needs scale_factor_offsets')
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
         units = np.zeros((frames * len(chans), 212), dtype=np.uint8)
         taken = np.zeros(frames * len(chans), dtype=np.uint8)
         dist = np.zeros((frames * len(chans), 2), dtype=np.float64) if return_distortion else None
         energy = np.zeros(frames * len(chans), dtype=np.float64) if return_distortion else None
         ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        if offs is not None:
+            shifts = np.zeros((frames * len(chans), 52), dtype=np.int8) if return_shifts else None
+            capi.check(capi.load().c1_encode_measured_sf_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts),
+                                                               None if m is None else m.ctypes.data, offs.ctypes.data, len(offs),
+                                                               units.ctypes.data, taken.ctypes.data,
+                                                               None if shifts is None else shifts.ctypes.data,
+                                                               None if dist is None else dist.ctypes.data,
+                                                               None if energy is None else energy.ctypes.data))
+            out = (units, taken) + ((shifts,) if return_shifts else ())
+            return out + (dist, energy) if return_distortion else out
         capi.check(capi.load().c1_encode_measured_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts),
                                                         None if m is None else m.ctypes.data, units.ctypes.data, taken.ctypes.data,
                                                         None if dist is None else dist.ctypes.data,
@@ -390,12 +409,22 @@ class Context:
                                                            vp(modes_ptr), vp(distortion_ptr), vp(energy_ptr)))
 
     def encode_measured_device(self, pcm_ptrs, frames, units_ptr=None, taken_ptr=None, distortion_ptr=None, energy_ptr=None,
-                               modes_ptr=None, options=None, halo_frames=0):
+                               modes_ptr=None, options=None, halo_frames=0, scale_factor_offsets=None, shifts_ptr=None):
         """c1_encode_measured_device: outputs on the device, each may be None (units_ptr None: measure only), not all; taken is
         uint8 [units], distortion float64 [units, 2], energy float64 [units]; modes_ptr = mode bytes on the device as for
-        encode_modes_device, or None."""
+        encode_modes_device, or None.  scale_factor_offsets (host values, as for encode_measured): c1_encode_measured_sf_device,
+        and shifts_ptr = int8 [units, 52] on the device, or None."""
         opts = (options or EncoderOptions()).to_c()
         vp = lambda p: C.c_void_p(p) if p else None
+        if scale_factor_offsets is not None:
+            offs = check_scale_factor_offsets(scale_factor_offsets, check=False)   # the library's own check decides
+            capi.check(capi.load().c1_encode_measured_sf_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                                C.byref(opts), vp(modes_ptr), offs.ctypes.data if len(offs) else None,
+                                                                len(offs), vp(units_ptr), vp(taken_ptr), vp(shifts_ptr),
+                                                                vp(distortion_ptr), vp(energy_ptr)))
+            return
+        if shifts_ptr:
+            raise ValueError('shifts_ptr needs scale_factor_offsets')
         capi.check(capi.load().c1_encode_measured_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                          C.byref(opts), vp(modes_ptr), vp(units_ptr), vp(taken_ptr),
                                                          vp(distortion_ptr), vp(energy_ptr)))
@@ -1058,6 +1087,31 @@ def mode_candidates(candidates, check=True):
             if b in out[:i]:
                 raise ValueError('candidate %d: mode byte 0x%02x is given twice' % (i, b))
     return np.ascontiguousarray(out, dtype=np.uint8).reshape(-1)
+
+
+# ---- the scale-factor index of every BFU chosen among findScaleFactor + offset (c1_encode_measured_sf_*) ------------------
+MAX_SCALE_FACTOR_OFFSETS = 8
+SCALE_FACTOR_OFFSETS = (0, -1, 1, -2, -3)       # the suggested set: offsets below -3 add 0.03 dB at most
+
+
+def check_scale_factor_offsets(offsets, check=True):
+    """the offsets of Context.encode_measured(scale_factor_offsets=...) -> int8 array in the caller's order.  check: ValueError
+    for none, for more than MAX_SCALE_FACTOR_OFFSETS, for a value outside -8..8, for a value given twice and for a first value
+    other than 0; without it the library's own check decides."""
+    out = [int(v) for v in list(offsets)]
+    if any(not -128 <= v <= 127 for v in out):
+        raise ValueError('scale-factor offsets must be within -8..8')
+    if check:
+        if not 1 <= len(out) <= MAX_SCALE_FACTOR_OFFSETS:
+            raise ValueError('between 1 and %d scale-factor offsets per call, got %d' % (MAX_SCALE_FACTOR_OFFSETS, len(out)))
+        for i, v in enumerate(out):
+            if not -8 <= v <= 8:
+                raise ValueError('scale-factor offset %d is %d, outside -8..8' % (i, v))
+            if v in out[:i]:
+                raise ValueError('scale-factor offset %d: %d is given twice' % (i, v))
+        if out[0] != 0:
+            raise ValueError('the first scale-factor offset must be 0 (the reference\'s own index), got %d' % out[0])
+    return np.ascontiguousarray(out, dtype=np.int8).reshape(-1)
 
 
 # ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----

@@ -804,6 +804,10 @@ struct BestBiasCall {
 struct MeasuredCall {
   uint8_t *taken;
   double *distortion, *energy;
+  // c1_encode_measured_sf_device: the candidate offsets (host memory, validated; null for c1_encode_measured_device) and its output
+  const int8_t *sf_offsets = nullptr;
+  int n_offsets = 0;
+  int8_t *shifts = nullptr;
 };
 
 // the first index byte that is not below n: C1_ERR_ARG naming frame and channel (of two)
@@ -1151,9 +1155,18 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       // mc (c1_encode_measured_device): the allocation chain above left the reference's record of every unit; k_measured_alloc
       // builds the unit's error table, allocates greedily by it, and replaces the record where that codes with less error
       ScopedTiming t(ctx, K_MEASURE, sB);
-      c1k_launch_measured_alloc(L, all_long, L.units != nullptr, mc->taken ? mc->taken + f0 * channels : nullptr,
-                                mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
-                                mc->energy ? mc->energy + f0 * channels : nullptr, sB);
+      if (mc->sf_offsets) {
+        // c1_encode_measured_sf_device: the same over the least error of the candidate scale-factor indices; a taken unit's chosen
+        // indices replace the scale-factor bytes of its side record, where the packing kernels read them
+        c1k_launch_measured_sf(L, all_long, L.units != nullptr, mc->sf_offsets, mc->n_offsets, mc->taken ? mc->taken + f0 * channels : nullptr,
+                               mc->shifts ? mc->shifts + f0 * channels * 52 : nullptr,
+                               mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
+                               mc->energy ? mc->energy + f0 * channels : nullptr, sB);
+      } else {
+        c1k_launch_measured_alloc(L, all_long, L.units != nullptr, mc->taken ? mc->taken + f0 * channels : nullptr,
+                                  mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
+                                  mc->energy ? mc->energy + f0 * channels : nullptr, sB);
+      }
     }
     if (L.units && quantize32) {
       // The coefficients are the reference's, and still the quantization need not be done in binary64: the packing
@@ -2674,6 +2687,98 @@ int c1_encode_measured_batch(c1_ctx *ctx, const float *const *pcm, int channels,
                                       taken ? d_taken : nullptr, distortion ? d_dist : nullptr, energy ? d_energy : nullptr))) return rc;
   if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// host only: 1 to 8 distinct offsets within -8 .. 8, the first of them 0
+static int check_sf_offsets(const char *what, const int8_t *sf_offsets, int n) {
+  if (n < 1 || n > C1_MAX_SF_OFFSETS) return fail(C1_ERR_ARG, "%s: n_offsets = %d is outside 1..%d", what, n, C1_MAX_SF_OFFSETS);
+  if (!sf_offsets) return fail(C1_ERR_ARG, "%s: sf_offsets is NULL", what);
+  for (int k = 0; k < n; k++) {
+    if (sf_offsets[k] < -8 || sf_offsets[k] > 8) return fail(C1_ERR_ARG, "%s: sf_offsets[%d] = %d is outside -8..8", what, k, (int)sf_offsets[k]);
+    for (int j = 0; j < k; j++) if (sf_offsets[j] == sf_offsets[k]) return fail(C1_ERR_ARG, "%s: sf_offsets[%d] repeats sf_offsets[%d] = %d", what, k, j, (int)sf_offsets[k]);
+  }
+  if (sf_offsets[0] != 0) return fail(C1_ERR_ARG, "%s: sf_offsets[0] = %d, not 0 (the reference's own index comes first)", what, (int)sf_offsets[0]);
+  return C1_OK;
+}
+
+int c1_encode_measured_sf_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                 const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                                 uint8_t *units, uint8_t *taken, int8_t *shifts, double *distortion, double *energy) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_sf_device", opts, modes == nullptr))) return rc;
+  if ((rc = check_sf_offsets("c1_encode_measured_sf_device", sf_offsets, n_offsets))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_measured_sf_device: units, taken, shifts, distortion and energy are all NULL");
+  // with given modes neither threshold nor fixed modes are read
+  c1_encode_options base = *opts;
+  if (modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  MeasuredCall mc = {taken, distortion, energy};
+  mc.sf_offsets = sf_offsets;                                   // they travel to the kernel as an argument of every launch
+  mc.n_offsets = n_offsets;
+  mc.shifts = shifts;
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            frames > 0 ? modes : nullptr, nullptr, nullptr, nullptr, &mc);
+}
+
+int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                                uint8_t *units, uint8_t *taken, int8_t *shifts, double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_sf_batch", opts, modes == nullptr))) return rc;
+  if ((rc = check_sf_offsets("c1_encode_measured_sf_batch", sf_offsets, n_offsets))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy) return fail(C1_ERR_ARG, "c1_encode_measured_sf_batch: units, taken, shifts, distortion and energy are all NULL");
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if (modes && (rc = check_mode_bytes("c1_encode_measured_sf_batch", modes, frames, channels))) return rc;
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "c1_encode_measured_sf_batch: no HIP device available; this library has no CPU path"); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), mode_off = up256(unit_off + n_units * C1_UNIT_BYTES), taken_off = up256(mode_off + n_units),
+               shift_off = up256(taken_off + n_units), dist_off = up256(shift_off + n_units * 52),
+               energy_off = up256(dist_off + n_units * 2 * sizeof(double));
+  if ((rc = ensure_io(ctx, energy_off + n_units * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_modes = (uint8_t *)ctx->d_io + mode_off, *d_taken = (uint8_t *)ctx->d_io + taken_off;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>((char *)ctx->d_io + shift_off);
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off);
+  if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, n_units, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_measured_sf_device(ctx, dptr, channels, frames, halo_frames, opts, modes ? d_modes : nullptr, sf_offsets, n_offsets,
+                                         units ? d_units : nullptr, taken ? d_taken : nullptr, shifts ? d_shifts : nullptr,
+                                         distortion ? d_dist : nullptr, energy ? d_energy : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (shifts) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
   if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));

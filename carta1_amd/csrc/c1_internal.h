@@ -346,6 +346,13 @@ void c1k_launch_choose_modes(const C1EncodeLaunch &L, const float *coefs_short, 
 // every unit has modes [0,0,0] (the side records' mode byte is not read)
 void c1k_launch_measured_alloc(const C1EncodeLaunch &L, bool all_long, bool finalize, uint8_t *taken, double *distortion, double *energy,
                                hipStream_t stream);
+// the measured allocation with every BFU's scale-factor index chosen by the same error (c1_k_measured_sf.hip; the definition is
+// include/carta1_hip.h's): c1k_launch_measured_alloc over the table of least errors of the n_offsets candidate indices
+// findScaleFactor + sf_offsets[k] (host memory, sf_offsets[0] == 0, n_offsets 1 .. 8).  finalize: a taken unit's greedy record
+// replaces the one in L.alloc and its chosen indices the scale-factor bytes of L.side; otherwise both are left alone.  shifts
+// (units * 52: the offset written per BFU, 0 where none) may be null like the other outputs
+void c1k_launch_measured_sf(const C1EncodeLaunch &L, bool all_long, bool finalize, const int8_t *sf_offsets, int n_offsets, uint8_t *taken,
+                            int8_t *shifts, double *distortion, double *energy, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

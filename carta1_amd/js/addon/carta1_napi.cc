@@ -437,6 +437,56 @@ napi_value EncodeMeasured(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// encodeMeasuredSf(ctx, [Float32Array...], haloFrames, options, Uint8Array modes | null, Int8Array offsets)
+// -> encodeMeasured's object and shifts: Int8Array(frames*channels*52), the offset written per BFU: c1_encode_measured_sf_batch
+napi_value EncodeMeasuredSf(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_modes = 0, n_offsets = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *modes = nullptr, *offsets = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o)) return nullptr;
+  napi_valuetype mt;
+  NAPI_OK(napi_typeof(env, argv[4], &mt));
+  const bool have_modes = mt != napi_null && mt != napi_undefined;
+  if (have_modes && !get_typed(env, argv[4], napi_uint8_array, &modes, &n_modes)) return nullptr;
+  if (!get_typed(env, argv[5], napi_int8_array, &offsets, &n_offsets)) return nullptr;
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  if (have_modes && n_modes != n_units) { napi_throw_type_error(env, nullptr, "modes: one byte per frame and channel"); return nullptr; }
+  if (n_offsets > 64) n_offsets = 64;                           // the library's own check names the limit
+  uint8_t *units, *taken;
+  napi_value out_units = make_u8(env, n_units * C1_UNIT_BYTES, &units), out_taken = make_u8(env, n_units, &taken);
+  if (!out_units || !out_taken) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  napi_value ab_s, ab_d, ab_e, out_shifts, out_dist, out_energy;
+  void *shifts, *dist, *energy;
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52, &shifts, &ab_s));
+  NAPI_OK(napi_create_typedarray(env, napi_int8_array, n_units * 52, ab_s, 0, &out_shifts));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 2 * sizeof(double), &dist, &ab_d));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * 2, ab_d, 0, &out_dist));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * sizeof(double), &energy, &ab_e));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units, ab_e, 0, &out_energy));
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_measured_sf_batch(ctx, p, (int)ch.size(), frames, halo, &o, have_modes ? static_cast<const uint8_t *>(modes) : nullptr,
+                                             static_cast<const int8_t *>(offsets), (int)n_offsets, units, taken, static_cast<int8_t *>(shifts),
+                                             static_cast<double *>(dist), static_cast<double *>(energy));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_set_named_property(env, obj, "units", out_units));
+  NAPI_OK(napi_set_named_property(env, obj, "taken", out_taken));
+  NAPI_OK(napi_set_named_property(env, obj, "shifts", out_shifts));
+  NAPI_OK(napi_set_named_property(env, obj, "distortion", out_dist));
+  NAPI_OK(napi_set_named_property(env, obj, "energy", out_energy));
+  return obj;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1240,6 +1290,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeBestBias", nullptr, EncodeBestBias, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBestModes", nullptr, EncodeBestModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasured", nullptr, EncodeMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

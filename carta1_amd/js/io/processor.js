@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, checkScaleFactorOffsets } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -50,7 +50,10 @@ export async function encodeAeaPcm(channels, options = {}) {
   // error instead of the reference's model of it, and keeps the reference's allocation where that codes better
   // (c1_encode_measured_batch).  The units are not the reference encoder's, but decode() reads them.  Alone or with blockModes;
   // mutually exclusive with allocationBiases, allocationBiasCandidates and blockModeCandidates (TypeError); devices is not used
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, ...encoderValues } = options
+  // options.scaleFactorOffsets (with measuredAllocation: true only, else TypeError): 1 to 8 distinct integers within -8 .. 8, the
+  // first 0 (SCALE_FACTOR_OFFSETS is the suggested set).  The measured allocation then also chooses every BFU's scale-factor
+  // index among findScaleFactor's plus each offset by the same error (c1_encode_measured_sf_batch)
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, scaleFactorOffsets, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
@@ -82,6 +85,11 @@ export async function encodeAeaPcm(channels, options = {}) {
         throw new TypeError(`measuredAllocation and ${name} are mutually exclusive: the measured allocation replaces the search over the reference's options`)
       }
     }
+  }
+  const haveOffsets = scaleFactorOffsets !== undefined && scaleFactorOffsets !== null
+  if (haveOffsets) {
+    if (!measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
+    checkScaleFactorOffsets(scaleFactorOffsets)
   }
   let candidates = null
   if (haveCandidates) {
@@ -134,7 +142,7 @@ export async function encodeAeaPcm(channels, options = {}) {
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
   if (frames > 0 && measuredAllocation) {
-    image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null).units, AEA_HEADER_SIZE)
+    image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null, haveOffsets ? scaleFactorOffsets : null).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && haveModeCandidates) {
     image.set(encodeBestModes(padded, encoderOptions.toNative(), blockModeCandidates).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && candidates) {

@@ -96,6 +96,27 @@ export function encodeBestModes(channels, nativeOptions, candidates, haloFrames 
 // Uint8Array(frames * channels), 1 where the greedy allocation coded with less error than the reference's record and was packed,
 // 0 where the unit is byte for byte the plain encode's, distortion: Float64Array(frames * channels * 2), per unit the reference
 // record's weighted error and the greedy allocation's, energy: Float64Array(frames * channels) }.
-export function encodeMeasured(channels, nativeOptions, modes = null, haloFrames = 0, ctx = context()) {
-  return native().encodeMeasured(ctx, channels, haloFrames, nativeOptions, modes)
+// scaleFactorOffsets (c1_encode_measured_sf_batch): null, or 1 .. 8 distinct integers within -8 .. 8, the first 0, e.g.
+// SCALE_FACTOR_OFFSETS.  Every BFU's scale-factor index is then chosen, per word length, among findScaleFactor's plus each
+// offset by the same error; a taken unit carries the chosen indices, and the result gains shifts: Int8Array(frames * channels *
+// 52), the offset written per BFU and 0 where none was.  A list that breaks these rules is a TypeError naming the option.
+// (A number in the place of scaleFactorOffsets is taken as haloFrames, as the function's earlier form had it.)
+export const SCALE_FACTOR_OFFSETS = Object.freeze([0, -1, 1, -2, -3])
+
+export function checkScaleFactorOffsets(scaleFactorOffsets) {
+  const list = scaleFactorOffsets !== null && typeof scaleFactorOffsets === 'object' && typeof scaleFactorOffsets.length === 'number' ? Array.from(scaleFactorOffsets) : null
+  if (!list) throw new TypeError('scaleFactorOffsets must be an array of integers')
+  if (list.length < 1 || list.length > 8) throw new TypeError(`scaleFactorOffsets must hold 1 to 8 offsets, got ${list.length}`)
+  list.forEach((v, k) => {
+    if (!Number.isInteger(v) || v < -8 || v > 8) throw new TypeError(`scaleFactorOffsets[${k}] = ${v} is not an integer within -8..8`)
+    if (list.indexOf(v) !== k) throw new TypeError(`scaleFactorOffsets[${k}] = ${v} is given twice`)
+  })
+  if (list[0] !== 0) throw new TypeError(`scaleFactorOffsets[0] must be 0, the reference's own index, got ${list[0]}`)
+  return Int8Array.from(list)
+}
+
+export function encodeMeasured(channels, nativeOptions, modes = null, scaleFactorOffsets = null, haloFrames = 0, ctx = context()) {
+  if (typeof scaleFactorOffsets === 'number') return encodeMeasured(channels, nativeOptions, modes, null, scaleFactorOffsets, haloFrames || context())
+  if (scaleFactorOffsets === null || scaleFactorOffsets === undefined) return native().encodeMeasured(ctx, channels, haloFrames, nativeOptions, modes)
+  return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }

@@ -405,6 +405,50 @@ int c1_encode_measured_batch(c1_ctx *ctx, const float *const *pcm, int channels,
                              uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
                              double *distortion /* host, or NULL */, double *energy /* host, or NULL */);
 
+/* ---- the measured allocation with every BFU's scale-factor index chosen by the same error ------------------------------------
+ * c1_encode_measured_* keeps every BFU at findScaleFactor's index, the smallest table entry not below the BFU's peak.  quantize
+ * clamps to +-range (quantization.js:49-53), so an index a few steps lower clips the few peaks and gives every other coefficient
+ * a finer grid; at the short word lengths where most BFUs end up that codes with less error.  This call lets the error decide.
+ * OPT-IN like its sibling; the units are ordinary sound units (decode() reads any index 1 .. 63).  Notation as above.
+ *   Candidates.  sf_offsets (HOST memory in both calls) holds n_offsets values, 1 <= n_offsets <= C1_MAX_SF_OFFSETS, distinct,
+ *     each in -8 .. 8, sf_offsets[0] == 0; otherwise C1_ERR_ARG with the outputs untouched.  For BFU b with s0 =
+ *     findScaleFactor(x_b) != 0 candidate k is valid when 1 <= s0 + sf_offsets[k] <= 63.  A BFU with s0 = 0 codes nothing.
+ *   Error table.  e_k(b,w) is e(b,w) above with sfi = s0 + sf_offsets[k] in both quantize and the dequantizer (binary64, no
+ *     fused operation, j ascending).  e(b,w) = min over the valid k of e_k(b,w); pick(b,w) is the first k, in the order given,
+ *     that attains it (a later candidate wins only when its error is strictly smaller).  e(b,0) is unchanged.
+ *   Greedy allocation: gains, greedy, totals, the first amount of least T and the NaN rule are those above, over this table.
+ *   Fallback.  T_ref is the one above: the sum of e_0 (offset 0, the reference's own indices) over the reference's record.
+ *     taken[u] = T(n*) < T_ref; a unit not taken is byte for byte the plain encode's.  No second greedy over the offset-0 table
+ *     is run, so T(n*) may now and then exceed c1_encode_measured_*'s (3 of 648 units of the test material).
+ *   Packed record of a taken unit.  nBfu and the word lengths are the greedy's; the scale-factor index written for b < nBfu is
+ *     s0 + sf_offsets[pick(b, wl[b])] where wl[b] > 0, else s0; the mantissas are quantize at that index and word length.
+ * Outputs: shifts[52 u + b] = the offset written for b < nBfu with wl[b] > 0 in a taken unit, 0 everywhere else (also in a
+ * measure-only call, where it is what a packing call would write); distortion[2u] = T_ref, distortion[2u + 1] = T(n*); units,
+ * taken and energy as above.  Each may be NULL; all five NULL is C1_ERR_ARG.  With units NULL no record of the context is touched.
+ * Everything else -- modes, limits, chunking, asynchrony, invariance under the speculation mode, the run length,
+ * C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP and the halo, repeatability, "measure" in c1_ctx_kernel_ms, no workspace on top of an
+ * encode call's -- is c1_encode_measured_*'s.  With sf_offsets = {0} every output is bit for bit c1_encode_measured_*'s and
+ * shifts is all zero.  The suggested set is {0, -1, 1, -2, -3}: 1.7 to 2.4 dB less error energy than c1_encode_measured_* on
+ * the test material; offsets below -3 add 0.03 dB at most. */
+#define C1_MAX_SF_OFFSETS 8
+int c1_encode_measured_sf_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                 const c1_encode_options *opts, const uint8_t *modes /* device, frames*channels, or NULL */,
+                                 const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
+                                 uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                                 uint8_t *taken /* device, frames*channels, or NULL */,
+                                 int8_t *shifts /* device, frames*channels*52, or NULL */,
+                                 double *distortion /* device, frames*channels*2: T_ref, T(n*), or NULL */,
+                                 double *energy /* device, frames*channels, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The options, the offsets, the outputs and every mode byte are validated
+ * before the context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a
+ * device the call then returns C1_ERR_NO_DEVICE.  frames 0 .. 2^22 per channel. */
+int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                const c1_encode_options *opts, const uint8_t *modes /* host, or NULL */,
+                                const int8_t *sf_offsets /* host, n_offsets values */, int n_offsets,
+                                uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                double *energy /* host, or NULL */);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
