@@ -302,7 +302,7 @@ class Context:
         return (units, choice, modes, dist, energy) if return_distortion else (units, choice, modes)
 
     def encode_measured(self, channels, modes=None, options=None, halo_frames=0, return_distortion=False, scale_factor_offsets=None,
-                        return_shifts=False):
+                        return_shifts=False, masking=None, return_weights=False):
         """encode() with the word lengths of every sound unit allocated by the measured coding error instead of the reference's
         model of it (c1_encode_measured_batch; opt-in: the units are not the reference encoder's, but ordinary sound units with
         its block modes and scale factors that its decode() reads).  Per unit a greedy allocation over the W-weighted error of
@@ -315,7 +315,12 @@ class Context:
         SCALE_FACTOR_OFFSETS.  Every BFU's scale-factor index is then chosen, per word length, among findScaleFactor's plus
         each offset by the same error, and a taken unit carries the chosen indices.  None: the call above, untouched.
         return_shifts (needs the offsets): shifts int8 [units, 52], the offset written per BFU and 0 where none was, follows
-        taken in the result."""
+        taken in the result.
+        masking (c1_encode_measured_masked_batch): True for the packaged tables (MASKING_DEFAULT) or a (floor [52], spread
+        [52, 52] or None) pair, see check_masking.  Every BFU's error is then divided by a masking threshold computed per unit
+        from the unit's own spectrum and these tables; distortion and energy are the weighted ones.  Without offsets the
+        offsets are (0,).  None: the calls above, untouched.  return_weights (needs masking): weights float64 [units, 52], the
+        reciprocal threshold of every BFU, ends the result."""
         opts = (options or EncoderOptions()).to_c()
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         n = len(chans[0])
@@ -325,12 +330,30 @@ class Context:
         m = None if modes is None else check_block_modes(modes, frames, len(chans))
         if return_shifts and scale_factor_offsets is None:
             raise ValueError('return_shifts needs scale_factor_offsets')
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
+        if return_shifts and mask is not None and scale_factor_offsets is None:
+            raise ValueError('return_shifts needs scale_factor_offsets')
         offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
+        if mask is not None and offs is None:
+            offs = check_scale_factor_offsets((0,))
         units = np.zeros((frames * len(chans), 212), dtype=np.uint8)
         taken = np.zeros(frames * len(chans), dtype=np.uint8)
         dist = np.zeros((frames * len(chans), 2), dtype=np.float64) if return_distortion else None
         energy = np.zeros(frames * len(chans), dtype=np.float64) if return_distortion else None
         ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        if mask is not None:
+            shifts = np.zeros((frames * len(chans), 52), dtype=np.int8) if return_shifts else None
+            weights = np.zeros((frames * len(chans), 52), dtype=np.float64) if return_weights else None
+            capi.check(capi.load().c1_encode_measured_masked_batch(
+                self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts), None if m is None else m.ctypes.data,
+                offs.ctypes.data, len(offs), mask[0].ctypes.data, None if mask[1] is None else mask[1].ctypes.data, units.ctypes.data,
+                taken.ctypes.data, None if shifts is None else shifts.ctypes.data, None if dist is None else dist.ctypes.data,
+                None if energy is None else energy.ctypes.data, None if weights is None else weights.ctypes.data))
+            out = (units, taken) + ((shifts,) if return_shifts else ())
+            out = out + (dist, energy) if return_distortion else out
+            return out + (weights,) if return_weights else out
         if offs is not None:
             shifts = np.zeros((frames * len(chans), 52), dtype=np.int8) if return_shifts else None
             capi.check(capi.load().c1_encode_measured_sf_batch(self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts),
@@ -409,13 +432,26 @@ class Context:
                                                            vp(modes_ptr), vp(distortion_ptr), vp(energy_ptr)))
 
     def encode_measured_device(self, pcm_ptrs, frames, units_ptr=None, taken_ptr=None, distortion_ptr=None, energy_ptr=None,
-                               modes_ptr=None, options=None, halo_frames=0, scale_factor_offsets=None, shifts_ptr=None):
+                               modes_ptr=None, options=None, halo_frames=0, scale_factor_offsets=None, shifts_ptr=None, masking=None,
+                               weights_ptr=None):
         """c1_encode_measured_device: outputs on the device, each may be None (units_ptr None: measure only), not all; taken is
         uint8 [units], distortion float64 [units, 2], energy float64 [units]; modes_ptr = mode bytes on the device as for
         encode_modes_device, or None.  scale_factor_offsets (host values, as for encode_measured): c1_encode_measured_sf_device,
-        and shifts_ptr = int8 [units, 52] on the device, or None."""
+        and shifts_ptr = int8 [units, 52] on the device, or None.  masking (host values, as for encode_measured):
+        c1_encode_measured_masked_device, offsets (0,) when none are given, and weights_ptr = float64 [units, 52] on the device, or
+        None."""
         opts = (options or EncoderOptions()).to_c()
         vp = lambda p: C.c_void_p(p) if p else None
+        if masking is not None:
+            mask = check_masking(masking, check=False)                             # the library's own check decides
+            offs = check_scale_factor_offsets((0,) if scale_factor_offsets is None else scale_factor_offsets, check=False)
+            capi.check(capi.load().c1_encode_measured_masked_device(
+                self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, C.byref(opts), vp(modes_ptr),
+                offs.ctypes.data if len(offs) else None, len(offs), mask[0].ctypes.data, None if mask[1] is None else mask[1].ctypes.data,
+                vp(units_ptr), vp(taken_ptr), vp(shifts_ptr), vp(distortion_ptr), vp(energy_ptr), vp(weights_ptr)))
+            return
+        if weights_ptr:
+            raise ValueError('weights_ptr needs masking')
         if scale_factor_offsets is not None:
             offs = check_scale_factor_offsets(scale_factor_offsets, check=False)   # the library's own check decides
             capi.check(capi.load().c1_encode_measured_sf_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
@@ -1112,6 +1148,57 @@ def check_scale_factor_offsets(offsets, check=True):
         if out[0] != 0:
             raise ValueError('the first scale-factor offset must be 0 (the reference\'s own index), got %d' % out[0])
     return np.ascontiguousarray(out, dtype=np.int8).reshape(-1)
+
+
+# ---- every BFU's error weighted by a masking threshold (c1_encode_measured_masked_*) ---------------------------------------
+_MASKING = None
+
+
+def _packaged_masking():
+    """carta1_amd/masking_default.json (tools/make_masking_tables.py): (floor float64 [52], spread float64 [52, 52]), read-only"""
+    global _MASKING
+    if _MASKING is None:
+        import json
+        import os
+        raw = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'masking_default.json')))
+        val = lambda h: struct.unpack('>d', bytes.fromhex(h))[0]
+        floor = np.array([val(h) for h in raw['floor_f64']], dtype=np.float64)
+        spread = np.array([[val(h) for h in row] for row in raw['spread_f64']], dtype=np.float64)
+        floor.setflags(write=False)
+        spread.setflags(write=False)
+        _MASKING = (floor, spread)
+    return _MASKING
+
+
+MASKING_DEFAULT = _packaged_masking()             # Schroeder spreading on the Bark scale, Terhardt's threshold in quiet (DESIGN.md 6k)
+
+
+def check_masking(masking, check=True):
+    """the masking of Context.encode_measured(masking=...) -> (floor float64 [52], spread float64 [52, 52] or None), contiguous.
+    masking: True (the packaged tables) or a (floor, spread or None) pair.  check: ValueError naming the table and the index for a
+    floor that is not finite and within [1e-60, 1e60] or a spread entry that is not finite and within [0, 1e60]; without it
+    the library's own check decides."""
+    if masking is True:
+        masking = _packaged_masking()
+    if masking is False or masking is None or len(masking) != 2:
+        raise ValueError('masking must be True or a (floor, spread) pair')
+    floor = np.ascontiguousarray(masking[0], dtype=np.float64).reshape(-1)
+    spread = None if masking[1] is None else np.ascontiguousarray(masking[1], dtype=np.float64)
+    if floor.size != 52:
+        raise ValueError('masking: the floor must hold 52 values, got %d' % floor.size)
+    if spread is not None:
+        if spread.size != 52 * 52:
+            raise ValueError('masking: the spread must hold 52 x 52 values, got %d' % spread.size)
+        spread = spread.reshape(52, 52)
+    if check:
+        bad = np.flatnonzero(~((floor >= 1e-60) & (floor <= 1e60)))
+        if bad.size:
+            raise ValueError('masking: mask_floor[%d] = %r is outside [1e-60, 1e60]' % (bad[0], float(floor[bad[0]])))
+        if spread is not None:
+            bad = np.flatnonzero(~((spread.reshape(-1) >= 0.0) & (spread.reshape(-1) <= 1e60)))
+            if bad.size:
+                raise ValueError('masking: mask_spread[%d] = %r is outside [0, 1e60]' % (bad[0], float(spread.reshape(-1)[bad[0]])))
+    return floor, spread
 
 
 # ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----

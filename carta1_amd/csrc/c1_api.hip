@@ -456,6 +456,10 @@ struct c1_ctx {
   // allocation bias per unit (c1_encode_biases_device): the palette's tables in device form, the tables uploaded last, and the
   // unit lists of one chunk ([0, 8) counts, then one list per entry); all allocated on first use
   C1DevEncOpts *d_palette = nullptr;
+  // the masking tables of c1_encode_measured_masked_device, uploaded by every such call: floor[52], then the spreading matrix
+  // transposed; a page-locked staging copy and the event of the last upload from it.  Allocated on first use
+  double *d_mask = nullptr, *h_mask = nullptr;
+  hipEvent_t ev_mask = nullptr;
   double pal_tables[C1_MAX_BIAS_PALETTE][64];
   int pal_n = 0;
   uint32_t *d_pal_lists = nullptr;
@@ -808,6 +812,10 @@ struct MeasuredCall {
   const int8_t *sf_offsets = nullptr;
   int n_offsets = 0;
   int8_t *shifts = nullptr;
+  // c1_encode_measured_masked_device: the uploaded tables (c1_ctx::d_mask; null for the calls above) and its output
+  const double *mask = nullptr;
+  bool has_spread = false;
+  double *weights = nullptr;
 };
 
 // the first index byte that is not below n: C1_ERR_ARG naming frame and channel (of two)
@@ -1155,7 +1163,14 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       // mc (c1_encode_measured_device): the allocation chain above left the reference's record of every unit; k_measured_alloc
       // builds the unit's error table, allocates greedily by it, and replaces the record where that codes with less error
       ScopedTiming t(ctx, K_MEASURE, sB);
-      if (mc->sf_offsets) {
+      if (mc->mask) {
+        // c1_encode_measured_masked_device: the same again over e' = P_b * e, P_b from the unit's own level-0 errors and the tables
+        c1k_launch_measured_masked(L, all_long, L.units != nullptr, mc->sf_offsets, mc->n_offsets, mc->mask, mc->has_spread,
+                                   mc->taken ? mc->taken + f0 * channels : nullptr, mc->shifts ? mc->shifts + f0 * channels * 52 : nullptr,
+                                   mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
+                                   mc->energy ? mc->energy + f0 * channels : nullptr,
+                                   mc->weights ? mc->weights + f0 * channels * 52 : nullptr, sB);
+      } else if (mc->sf_offsets) {
         // c1_encode_measured_sf_device: the same over the least error of the candidate scale-factor indices; a taken unit's chosen
         // indices replace the scale-factor bytes of its side record, where the packing kernels read them
         c1k_launch_measured_sf(L, all_long, L.units != nullptr, mc->sf_offsets, mc->n_offsets, mc->taken ? mc->taken + f0 * channels : nullptr,
@@ -1414,6 +1429,9 @@ int c1_ctx_destroy(c1_ctx *ctx) {
   if (ctx->d_tables) hipFree(ctx->d_tables);
   if (ctx->d_opts) hipFree(ctx->d_opts);
   if (ctx->d_palette) hipFree(ctx->d_palette);
+  if (ctx->d_mask) hipFree(ctx->d_mask);
+  if (ctx->h_mask) hipHostFree(ctx->h_mask);
+  if (ctx->ev_mask) hipEventDestroy(ctx->ev_mask);
   if (ctx->d_spec_totals) hipFree(ctx->d_spec_totals);
   (void)hipDeviceSynchronize();
   free_workspace(ctx);
@@ -2781,6 +2799,131 @@ int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channe
   if (shifts) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
   if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// host only: every floor finite and within [1e-60, 1e60], every spread entry finite and within [0, 1e60]
+static int check_masking(const char *what, const double *mask_floor, const double *mask_spread) {
+  if (!mask_floor) return fail(C1_ERR_ARG, "%s: mask_floor is NULL", what);
+  for (int b = 0; b < 52; b++)
+    if (!(mask_floor[b] >= 1e-60 && mask_floor[b] <= 1e60)) return fail(C1_ERR_ARG, "%s: mask_floor[%d] = %g is outside [1e-60, 1e60]", what, b, mask_floor[b]);
+  for (int i = 0; mask_spread && i < 52 * 52; i++)
+    if (!(mask_spread[i] >= 0.0 && mask_spread[i] <= 1e60)) return fail(C1_ERR_ARG, "%s: mask_spread[%d] = %g (masker %d onto BFU %d) is outside [0, 1e60]", what, i, mask_spread[i], i % 52, i / 52);
+  return C1_OK;
+}
+
+constexpr size_t kMaskDoubles = 52 + 52 * 52;                  // 22 048 bytes
+
+// the tables of one call into c1_ctx::d_mask, ordered on the context's stream like the call's kernels: behind the kernels of every
+// earlier call, in front of this one's.  The staging copy is rewritten only once the upload before has left it
+static int upload_masking(c1_ctx *ctx, const double *mask_floor, const double *mask_spread) {
+  if (!ctx->d_mask) {
+    HIP_TRY(hipMalloc(&ctx->d_mask, kMaskDoubles * sizeof(double)));
+    HIP_TRY(hipHostMalloc((void **)&ctx->h_mask, kMaskDoubles * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_mask, hipEventDisableTiming));
+  } else {
+    HIP_TRY(hipEventSynchronize(ctx->ev_mask));
+  }
+  for (int b = 0; b < 52; b++) ctx->h_mask[b] = mask_floor[b];
+  for (int b = 0; b < 52; b++)
+    for (int c = 0; c < 52; c++) ctx->h_mask[52 + 52 * c + b] = mask_spread ? mask_spread[52 * b + c] : 0.0;
+  HIP_TRY(hipMemcpyAsync(ctx->d_mask, ctx->h_mask, kMaskDoubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev_mask, ctx->stream));
+  return C1_OK;
+}
+
+int c1_encode_measured_masked_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                     const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                                     const double *mask_floor, const double *mask_spread, uint8_t *units, uint8_t *taken,
+                                     int8_t *shifts, double *distortion, double *energy, double *weights) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_masked_device", opts, modes == nullptr))) return rc;
+  if ((rc = check_sf_offsets("c1_encode_measured_masked_device", sf_offsets, n_offsets))) return rc;
+  if ((rc = check_masking("c1_encode_measured_masked_device", mask_floor, mask_spread))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy && !weights) return fail(C1_ERR_ARG, "c1_encode_measured_masked_device: units, taken, shifts, distortion, energy and weights are all NULL");
+  // with given modes neither threshold nor fixed modes are read
+  c1_encode_options base = *opts;
+  if (modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  if (frames > 0) {
+    // the tail of an earlier speculative encode may still run beside the context's stream: it reads none of this
+    if ((rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+  }
+  MeasuredCall mc = {taken, distortion, energy};
+  mc.sf_offsets = sf_offsets;
+  mc.n_offsets = n_offsets;
+  mc.shifts = shifts;
+  mc.mask = ctx->d_mask;
+  mc.has_spread = mask_spread != nullptr;
+  mc.weights = weights;
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            frames > 0 ? modes : nullptr, nullptr, nullptr, nullptr, frames > 0 ? &mc : nullptr);
+}
+
+int c1_encode_measured_masked_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                    const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                                    const double *mask_floor, const double *mask_spread, uint8_t *units, uint8_t *taken,
+                                    int8_t *shifts, double *distortion, double *energy, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_encode_measured_masked_batch";
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts(what, opts, modes == nullptr))) return rc;
+  if ((rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if ((rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy && !weights) return fail(C1_ERR_ARG, "%s: units, taken, shifts, distortion, energy and weights are all NULL", what);
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if (modes && (rc = check_mode_bytes(what, modes, frames, channels))) return rc;
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), mode_off = up256(unit_off + n_units * C1_UNIT_BYTES), taken_off = up256(mode_off + n_units),
+               shift_off = up256(taken_off + n_units), dist_off = up256(shift_off + n_units * 52),
+               energy_off = up256(dist_off + n_units * 2 * sizeof(double)), weight_off = up256(energy_off + n_units * sizeof(double));
+  if ((rc = ensure_io(ctx, weight_off + n_units * 52 * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_modes = (uint8_t *)ctx->d_io + mode_off, *d_taken = (uint8_t *)ctx->d_io + taken_off;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>((char *)ctx->d_io + shift_off);
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off),
+         *d_weights = reinterpret_cast<double *>((char *)ctx->d_io + weight_off);
+  if (modes) HIP_TRY(hipMemcpyAsync(d_modes, modes, n_units, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_encode_measured_masked_device(ctx, dptr, channels, frames, halo_frames, opts, modes ? d_modes : nullptr, sf_offsets, n_offsets,
+                                             mask_floor, mask_spread, units ? d_units : nullptr, taken ? d_taken : nullptr,
+                                             shifts ? d_shifts : nullptr, distortion ? d_dist : nullptr, energy ? d_energy : nullptr,
+                                             weights ? d_weights : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (shifts) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, d_weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }

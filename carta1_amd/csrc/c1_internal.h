@@ -353,6 +353,13 @@ void c1k_launch_measured_alloc(const C1EncodeLaunch &L, bool all_long, bool fina
 // (units * 52: the offset written per BFU, 0 where none) may be null like the other outputs
 void c1k_launch_measured_sf(const C1EncodeLaunch &L, bool all_long, bool finalize, const int8_t *sf_offsets, int n_offsets, uint8_t *taken,
                             int8_t *shifts, double *distortion, double *energy, hipStream_t stream);
+// c1k_launch_measured_sf with every BFU's error divided by a masking threshold (c1_k_measured_masked.hip; the definition is
+// include/carta1_hip.h's).  mask: 52 + 52 * 52 doubles on the device, floor[b] at [b] and spread[b][c] at [52 + 52 * c + b] (the
+// matrix transposed); has_spread false: M_b = +0.0 and the matrix is not read.  weights (units * 52: P_b) may be null like the
+// other outputs
+void c1k_launch_measured_masked(const C1EncodeLaunch &L, bool all_long, bool finalize, const int8_t *sf_offsets, int n_offsets,
+                                const double *mask, bool has_spread, uint8_t *taken, int8_t *shifts, double *distortion, double *energy,
+                                double *weights, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -487,6 +487,66 @@ napi_value EncodeMeasuredSf(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// encodeMeasuredMasked(ctx, [Float32Array...], haloFrames, options, Uint8Array modes | null, Int8Array offsets, Float64Array floor,
+// Float64Array spread | null) -> encodeMeasuredSf's object and weights: Float64Array(frames*channels*52), the reciprocal masking
+// threshold of every BFU: c1_encode_measured_masked_batch
+napi_value EncodeMeasuredMasked(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_modes = 0, n_offsets = 0, n_floor = 0, n_spread = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *modes = nullptr, *offsets = nullptr, *floor = nullptr, *spread = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o)) return nullptr;
+  napi_valuetype mt, st;
+  NAPI_OK(napi_typeof(env, argv[4], &mt));
+  NAPI_OK(napi_typeof(env, argv[7], &st));
+  const bool have_modes = mt != napi_null && mt != napi_undefined, have_spread = st != napi_null && st != napi_undefined;
+  if (have_modes && !get_typed(env, argv[4], napi_uint8_array, &modes, &n_modes)) return nullptr;
+  if (!get_typed(env, argv[5], napi_int8_array, &offsets, &n_offsets)) return nullptr;
+  if (!get_typed(env, argv[6], napi_float64_array, &floor, &n_floor)) return nullptr;
+  if (have_spread && !get_typed(env, argv[7], napi_float64_array, &spread, &n_spread)) return nullptr;
+  if (n_floor != 52 || (have_spread && n_spread != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  if (have_modes && n_modes != n_units) { napi_throw_type_error(env, nullptr, "modes: one byte per frame and channel"); return nullptr; }
+  if (n_offsets > 64) n_offsets = 64;                           // the library's own check names the limit
+  uint8_t *units, *taken;
+  napi_value out_units = make_u8(env, n_units * C1_UNIT_BYTES, &units), out_taken = make_u8(env, n_units, &taken);
+  if (!out_units || !out_taken) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  napi_value ab_s, ab_d, ab_e, ab_w, out_shifts, out_dist, out_energy, out_weights;
+  void *shifts, *dist, *energy, *weights;
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52, &shifts, &ab_s));
+  NAPI_OK(napi_create_typedarray(env, napi_int8_array, n_units * 52, ab_s, 0, &out_shifts));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 2 * sizeof(double), &dist, &ab_d));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * 2, ab_d, 0, &out_dist));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * sizeof(double), &energy, &ab_e));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units, ab_e, 0, &out_energy));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52 * sizeof(double), &weights, &ab_w));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * 52, ab_w, 0, &out_weights));
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_measured_masked_batch(ctx, p, (int)ch.size(), frames, halo, &o, have_modes ? static_cast<const uint8_t *>(modes) : nullptr,
+                                                 static_cast<const int8_t *>(offsets), (int)n_offsets, static_cast<const double *>(floor),
+                                                 have_spread ? static_cast<const double *>(spread) : nullptr, units, taken,
+                                                 static_cast<int8_t *>(shifts), static_cast<double *>(dist), static_cast<double *>(energy),
+                                                 static_cast<double *>(weights));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_set_named_property(env, obj, "units", out_units));
+  NAPI_OK(napi_set_named_property(env, obj, "taken", out_taken));
+  NAPI_OK(napi_set_named_property(env, obj, "shifts", out_shifts));
+  NAPI_OK(napi_set_named_property(env, obj, "distortion", out_dist));
+  NAPI_OK(napi_set_named_property(env, obj, "energy", out_energy));
+  NAPI_OK(napi_set_named_property(env, obj, "weights", out_weights));
+  return obj;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1291,6 +1351,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeBestModes", nullptr, EncodeBestModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasured", nullptr, EncodeMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, checkScaleFactorOffsets } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -53,7 +53,10 @@ export async function encodeAeaPcm(channels, options = {}) {
   // options.scaleFactorOffsets (with measuredAllocation: true only, else TypeError): 1 to 8 distinct integers within -8 .. 8, the
   // first 0 (SCALE_FACTOR_OFFSETS is the suggested set).  The measured allocation then also chooses every BFU's scale-factor
   // index among findScaleFactor's plus each offset by the same error (c1_encode_measured_sf_batch)
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, scaleFactorOffsets, ...encoderValues } = options
+  // options.masking (with measuredAllocation: true only, else TypeError): true (the packaged tables, MASKING_DEFAULT) or { floor,
+  // spread } as for encodeMeasured.  The measured allocation then minimises every BFU's error divided by a masking threshold
+  // computed from the unit's own spectrum and these tables (c1_encode_measured_masked_batch)
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, scaleFactorOffsets, masking, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
@@ -90,6 +93,11 @@ export async function encodeAeaPcm(channels, options = {}) {
   if (haveOffsets) {
     if (!measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
     checkScaleFactorOffsets(scaleFactorOffsets)
+  }
+  const haveMasking = masking !== undefined && masking !== null && masking !== false
+  if (haveMasking) {
+    if (!measuredAllocation) throw new TypeError('masking needs measuredAllocation: true; no other path weighs its errors')
+    checkMasking(masking)
   }
   let candidates = null
   if (haveCandidates) {
@@ -142,7 +150,7 @@ export async function encodeAeaPcm(channels, options = {}) {
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
   if (frames > 0 && measuredAllocation) {
-    image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null, haveOffsets ? scaleFactorOffsets : null).units, AEA_HEADER_SIZE)
+    image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null, haveOffsets ? scaleFactorOffsets : null, haveMasking ? masking : null).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && haveModeCandidates) {
     image.set(encodeBestModes(padded, encoderOptions.toNative(), blockModeCandidates).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && candidates) {

@@ -1,6 +1,7 @@
 // Loads the N-API addon (addon/carta1_napi.node -> lib/libcarta1_hip.so) and owns the default device
 // context.  There is no JavaScript fallback for the hot path: if the addon or a HIP device is missing,
 // the first call throws the library's error.
+import fs from 'fs'
 import { createRequire } from 'module'
 import { buildNativeTables } from './core/constants.js'
 
@@ -115,8 +116,54 @@ export function checkScaleFactorOffsets(scaleFactorOffsets) {
   return Int8Array.from(list)
 }
 
-export function encodeMeasured(channels, nativeOptions, modes = null, scaleFactorOffsets = null, haloFrames = 0, ctx = context()) {
-  if (typeof scaleFactorOffsets === 'number') return encodeMeasured(channels, nativeOptions, modes, null, scaleFactorOffsets, haloFrames || context())
+// masking (c1_encode_measured_masked_batch): null, true (MASKING_DEFAULT, the packaged tables of carta1_amd/masking_default.json,
+// which both hosts read so that they feed identical bits) or { floor, spread }: floor 52 finite numbers within [1e-60, 1e60],
+// spread null or 52 * 52 finite numbers within [0, 1e60], row-major (or 52 rows of 52), spread[52 b + c] = masker c onto maskee b.
+// Every BFU's error is then divided by a masking threshold computed per unit from the unit's own spectrum and these tables;
+// distortion and energy are the weighted ones, and the result gains weights: Float64Array(frames * channels * 52), the reciprocal
+// threshold of every BFU.  Without offsets the offsets are [0].  Tables that break the rules are a TypeError naming the option.
+// (A number in the place of masking is taken as haloFrames, as the function's earlier form had it.)
+let maskingDefault = null
+function packagedMasking() {
+  if (!maskingDefault) {
+    const raw = JSON.parse(fs.readFileSync(new URL('../masking_default.json', import.meta.url), 'utf8'))
+    const value = (h) => new DataView(Uint8Array.from(h.match(/../g), (x) => parseInt(x, 16)).buffer).getFloat64(0, false)
+    maskingDefault = Object.freeze({ floor: Float64Array.from(raw.floor_f64, value), spread: Float64Array.from(raw.spread_f64.flat(), value) })
+  }
+  return maskingDefault
+}
+export const MASKING_DEFAULT = Object.freeze({
+  get floor() { return packagedMasking().floor },
+  get spread() { return packagedMasking().spread },
+})
+
+export function checkMasking(masking) {
+  if (masking === true) return packagedMasking()
+  if (masking === null || typeof masking !== 'object' || masking.floor === undefined) throw new TypeError('masking must be true or { floor, spread }')
+  const numbers = (x) => (x !== null && typeof x === 'object' && typeof x.length === 'number' ? Array.from(x).flatMap((v) => (v !== null && typeof v === 'object' ? Array.from(v) : [v])) : null)
+  const floor = numbers(masking.floor)
+  const spread = masking.spread === null || masking.spread === undefined ? null : numbers(masking.spread)
+  if (!floor || floor.length !== 52) throw new TypeError('masking.floor must hold 52 numbers')
+  if (masking.spread !== null && masking.spread !== undefined && (!spread || spread.length !== 52 * 52)) throw new TypeError('masking.spread must be null or hold 52 * 52 numbers')
+  floor.forEach((v, b) => {
+    if (typeof v !== 'number' || !(v >= 1e-60 && v <= 1e60)) throw new TypeError(`masking.floor[${b}] = ${v} is outside [1e-60, 1e60]`)
+  })
+  if (spread) {
+    spread.forEach((v, i) => {
+      if (typeof v !== 'number' || !(v >= 0 && v <= 1e60)) throw new TypeError(`masking.spread[${i}] = ${v} is outside [0, 1e60]`)
+    })
+  }
+  return { floor: Float64Array.from(floor), spread: spread ? Float64Array.from(spread) : null }
+}
+
+export function encodeMeasured(channels, nativeOptions, modes = null, scaleFactorOffsets = null, masking = null, haloFrames = 0, ctx = context()) {
+  if (typeof scaleFactorOffsets === 'number') return encodeMeasured(channels, nativeOptions, modes, null, null, scaleFactorOffsets, masking || context())
+  if (typeof masking === 'number') return encodeMeasured(channels, nativeOptions, modes, scaleFactorOffsets, null, masking, haloFrames || context())
+  if (masking !== null && masking !== undefined) {
+    const tables = checkMasking(masking)
+    const offsets = scaleFactorOffsets === null || scaleFactorOffsets === undefined ? Int8Array.of(0) : checkScaleFactorOffsets(scaleFactorOffsets)
+    return native().encodeMeasuredMasked(ctx, channels, haloFrames, nativeOptions, modes, offsets, tables.floor, tables.spread)
+  }
   if (scaleFactorOffsets === null || scaleFactorOffsets === undefined) return native().encodeMeasured(ctx, channels, haloFrames, nativeOptions, modes)
   return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }

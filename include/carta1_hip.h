@@ -449,6 +449,57 @@ int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channe
                                 int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                 double *energy /* host, or NULL */);
 
+/* ---- the measured allocation with every BFU's error weighted by a masking threshold ------------------------------------------
+ * c1_encode_measured_sf_* minimises the plain squared error of the coefficients, so its greedy spends bits where the signal is
+ * loud.  This call divides every BFU's error by a threshold computed per sound unit from the unit's own spectrum and two tables
+ * of the caller's, and minimises that noise-to-mask ratio instead.  OPT-IN like its siblings; the units are ordinary sound
+ * units.  The figures are noise-to-mask under this model; nobody has listened to the result.  Notation as above.
+ *   Tables (HOST memory in both calls).  mask_floor: 52 values, each finite and within [1e-60, 1e60].  mask_spread: 52 * 52
+ *     values, row-major, mask_spread[52 b + c] = masker c onto maskee b, each finite and within [0, 1e60]; or NULL = all zero.
+ *     Anything else is C1_ERR_ARG naming the table and the index, with every output untouched.
+ *   Weights, per unit, in binary64 with no fused operation:
+ *     E_c   = e(c,0), c = 0 .. 51 (W_c * sum_j x_c[j]^2, j ascending)
+ *     M_b   = sum_c mask_spread[52 b + c] * E_c, c ascending, each product rounded and then added to a sum that starts at +0.0;
+ *             +0.0 with mask_spread NULL
+ *     thr_b = M_b > mask_floor[b] ? M_b : mask_floor[b]   (a NaN M_b falls to the floor)
+ *     P_b   = 1.0 / thr_b
+ *   Error table.  e'_k(b,w) = P_b * e_k(b,w), level 0 included; the multiply is applied to the finished e_k(b,w), after the W_b
+ *     multiply.  The minimum over the candidates and pick (first candidate, strictly smaller wins), the gains, the greedy, the
+ *     totals, the first amount of least T and the NaN rule are c1_encode_measured_sf_*'s, run on e'.
+ *   Fallback.  T_ref = sum_b e'_0(b, wl_ref[b]); taken[u] = T(n*) < T_ref.
+ *   Records, shifts, the packing of a taken unit and the bytes of a unit not taken (the plain encode's) are
+ *     c1_encode_measured_sf_*'s: the bytes do not reveal the weights.
+ * Outputs: distortion holds the weighted T_ref and T(n*); energy = sum_b e'(b,0) in BFU order; weights[52 u + b] = P_b for all
+ * 52 BFUs, taken or not, also in a measure-only call; units, taken and shifts as above.  Each may be NULL; all six NULL is
+ * C1_ERR_ARG.
+ * Consequences.  With mask_floor all 1.0 and mask_spread NULL or all zero, P_b is exactly 1.0 and units, taken, shifts,
+ * distortion and energy are bit for bit c1_encode_measured_sf_*'s.  Scaling both tables by 4.0 leaves units, taken and shifts
+ * unchanged and multiplies distortion, energy and weights by exactly 0.25.  Everything else -- the offsets' rules, modes,
+ * limits, chunking, asynchrony, invariance under the speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP
+ * and the halo, repeatability, "measure" in c1_ctx_kernel_ms -- is c1_encode_measured_sf_*'s.  The tables are copied into a
+ * buffer of the context (22 048 bytes) on the context's stream by every call, behind the work of every earlier call: the
+ * caller's arrays are free when the call returns, and no other call reads the buffer. */
+int c1_encode_measured_masked_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                     const c1_encode_options *opts, const uint8_t *modes /* device, frames*channels, or NULL */,
+                                     const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
+                                     const double *mask_floor /* HOST, 52 */, const double *mask_spread /* HOST, 52*52, or NULL */,
+                                     uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                                     uint8_t *taken /* device, frames*channels, or NULL */,
+                                     int8_t *shifts /* device, frames*channels*52, or NULL */,
+                                     double *distortion /* device, frames*channels*2: weighted T_ref, T(n*), or NULL */,
+                                     double *energy /* device, frames*channels, or NULL */,
+                                     double *weights /* device, frames*channels*52: P_b, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The options, the offsets, the tables, the outputs and every mode byte are
+ * validated before the context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and
+ * without a device the call then returns C1_ERR_NO_DEVICE.  frames 0 .. 2^22 per channel. */
+int c1_encode_measured_masked_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                    const c1_encode_options *opts, const uint8_t *modes /* host, or NULL */,
+                                    const int8_t *sf_offsets /* host, n_offsets values */, int n_offsets,
+                                    const double *mask_floor /* host, 52 */, const double *mask_spread /* host, 52*52, or NULL */,
+                                    uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                    int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                    double *energy /* host, or NULL */, double *weights /* host, or NULL */);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
