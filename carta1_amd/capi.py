@@ -119,6 +119,8 @@ SIGNATURES = {
     'c1_enc_stream_push_modes': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p]),
     'c1_enc_stream_push_biases': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(EncodeOptions), C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_enc_stream_push_measured': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_enc_stream_destroy': (C.c_int, [C.c_void_p]),
     'c1_enc_stream_set_options': (C.c_int, [C.c_void_p, C.POINTER(EncodeOptions)]),
     'c1_dec_stream_create': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

@@ -980,6 +980,44 @@ class EncoderStream:
             capi.check(capi.load().c1_enc_stream_push_modes(self._h, ptrs, frames, m.ctypes.data, units.ctypes.data))
         return units
 
+    def push_measured(self, channels, modes=None, scale_factor_offsets=None, masking=None, return_distortion=False,
+                      return_shifts=False, return_weights=False):
+        """push() with the word lengths (and, with scale_factor_offsets, the scale-factor indices) of every pushed unit
+        allocated by the measured coding error: Context.encode_measured on a live stream (c1_enc_stream_push_measured).  The
+        analysis, the block modes and the reference's own record per unit are push()'s (push(modes=...)'s when modes is
+        given); the measured allocation keeps no state, so the stream afterwards is what it is after the plain push and the
+        kinds of push may be mixed.  modes, scale_factor_offsets, masking, the return_* flags, their ValueErrors and the
+        result -- (units, taken[, shifts][, distortion, energy][, weights]) -- are Context.encode_measured's."""
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        if len(chans) != self.channels:
+            raise ValueError('expected %d channels' % self.channels)
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = n // 512
+        m = None if modes is None else check_block_modes(modes, frames, self.channels)
+        if return_shifts and scale_factor_offsets is None:
+            raise ValueError('return_shifts needs scale_factor_offsets')
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
+        count = frames * self.channels
+        units = np.zeros((count, 212), dtype=np.uint8)
+        taken = np.zeros(count, dtype=np.uint8)
+        shifts = np.zeros((count, 52), dtype=np.int8) if return_shifts else None
+        dist = np.zeros((count, 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros(count, dtype=np.float64) if return_distortion else None
+        weights = np.zeros((count, 52), dtype=np.float64) if return_weights else None
+        data = lambda a: None if a is None else a.ctypes.data
+        capi.check(capi.load().c1_enc_stream_push_measured(
+            self._h, capi.ptr_array([c.ctypes.data for c in chans]), frames, data(m), data(offs), 0 if offs is None else len(offs),
+            None if mask is None else mask[0].ctypes.data, None if mask is None else data(mask[1]), units.ctypes.data,
+            taken.ctypes.data, data(shifts), data(dist), data(energy), data(weights)))
+        out = (units, taken) + ((shifts,) if return_shifts else ())
+        out = out + (dist, energy) if return_distortion else out
+        return out + (weights,) if return_weights else out
+
     def set_options(self, options):
         """The options of every channel from the next push on, as the reference's encode() reads them on every call; the
         stream goes on (include/carta1_hip.h, c1_enc_stream_set_options).  Invalid options raise and change nothing."""

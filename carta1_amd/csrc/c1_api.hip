@@ -486,6 +486,7 @@ struct c1_ctx {
   int ws_next = 0;
   int64_t chunk_frames = 0;
   bool pipeline = true;
+  int measured_wide = -1;                         // C1_MEASURED_WIDE: -1 unset (the threshold decides), 0 never, 1 always
   hipStream_t s_ana = nullptr, s_rest = nullptr;  // internal streams of the two pipeline halves
   hipEvent_t ev_in = nullptr, ev_ana[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_end[2] = {nullptr, nullptr};
   // profiling
@@ -880,6 +881,36 @@ int collect_timings(c1_ctx *ctx) {
   return C1_OK;
 }
 
+// The measured step of one launch, between the allocation chain and packing: L.coefs / L.side / L.alloc hold the launch's units,
+// whose outputs start at unit `at` of the call's.  A taken unit's record in L.alloc and the scale-factor bytes of its side record
+// are rewritten when the launch packs (L.units), where every packing kernel reads them.  Which kernel: by the call's arguments
+// (tables: c1_encode_measured_masked_device; offsets alone: _sf_; neither: c1_encode_measured_device), and the workgroup-per-unit
+// kernel (c1_k_measured_wide.hip, the same outputs bit for bit) for a launch of at most kMeasuredWideUnits units
+void launch_measured(c1_ctx *ctx, const C1EncodeLaunch &L, bool all_long, const MeasuredCall *mc, int64_t at, hipStream_t stream) {
+  ScopedTiming t(ctx, K_MEASURE, stream);
+  uint8_t *taken = mc->taken ? mc->taken + at : nullptr;
+  int8_t *shifts = mc->shifts ? mc->shifts + at * 52 : nullptr;
+  double *distortion = mc->distortion ? mc->distortion + at * 2 : nullptr, *energy = mc->energy ? mc->energy + at : nullptr;
+  double *weights = mc->weights ? mc->weights + at * 52 : nullptr;
+  const bool finalize = L.units != nullptr;
+  const int64_t units = L.frames * L.channels;
+  const bool wide = ctx->measured_wide < 0 ? units <= kMeasuredWideUnits : ctx->measured_wide != 0;
+  if (wide) {
+    static const int8_t kNoOffset[1] = {0};
+    c1k_launch_measured_wide(L, all_long, finalize, mc->sf_offsets ? mc->sf_offsets : kNoOffset, mc->sf_offsets ? mc->n_offsets : 1, mc->mask,
+                             mc->has_spread, taken, mc->sf_offsets ? shifts : nullptr, distortion, energy, weights, stream);
+  } else if (mc->mask) {
+    // the same over e' = P_b * e, P_b from the unit's own level-0 errors and the tables
+    c1k_launch_measured_masked(L, all_long, finalize, mc->sf_offsets, mc->n_offsets, mc->mask, mc->has_spread, taken, shifts, distortion,
+                               energy, weights, stream);
+  } else if (mc->sf_offsets) {
+    // the same over the least error of the candidate scale-factor indices
+    c1k_launch_measured_sf(L, all_long, finalize, mc->sf_offsets, mc->n_offsets, taken, shifts, distortion, energy, stream);
+  } else {
+    c1k_launch_measured_alloc(L, all_long, finalize, taken, distortion, energy, stream);
+  }
+}
+
 int check_channels(int channels) {
   if (channels != 1 && channels != 2) return fail(C1_ERR_ARG, "channels must be 1 or 2, got %d", channels);
   return C1_OK;
@@ -1159,30 +1190,9 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
       ScopedTiming t(ctx, K_ALLOCATE, sB);
       c1k_launch_allocate_palette(L, ctx->d_palette, pal->n, pal->index + f0 * channels, ctx->d_pal_lists, ctx->d_pal_lists + 8, n * channels, sB);
     } else { ScopedTiming t(ctx, K_ALLOCATE, sB); c1k_launch_allocate(L, sB); }
-    if (mc) {
-      // mc (c1_encode_measured_device): the allocation chain above left the reference's record of every unit; k_measured_alloc
-      // builds the unit's error table, allocates greedily by it, and replaces the record where that codes with less error
-      ScopedTiming t(ctx, K_MEASURE, sB);
-      if (mc->mask) {
-        // c1_encode_measured_masked_device: the same again over e' = P_b * e, P_b from the unit's own level-0 errors and the tables
-        c1k_launch_measured_masked(L, all_long, L.units != nullptr, mc->sf_offsets, mc->n_offsets, mc->mask, mc->has_spread,
-                                   mc->taken ? mc->taken + f0 * channels : nullptr, mc->shifts ? mc->shifts + f0 * channels * 52 : nullptr,
-                                   mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
-                                   mc->energy ? mc->energy + f0 * channels : nullptr,
-                                   mc->weights ? mc->weights + f0 * channels * 52 : nullptr, sB);
-      } else if (mc->sf_offsets) {
-        // c1_encode_measured_sf_device: the same over the least error of the candidate scale-factor indices; a taken unit's chosen
-        // indices replace the scale-factor bytes of its side record, where the packing kernels read them
-        c1k_launch_measured_sf(L, all_long, L.units != nullptr, mc->sf_offsets, mc->n_offsets, mc->taken ? mc->taken + f0 * channels : nullptr,
-                               mc->shifts ? mc->shifts + f0 * channels * 52 : nullptr,
-                               mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
-                               mc->energy ? mc->energy + f0 * channels : nullptr, sB);
-      } else {
-        c1k_launch_measured_alloc(L, all_long, L.units != nullptr, mc->taken ? mc->taken + f0 * channels : nullptr,
-                                  mc->distortion ? mc->distortion + f0 * channels * 2 : nullptr,
-                                  mc->energy ? mc->energy + f0 * channels : nullptr, sB);
-      }
-    }
+    // mc (c1_encode_measured_device): the allocation chain above left the reference's record of every unit; the measured kernel
+    // builds the unit's error table, allocates greedily by it, and replaces the record where that codes with less error
+    if (mc) launch_measured(ctx, L, all_long, mc, f0 * channels, sB);
     if (L.units && quantize32) {
       // The coefficients are the reference's, and still the quantization need not be done in binary64: the packing
       // kernel of the speculative path with a bound of zero forms |x| norm + 0.5 in binary32 and accepts a mantissa only
@@ -1409,6 +1419,10 @@ int c1_ctx_create(int device, void *hip_stream, c1_ctx **out) {
     const char *pl = getenv("C1_PIPELINE");
     ctx->pipeline = pl ? atoi(pl) != 0 : false;   // measured: no gain while one kernel's grid already owns every CU's LDS
   }
+  // C1_MEASURED_WIDE: 0 never takes the workgroup-per-unit measured kernel, 1 always; unset: launches of at most
+  // kMeasuredWideUnits units take it.  The outputs are the same bits either way
+  const char *mw = getenv("C1_MEASURED_WIDE");
+  ctx->measured_wide = mw ? (atoi(mw) != 0 ? 1 : 0) : -1;
   const char *env = getenv("C1_CHUNK_FRAMES");
   ctx->chunk_frames = env ? atoll(env) : (int64_t)1 << 24;   // chunk_for_call() cuts it down to what fits
   if (ctx->chunk_frames < 16) ctx->chunk_frames = 16;
@@ -3455,6 +3469,8 @@ struct c1_enc_stream {
   uint8_t *d_units = nullptr;
   uint8_t *d_given = nullptr;      // mode bytes of a push with given modes (c1_enc_stream_push_modes), cap_frames * channels
   uint8_t *d_bias = nullptr;       // bias index bytes of a push with a palette (c1_enc_stream_push_biases), cap_frames * channels
+  void *d_meas = nullptr;          // the per-unit outputs of a measured push (c1_enc_stream_push_measured), meas_units units
+  int64_t meas_units = 0;
   int64_t cap_frames = 0;
   int64_t pushed = 0;              // frames per channel encoded so far
   EncHistory hist = HIST_PREV;     // where the detection history of the next frame lives (same for every channel)
@@ -3519,7 +3535,9 @@ int enc_stream_bands(c1_enc_stream *s, const float *const *pcm, int64_t frames, 
 // blockSelectorStage against the stored bands or a fresh pool's zeros, mdctStage with t-1's bands as the overlap,
 // quantizationStage, serializeFrame -> units[c * 212].
 // per_channel: when not null, channel c's allocation runs under per_channel[c] (the stream's options with another bias table)
-int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *units, const c1_encode_options *per_channel = nullptr) {
+// mc: when not null, the measured allocation of channel c (output row c) runs between its allocation and its fields
+int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *units, const c1_encode_options *per_channel = nullptr,
+                            const MeasuredCall *mc = nullptr) {
   c1_ctx *ctx = s->ctx;
   EncSwitchScratch &w = s->sw;
   const int C = s->channels;
@@ -3555,6 +3573,13 @@ int enc_stream_switch_frame(c1_enc_stream *s, const float *const *pcm, uint8_t *
     L.sel_list = w.work1 + 4 + 7;
     if (per_channel && (rc = upload_opts(ctx, &per_channel[c]))) return rc;
     c1k_launch_allocate(L, ctx->stream);
+    if (mc) {
+      // the measured kernel takes the unit's modes from the side record, where k_stage_scale_factors left zeros; a taken unit's
+      // allocation record and scale-factor bytes are rewritten in place, and k_stage_fields reads both
+      HIP_TRY(hipMemcpyAsync(w.side1 + 52, w.mode_byte, 1, hipMemcpyDeviceToDevice, ctx->stream));
+      L.units = units + (size_t)c * C1_UNIT_BYTES;             // the launch packs: the records are finalized
+      launch_measured(ctx, L, false, mc, c, ctx->stream);
+    }
     c1k_launch_stage_fields(ctx->d_tables, w.coef1, modes, w.side1, w.alloc1, 1, w.nbfu, w.sfi, w.wl, w.q, ctx->stream);
     c1k_launch_pack_units(w.nbfu, modes, w.sfi, w.wl, w.q, 1, units + (size_t)c * C1_UNIT_BYTES, ctx->stream);
     HIP_TRY(hipGetLastError());
@@ -3569,8 +3594,10 @@ constexpr int64_t kStateDecodeChunk = 65536;      // pools whose unpacked fields
 
 // n pools on the context's stream: the from-state kernel into the workspace, then the encoder's own allocation and packing
 // kernels on it (one unit per pool).  Device pointers; pool i reads pcm + i * pcm_stride.  out may be in, or null.
+// mc: when not null, the measured allocation of pool i (output row mc_at + i) runs between its allocation and packing
 int encode_from_states_impl(c1_ctx *ctx, int64_t n, const float *pcm, int64_t pcm_stride, const float *in,
-                            const c1_encode_options *opts, uint8_t *units, float *out) {
+                            const c1_encode_options *opts, uint8_t *units, float *out, const MeasuredCall *mc = nullptr,
+                            int64_t mc_at = 0) {
   int rc;
   if ((rc = upload_opts(ctx, opts))) return rc;
   if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
@@ -3608,6 +3635,7 @@ int encode_from_states_impl(c1_ctx *ctx, int64_t n, const float *pcm, int64_t pc
     L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
     L.units = units + n0 * C1_UNIT_BYTES;
     { ScopedTiming t(ctx, K_ALLOCATE); c1k_launch_allocate(L, ctx->stream); }
+    if (mc) launch_measured(ctx, L, false, mc, mc_at + n0, ctx->stream);   // the side records carry the pools' mode bytes
     { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
   }
   HIP_TRY(hipGetLastError());
@@ -3691,7 +3719,8 @@ int enc_stream_freeze_history(c1_enc_stream *s) {
 }
 
 int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
-                         const c1_encode_options *palette = nullptr, int n_palette = 0, const uint8_t *bias_index = nullptr);
+                         const c1_encode_options *palette = nullptr, int n_palette = 0, const uint8_t *bias_index = nullptr,
+                         const MeasuredCall *mc = nullptr, const MeasuredCall *mc_host = nullptr);
 }  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
@@ -3749,14 +3778,76 @@ int c1_enc_stream_push_biases(c1_enc_stream *s, const float *const *pcm, int64_t
   return enc_stream_push_impl(s, pcm, frames, modes, units, palette, n_palette, bias_index);
 }
 
+int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes,
+                                const int8_t *sf_offsets, int n_offsets, const double *mask_floor, const double *mask_spread,
+                                uint8_t *units, uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a stream nor a device
+  const char *const what = "c1_enc_stream_push_measured";
+  int rc;
+  if (mask_spread && !mask_floor) return fail(C1_ERR_ARG, "%s: mask_spread is given without mask_floor", what);
+  if (weights && !mask_floor) return fail(C1_ERR_ARG, "%s: weights is given without mask_floor", what);
+  if (!sf_offsets && n_offsets != 0) return fail(C1_ERR_ARG, "%s: n_offsets = %d, but sf_offsets is NULL", what, n_offsets);
+  if (sf_offsets && (rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if (mask_floor && (rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  if (!s) return fail(C1_ERR_ARG, "stream is NULL");
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames < 0) return fail(C1_ERR_ARG, "frames must be >= 0");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts(what, &s->opts, modes == nullptr))) return rc;
+  if (frames == 0) return C1_OK;
+  if (!pcm || !units) return fail(C1_ERR_ARG, "pcm or units is NULL");
+  for (int c = 0; c < s->channels; c++)
+    if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  if (modes && (rc = check_mode_bytes(what, modes, frames, s->channels))) return rc;
+  // from here on only the device can fail.  The outputs' staging: one block, grown to the largest push so far
+  const int64_t n_units = frames * s->channels;
+  if (n_units > s->meas_units) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (s->d_meas) (void)hipFree(s->d_meas);
+    s->d_meas = nullptr; s->meas_units = 0;
+    HIP_TRY(hipMalloc(&s->d_meas, (size_t)n_units * (52 * sizeof(double) + 3 * sizeof(double) + 52 + 8)));
+    s->meas_units = n_units;
+  }
+  char *block = static_cast<char *>(s->d_meas);
+  const size_t cap = (size_t)s->meas_units;
+  double *d_weights = reinterpret_cast<double *>(block), *d_dist = d_weights + cap * 52, *d_energy = d_dist + cap * 2;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>(d_energy + cap);
+  uint8_t *d_taken = reinterpret_cast<uint8_t *>(d_shifts + cap * 52);
+  static const int8_t kOwnIndex[1] = {0};                      // tables without offsets: the masked call with the single offset 0
+  MeasuredCall mc = {taken ? d_taken : nullptr, distortion ? d_dist : nullptr, energy ? d_energy : nullptr};
+  if (sf_offsets || mask_floor) {
+    mc.sf_offsets = sf_offsets ? sf_offsets : kOwnIndex;
+    mc.n_offsets = sf_offsets ? n_offsets : 1;
+    mc.shifts = shifts ? d_shifts : nullptr;
+  }
+  if (mask_floor) {
+    if ((rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+    mc.mask = ctx->d_mask;
+    mc.has_spread = mask_spread != nullptr;
+    mc.weights = weights ? d_weights : nullptr;
+  }
+  MeasuredCall host = {taken, distortion, energy};
+  host.shifts = shifts;
+  host.weights = weights;
+  if ((rc = enc_stream_push_impl(s, pcm, frames, modes, units, nullptr, 0, nullptr, &mc, &host))) return rc;
+  if (shifts && !mc.shifts) memset(shifts, 0, (size_t)n_units * 52);   // c1_encode_measured_*: no index moves
+  return C1_OK;
+}
+
 namespace {
 // modes null: the stream's options decide.  Else the frames behave as if the options had been switched to fixed block modes
 // for them, frame by frame and channel by channel, and back afterwards: the detector does not run, and on a stream under
 // detection its history stays where c1_enc_stream_set_options would have frozen it.
 // palette non-null (c1_enc_stream_push_biases): unit u allocates under the table of palette[bias_index[u]] instead of the
 // stream's; nothing else of the entries is read, and the stream's options and state are as after the same push without it
+// mc non-null (c1_enc_stream_push_measured, everything validated and the tables uploaded): the measured allocation runs between
+// allocation and packing on whichever of the three paths a frame takes; mc's outputs are device memory over the push's units and
+// are copied to mc_host's with the units.  It keeps no state: the stream is as after the same push without it
 int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
-                         const c1_encode_options *palette, int n_palette, const uint8_t *bias_index) {
+                         const c1_encode_options *palette, int n_palette, const uint8_t *bias_index, const MeasuredCall *mc,
+                         const MeasuredCall *mc_host) {
   if (!s) return fail(C1_ERR_ARG, "stream is NULL");
   c1_ctx *ctx = s->ctx;
   CTX_GUARD(ctx);
@@ -3814,23 +3905,34 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   // the frames that are not encoded from the explicit state: the stream's options, or the given modes in their place
   auto encode_rest = [&](const float *const *p, int64_t first, int64_t n) {
     uint8_t *out = s->d_units + (size_t)first * s->channels * C1_UNIT_BYTES;
-    if (!modes && !palette) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
+    if (!modes && !palette && !mc) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
+    MeasuredCall part;
+    if (mc) {                                                  // the call's outputs from unit first * channels on
+      const int64_t at = first * s->channels;
+      part = *mc;
+      if (part.taken) part.taken += at;
+      if (part.shifts) part.shifts += at * 52;
+      if (part.distortion) part.distortion += at * 2;
+      if (part.energy) part.energy += at;
+      if (part.weights) part.weights += at * 52;
+    }
     const PaletteCall pc = {n_palette, palette ? s->d_bias + (size_t)first * s->channels : nullptr};
     return encode_device_impl(ctx, p, s->channels, n, 2, &s->opts, out, nullptr, nullptr, nullptr, nullptr, false,
-                              modes ? s->d_given + (size_t)first * s->channels : nullptr, palette ? &pc : nullptr);
+                              modes ? s->d_given + (size_t)first * s->channels : nullptr, palette ? &pc : nullptr, nullptr, nullptr,
+                              mc ? &part : nullptr);
   };
   if (from_state > 0) {
     for (int64_t f = 0; f < from_state; f++) {   // frame after frame: each continues the pool the one before left
       if (!modes && !palette) {
         if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
-                                          s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state))) return rc;
+                                          s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state, mc, f * s->channels))) return rc;
         continue;
       }
       for (int c = 0; c < s->channels; c++) {    // the from-state kernel takes one triple per launch: a pool at a time
         const c1_encode_options one = unit_opts(f, c);
         if ((rc = encode_from_states_impl(ctx, 1, dptr[c] + f * 512, (int64_t)stride, s->d_state + (size_t)c * kEncStateFloats, &one,
                                           s->d_units + (size_t)(f * s->channels + c) * C1_UNIT_BYTES,
-                                          s->d_state + (size_t)c * kEncStateFloats))) return rc;
+                                          s->d_state + (size_t)c * kEncStateFloats, mc, f * s->channels + c))) return rc;
       }
     }
     if (frames > from_state) {
@@ -3840,7 +3942,7 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
     }
   } else if (switch_frame) {
     const c1_encode_options per_channel[C1_MAX_CHANNELS] = {unit_opts(0, 0), unit_opts(0, s->channels - 1)};
-    if ((rc = enc_stream_switch_frame(s, dptr, s->d_units, palette ? per_channel : nullptr))) return rc;
+    if ((rc = enc_stream_switch_frame(s, dptr, s->d_units, palette ? per_channel : nullptr, mc))) return rc;
     if (frames > 1) {
       const float *rest[C1_MAX_CHANNELS] = {nullptr, nullptr};
       for (int c = 0; c < s->channels; c++) rest[c] = dptr[c] + 512;
@@ -3853,6 +3955,14 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
     HIP_TRY(hipMemcpyAsync(s->d_hist + 1024 * c, s->d_buf + stride * c + (size_t)frames * 512, 1024 * sizeof(float),
                            hipMemcpyDeviceToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(units, s->d_units, (size_t)s->channels * frames * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (mc && mc_host) {
+    const size_t n_units = (size_t)s->channels * frames;
+    if (mc_host->taken) HIP_TRY(hipMemcpyAsync(mc_host->taken, mc->taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+    if (mc_host->shifts && mc->shifts) HIP_TRY(hipMemcpyAsync(mc_host->shifts, mc->shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
+    if (mc_host->distortion) HIP_TRY(hipMemcpyAsync(mc_host->distortion, mc->distortion, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (mc_host->energy) HIP_TRY(hipMemcpyAsync(mc_host->energy, mc->energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (mc_host->weights) HIP_TRY(hipMemcpyAsync(mc_host->weights, mc->weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   s->pushed += frames;
   if (from_state > 0) {
@@ -3876,6 +3986,7 @@ int c1_enc_stream_destroy(c1_enc_stream *s) {
   if (s->d_units) hipFree(s->d_units);
   if (s->d_given) hipFree(s->d_given);
   if (s->d_bias) hipFree(s->d_bias);
+  if (s->d_meas) hipFree(s->d_meas);
   if (s->d_sw_block) hipFree(s->d_sw_block);
   if (s->d_state) hipFree(s->d_state);
   delete s;

@@ -360,6 +360,15 @@ void c1k_launch_measured_sf(const C1EncodeLaunch &L, bool all_long, bool finaliz
 void c1k_launch_measured_masked(const C1EncodeLaunch &L, bool all_long, bool finalize, const int8_t *sf_offsets, int n_offsets,
                                 const double *mask, bool has_spread, uint8_t *taken, int8_t *shifts, double *distortion, double *energy,
                                 double *weights, hipStream_t stream);
+// the three launches above for few units (c1_k_measured_wide.hip): a workgroup of eight waves per unit, the sixteen table rows
+// dealt over the waves and one greedy amount per wave; every output is bit for bit the kernels' above.  mask null: P_b = 1 and no
+// weights (c1k_launch_measured_sf); one offset 0 besides: c1k_launch_measured_alloc
+void c1k_launch_measured_wide(const C1EncodeLaunch &L, bool all_long, bool finalize, const int8_t *sf_offsets, int n_offsets,
+                              const double *mask, bool has_spread, uint8_t *taken, int8_t *shifts, double *distortion, double *energy,
+                              double *weights, hipStream_t stream);
+// launches of at most this many units take c1k_launch_measured_wide: the largest count of DESIGN.md 6l's sweep (1 .. 8 192 units),
+// at every one of which it was the faster kernel (5 times at up to 256 units, 1.3 times at 8 192); C1_MEASURED_WIDE overrides
+constexpr int64_t kMeasuredWideUnits = 8192;
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -887,6 +887,36 @@ napi_value EncStreamPush(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encStreamPushMeasured(stream, [Float32Array...], Int8Array offsets | null, Float64Array floor | null, Float64Array spread | null)
+// -> Uint8Array units: encStreamPush with the measured allocation of encodeMeasured (offsets and tables null), encodeMeasuredSf
+// (offsets) or encodeMeasuredMasked (tables; without offsets the single offset 0): c1_enc_stream_push_measured
+napi_value EncStreamPushMeasured(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  c1_enc_stream *s;
+  std::vector<float *> ch;
+  size_t samples = 0, n[3] = {0, 0, 0};
+  void *data[3] = {nullptr, nullptr, nullptr};
+  if (!get_external(env, argv[0], &s) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  const napi_typedarray_type kinds[3] = {napi_int8_array, napi_float64_array, napi_float64_array};
+  for (int k = 0; k < 3; k++) {
+    napi_valuetype t;
+    NAPI_OK(napi_typeof(env, argv[2 + k], &t));
+    if (t != napi_null && t != napi_undefined && !get_typed(env, argv[2 + k], kinds[k], &data[k], &n[k])) return nullptr;
+  }
+  if ((data[1] && n[1] != 52) || (data[2] && n[2] != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (samples % 512) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  if (n[0] > 64) n[0] = 64;                                     // the library's own check names the limit
+  const int64_t frames = (int64_t)(samples / 512);
+  uint8_t *units;
+  napi_value out = make_u8(env, (size_t)frames * ch.size() * C1_UNIT_BYTES, &units);
+  const float *p[2] = {ch[0], ch.size() > 1 ? ch[1] : nullptr};
+  const int rc = c1_enc_stream_push_measured(s, p, frames, nullptr, static_cast<const int8_t *>(data[0]), data[0] ? (int)n[0] : 0,
+                                             static_cast<const double *>(data[1]), static_cast<const double *>(data[2]), units, nullptr,
+                                             nullptr, nullptr, nullptr, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 // encStreamSetOptions(stream, packedOptions): the options of the next push on (c1_enc_stream_set_options)
 napi_value EncStreamSetOptions(napi_env env, napi_callback_info info) {
   napi_value argv[2];
@@ -1361,6 +1391,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"decodeSignals", nullptr, DecodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamPushMeasured", nullptr, EncStreamPushMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamGetState", nullptr, StreamGetState<c1_enc_stream, c1_enc_state, c1_enc_stream_get_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetState", nullptr, StreamSetState<c1_enc_stream, c1_enc_state, c1_enc_stream_set_state>, nullptr, nullptr, nullptr, napi_default, nullptr},

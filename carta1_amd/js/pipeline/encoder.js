@@ -7,16 +7,37 @@ import { EncoderOptions } from '../core/options.js'
 import { BufferPool } from '../core/buffers.js'
 import { SAMPLES_PER_FRAME, SCALE_FACTORS, SPECS_PER_BFU } from '../core/constants.js'
 import { deserializeFrame } from '../io/serialization.js'
-import { native, context } from '../native.js'
+import { native, context, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { throwError } from '../utils.js'
 
-export function encode(options = new EncoderOptions(), bufferPool = new BufferPool()) {
+// measured (not in the reference; optional, read per call as `options` is): { measuredAllocation: true, scaleFactorOffsets,
+// masking } allocates the frame's word lengths -- with scaleFactorOffsets its scale-factor indices too, with masking under a
+// masking threshold -- by the measured coding error, as encodeAeaPcm's options of the same names do (include/carta1_hip.h,
+// c1_enc_stream_push_measured).  The measured allocation keeps no state, so frames with and without it may alternate on one
+// pool.  Without the object, or with measuredAllocation falsy, the closure is the reference's, byte for byte; scaleFactorOffsets
+// or masking without measuredAllocation: true is encodeAeaPcm's TypeError.
+function measuredArguments(measured) {
+  if (measured === undefined || measured === null) return null
+  const { measuredAllocation, scaleFactorOffsets, masking } = measured
+  if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
+    throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
+  }
+  const haveOffsets = scaleFactorOffsets !== undefined && scaleFactorOffsets !== null
+  if (haveOffsets && !measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
+  const haveMasking = masking !== undefined && masking !== null && masking !== false
+  if (haveMasking && !measuredAllocation) throw new TypeError('masking needs measuredAllocation: true; no other path weighs its errors')
+  if (!measuredAllocation) return null
+  return { offsets: haveOffsets ? checkScaleFactorOffsets(scaleFactorOffsets) : null, tables: haveMasking ? checkMasking(masking) : { floor: null, spread: null } }
+}
+
+export function encode(options = new EncoderOptions(), bufferPool = new BufferPool(), measured = undefined) {
   if (!bufferPool) throwError('qmfAnalysisStage: bufferPool is required')
   if (!options) throwError('blockSelectorStage: options is required')
   return (pcmSamples) => {
     if (!(pcmSamples instanceof Float32Array) || pcmSamples.length !== SAMPLES_PER_FRAME) {
       throwError(`encode: expected a Float32Array of ${SAMPLES_PER_FRAME} samples`)
     }
+    const how = measuredArguments(measured)   // before anything changes: a TypeError leaves the pool as it was
     const addon = native()
     // options are read per call, as the reference's stages do (encoder.js:131,381); a change goes on with the same stream
     // from the next frame, detection history included (include/carta1_hip.h, c1_enc_stream_set_options)
@@ -33,7 +54,9 @@ export function encode(options = new EncoderOptions(), bufferPool = new BufferPo
       addon.encStreamSetOptions(bufferPool.encoderStream, packed)
       bufferPool.encoderOptionsKey = key
     }
-    const unit = addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
+    const unit = how
+      ? addon.encStreamPushMeasured(bufferPool.encoderStream, [pcmSamples], how.offsets, how.tables.floor, how.tables.spread)
+      : addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
     const fields = deserializeFrame(unit)
     if (options.fixedBlockModes) fields.blockModes = options.fixedBlockModes // same array, as encoder.js:131-132
     return fields

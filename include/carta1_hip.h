@@ -568,6 +568,42 @@ int c1_enc_stream_push_modes(c1_enc_stream *s, const float *const *pcm /* host *
 int c1_enc_stream_push_biases(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
                               const c1_encode_options *palette, int n_palette, const uint8_t *bias_index /* host, frames*channels */,
                               const uint8_t *modes /* host, frames*channels, or NULL */, uint8_t *units /* host */);
+/* c1_enc_stream_push (modes NULL) or c1_enc_stream_push_modes (modes given) with the word lengths, and optionally the scale-factor
+ * indices, of every pushed unit allocated by the measured coding error: the streaming form of c1_encode_measured_*,
+ * c1_encode_measured_sf_* and c1_encode_measured_masked_*, which are nested bit for bit (flat tables give the sf call, the single
+ * offset 0 the plain one).  The call the push behaves as follows from its arguments:
+ *     mask_floor   sf_offsets
+ *     non-NULL     non-NULL     c1_encode_measured_masked_* with those offsets
+ *     non-NULL     NULL         c1_encode_measured_masked_* with the single offset 0; n_offsets must be 0
+ *     NULL         non-NULL     c1_encode_measured_sf_*
+ *     NULL         NULL         c1_encode_measured_*; n_offsets must be 0
+ * Definition.  The analysis of the pushed frames, their block modes and the record the reference's allocation chain leaves per
+ * unit are exactly what c1_enc_stream_push computes for the same PCM on the same stream (c1_enc_stream_push_modes when modes is
+ * given).  On top of that record every unit is the per-unit function defined above for c1_encode_measured_masked_*, word for
+ * word: weights, error table, candidates and pick, gains, greedy, totals, the first amount of least T, the NaN rule, the fallback
+ * against T_ref, the records of a taken unit and its packing.  This holds for every frame of the push, including the ones a
+ * stream encodes one at a time (the first two after c1_enc_stream_set_state, the first after a switch back to detection).
+ * The measured allocation keeps no state: after the push c1_enc_stream_get_state, the detection history and the count of pushed
+ * frames are bit for bit what they are after the plain push of the same PCM, so plain, modes, biases and measured pushes may be
+ * mixed freely on one stream.
+ * Arguments.  Every pointer is HOST memory.  units is required; taken (frames*channels), shifts (frames*channels*52),
+ * distortion (frames*channels*2), energy (frames*channels) and weights (frames*channels*52) may each be NULL and have the shapes
+ * and meanings of the *_batch calls.  shifts without offsets is written as zeros.  mask_spread without mask_floor, weights
+ * without mask_floor and n_offsets != 0 with sf_offsets NULL are C1_ERR_ARG; the offsets and the tables are validated as in the
+ * whole-buffer calls, with the same messages; the stream's options are validated as those calls validate theirs; the mode bytes
+ * as c1_enc_stream_push_modes validates them.  What the arguments alone decide is decided before the stream is looked at.  A
+ * rejected call leaves the stream and every output as they were.  frames 0 .. 2^22 per call.  The tables are uploaded as in
+ * c1_encode_measured_masked_device, under the same stream-order contract.  "measure" in c1_ctx_kernel_ms counts the step.
+ * Which kernel measures: a launch of at most 8 192 sound units -- of this call or of the whole-buffer calls above -- takes a kernel
+ * that spends a workgroup on every unit, larger ones a wave; the outputs are the same bits.  C1_MEASURED_WIDE, read when a context
+ * is created, overrides this: 0 never the workgroup kernel, 1 always. */
+int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
+                                const uint8_t *modes /* host, frames*channels, or NULL */,
+                                const int8_t *sf_offsets /* host, n_offsets values, or NULL */, int n_offsets,
+                                const double *mask_floor /* host, 52, or NULL */, const double *mask_spread /* host, 52*52, or NULL */,
+                                uint8_t *units /* host, frames*channels*212 */, uint8_t *taken /* host, or NULL */,
+                                int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                double *energy /* host, or NULL */, double *weights /* host, or NULL */);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
