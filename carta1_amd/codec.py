@@ -370,6 +370,35 @@ class Context:
                                                         None if energy is None else energy.ctypes.data))
         return (units, taken, dist, energy) if return_distortion else (units, taken)
 
+    def measure_units(self, channels, units, masking=None, halo_frames=0, return_weights=False):
+        """The coding error of sound units that already exist against their PCM (c1_measure_units_batch): any encoder's units,
+        scored from the bytes with the yardstick of encode_measured().  channels: the PCM as for encode() (halo_frames frames of
+        real history first); units: uint8 [frames * channels, 212], unit index = frame * channels + channel, every unit's block
+        modes inside the domain of encode_modes() (ValueError naming frame, channel and field).  Returns (noise float64 [units,
+        52], signal float64 [units, 52], totals float64 [units, 2]): per BFU the W-weighted squared error of the dequantized
+        unit against the exact coefficients under the unit's own block modes and the W-weighted energy of those, and their sums
+        over the BFUs.  masking: None, or as for encode_measured() -- totals are then the sums weighted by every BFU's reciprocal
+        masking threshold, which return_weights (needs masking) appends as weights float64 [units, 52]."""
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = max(n // 512 - halo_frames, 0)
+        u = check_measured_units(units, frames, len(chans))
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
+        noise = np.zeros((frames * len(chans), 52), dtype=np.float64)
+        signal = np.zeros((frames * len(chans), 52), dtype=np.float64)
+        totals = np.zeros((frames * len(chans), 2), dtype=np.float64)
+        weights = np.zeros((frames * len(chans), 52), dtype=np.float64) if return_weights else None
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_measure_units_batch(
+            self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, u.ctypes.data,
+            None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
+            noise.ctypes.data, signal.ctypes.data, totals.ctypes.data, None if weights is None else weights.ctypes.data))
+        return (noise, signal, totals, weights) if return_weights else (noise, signal, totals)
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -464,6 +493,19 @@ class Context:
         capi.check(capi.load().c1_encode_measured_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                          C.byref(opts), vp(modes_ptr), vp(units_ptr), vp(taken_ptr),
                                                          vp(distortion_ptr), vp(energy_ptr)))
+
+    def measure_units_device(self, pcm_ptrs, frames, units_ptr, noise_ptr=None, signal_ptr=None, totals_ptr=None, weights_ptr=None,
+                             masking=None, halo_frames=0):
+        """c1_measure_units_device: units_ptr = frames * channels sound units on the device (4-byte aligned; the block modes are
+        not checked: a unit outside the domain is measured under the byte brought into it, never with an access outside the
+        buffers); outputs on the device, each may be None, not all: noise, signal and weights float64 [units, 52], totals
+        float64 [units, 2].  masking (host values, as for measure_units); weights_ptr needs it (the library's own check)."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        mask = None if masking is None else check_masking(masking, check=False)   # the library's own check decides
+        capi.check(capi.load().c1_measure_units_device(
+            self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, vp(units_ptr),
+            None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
+            vp(noise_ptr), vp(signal_ptr), vp(totals_ptr), vp(weights_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -1237,6 +1279,31 @@ def check_masking(masking, check=True):
             if bad.size:
                 raise ValueError('masking: mask_spread[%d] = %r is outside [0, 1e60]' % (bad[0], float(spread.reshape(-1)[bad[0]])))
     return floor, spread
+
+
+# ---- the coding error of given sound units (c1_measure_units_*) --------------------------------------------------------------
+def check_measured_units(units, frames, channels):
+    """the units of Context.measure_units -> contiguous uint8 [frames * channels, 212].  ValueError for another size and for the
+    first unit whose block modes (deserializeFrame's: 2, 2 and 3 minus the fields of the first six bits) are outside the
+    domain of encode_modes(), naming its frame, channel and field."""
+    u = np.ascontiguousarray(units)
+    if u.dtype != np.uint8:
+        raise ValueError('units must be uint8')
+    if u.size != frames * channels * 212:
+        raise ValueError('units must hold frames * channels = %d sound units of 212 bytes, got %d bytes' % (frames * channels, u.size))
+    u = u.reshape(-1, 212)
+    first = u[:, 0].astype(np.int64)
+    m = np.stack([2 - ((first >> 6) & 3), 2 - ((first >> 4) & 3), 3 - ((first >> 2) & 3)], axis=1)
+    ok = ((m[:, 0] == 0) | (m[:, 0] == 2)) & ((m[:, 1] == 0) | (m[:, 1] == 2)) & ((m[:, 2] == 0) | (m[:, 2] == 3))
+    bad = np.flatnonzero(~ok)
+    if bad.size:
+        i = int(bad[0])
+        where = 'frame %d, channel %d' % (i // channels, i % channels) if channels == 2 else 'frame %d' % i
+        for k, name in enumerate(_MODE_FIELDS):
+            other = 3 if k == 2 else 2
+            if int(m[i, k]) not in (0, other):
+                raise ValueError('%s: %s block mode of the unit is %d, not 0 or %d' % (where, name, int(m[i, k]), other))
+    return u
 
 
 # ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----

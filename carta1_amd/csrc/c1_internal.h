@@ -369,6 +369,14 @@ void c1k_launch_measured_wide(const C1EncodeLaunch &L, bool all_long, bool final
 // launches of at most this many units take c1k_launch_measured_wide: the largest count of DESIGN.md 6l's sweep (1 .. 8 192 units),
 // at every one of which it was the faster kernel (5 times at up to 256 units, 1.3 times at 8 192); C1_MEASURED_WIDE overrides
 constexpr int64_t kMeasuredWideUnits = 8192;
+// the coding error of given sound units (c1_k_measure_units.hip; the definition is include/carta1_hip.h's).  The mode byte of
+// each of n units (device memory, 212 bytes each, any alignment) as deserializeFrame reports its block modes, low | mid << 2 |
+// high << 4, not yet brought into the domain: c1k_launch_modes_front's input
+void c1k_launch_unit_mode_bytes(const uint8_t *units, int64_t n, uint8_t *modes, hipStream_t stream);
+// coefs: n * 512 coefficients of the exact analysis under those modes; units 4-byte aligned; mask as for
+// c1k_launch_measured_masked, or null: P_b = 1.0.  noise, signal, weights (n * 52) and totals (n * 2) may each be null
+void c1k_launch_measure_units(const C1DevTables *tables, const float *coefs, const uint8_t *units, int64_t n, const double *mask,
+                              bool has_spread, double *noise, double *signal, double *totals, double *weights, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -547,6 +547,53 @@ napi_value EncodeMeasuredMasked(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// measureUnits(ctx, [Float32Array...], haloFrames, Uint8Array units, Float64Array floor | null, Float64Array spread | null)
+// -> { noise, signal: Float64Array(frames*channels*52), totals: Float64Array(frames*channels*2), weights: Float64Array(frames*
+// channels*52), with tables only }: the coding error of given sound units against their PCM, c1_measure_units_batch
+napi_value MeasureUnits(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_bytes = 0, n_floor = 0, n_spread = 0;
+  int32_t halo = 0;
+  void *units = nullptr, *floor = nullptr, *spread = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_typed(env, argv[3], napi_uint8_array, &units, &n_bytes)) return nullptr;
+  napi_valuetype ft, st;
+  NAPI_OK(napi_typeof(env, argv[4], &ft));
+  NAPI_OK(napi_typeof(env, argv[5], &st));
+  const bool have_floor = ft != napi_null && ft != napi_undefined, have_spread = st != napi_null && st != napi_undefined;
+  if (have_floor && !get_typed(env, argv[4], napi_float64_array, &floor, &n_floor)) return nullptr;
+  if (have_spread && !get_typed(env, argv[5], napi_float64_array, &spread, &n_spread)) return nullptr;
+  if ((have_floor && n_floor != 52) || (have_spread && n_spread != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  if (n_bytes != n_units * C1_UNIT_BYTES) { napi_throw_type_error(env, nullptr, "units: 212 bytes per frame and channel"); return nullptr; }
+  const char *const names[4] = {"noise", "signal", "totals", "weights"};
+  const size_t width[4] = {52, 52, 2, 52};
+  napi_value arrays[4];
+  void *data[4] = {nullptr, nullptr, nullptr, nullptr};
+  const int n_out = have_floor ? 4 : 3;
+  for (int k = 0; k < n_out; k++) {
+    napi_value ab;
+    NAPI_OK(napi_create_arraybuffer(env, n_units * width[k] * sizeof(double), &data[k], &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * width[k], ab, 0, &arrays[k]));
+  }
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_measure_units_batch(ctx, p, (int)ch.size(), frames, halo, static_cast<const uint8_t *>(units),
+                                        have_floor ? static_cast<const double *>(floor) : nullptr,
+                                        have_spread ? static_cast<const double *>(spread) : nullptr, static_cast<double *>(data[0]),
+                                        static_cast<double *>(data[1]), static_cast<double *>(data[2]), static_cast<double *>(data[3]));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  for (int k = 0; k < n_out; k++) NAPI_OK(napi_set_named_property(env, obj, names[k], arrays[k]));
+  return obj;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1382,6 +1429,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeMeasured", nullptr, EncodeMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"measureUnits", nullptr, MeasureUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -167,3 +167,45 @@ export function encodeMeasured(channels, nativeOptions, modes = null, scaleFacto
   if (scaleFactorOffsets === null || scaleFactorOffsets === undefined) return native().encodeMeasured(ctx, channels, haloFrames, nativeOptions, modes)
   return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }
+
+// c1_measure_units_batch on the default context: the coding error of sound units that already exist -- any encoder's -- against
+// their PCM, scored from the bytes with the yardstick of encodeMeasured.  channels: one or two Float32Arrays of (haloFrames +
+// frames) * 512 samples; units: Uint8Array of frames * channels * 212 bytes (frame-major, channels interleaved), every unit's
+// block modes as the encoder writes them (low and mid 0 or 2, high 0 or 3).  options: { masking, haloFrames }; masking: null,
+// true or { floor, spread } as for encodeMeasured.  Returns { noise, signal: Float64Array(frames * channels * 52), per BFU the
+// W-weighted squared error of the dequantized unit against the exact coefficients under the unit's own block modes and the
+// W-weighted energy of those, totals: Float64Array(frames * channels * 2), their sums over the BFUs -- weighted by every BFU's
+// reciprocal masking threshold when masking is given, and the result then gains weights: Float64Array(frames * channels * 52) }.
+// Arguments that break these rules are a TypeError naming the argument, raised before any native call.
+export function checkMeasuredUnits(channels, units, haloFrames = 0) {
+  if (!Array.isArray(channels) || channels.length < 1 || channels.length > 2 || channels.some((c) => !(c instanceof Float32Array))) {
+    throw new TypeError('channels must be an array of one or two Float32Array')
+  }
+  if (!Number.isInteger(haloFrames) || haloFrames < 0 || haloFrames > 2) throw new TypeError(`haloFrames must be 0, 1 or 2, got ${haloFrames}`)
+  const samples = channels[0].length
+  if (channels.some((c) => c.length !== samples) || samples % 512 || samples / 512 < haloFrames) {
+    throw new TypeError('channels must have equal length, a multiple of 512 that covers haloFrames')
+  }
+  const count = (samples / 512 - haloFrames) * channels.length
+  if (!(units instanceof Uint8Array)) throw new TypeError('units must be a Uint8Array')
+  if (units.length !== count * 212) throw new TypeError(`units must hold frames * channels = ${count} sound units of 212 bytes, got ${units.length} bytes`)
+  for (let u = 0; u < count; u++) {
+    const first = units[212 * u]
+    const fields = [['low', 2 - ((first >> 6) & 3), 2], ['mid', 2 - ((first >> 4) & 3), 2], ['high', 3 - ((first >> 2) & 3), 3]]
+    for (const [name, mode, other] of fields) {
+      if (mode !== 0 && mode !== other) {
+        const where = channels.length === 2 ? `frame ${u >> 1}, channel ${u & 1}` : `frame ${u}`
+        throw new TypeError(`units: ${where}: ${name} block mode of the unit is ${mode}, not 0 or ${other}`)
+      }
+    }
+  }
+  return count
+}
+
+export function measureUnits(channels, units, options = {}, ctx = context()) {
+  if (options === null || typeof options !== 'object') throw new TypeError('options must be an object { masking, haloFrames }')
+  const haloFrames = options.haloFrames === undefined ? 0 : options.haloFrames
+  checkMeasuredUnits(channels, units, haloFrames)
+  const tables = options.masking === null || options.masking === undefined ? null : checkMasking(options.masking)
+  return native().measureUnits(ctx, channels, haloFrames, units, tables ? tables.floor : null, tables ? tables.spread : null)
+}

@@ -129,7 +129,7 @@ int c1_ctx_create(int device, void *hip_stream /* hipStream_t or NULL = own stre
 int c1_ctx_destroy(c1_ctx *ctx);
 int c1_ctx_synchronize(c1_ctx *ctx);
 /* milliseconds the device spent in the named kernel during the most recent *_device call on this
- * context ("analysis", "allocate", "pack", "decode", "redo", "choose", or "total"), in the most recent c1_pack_units call
+ * context ("analysis", "allocate", "pack", "decode", "redo", "choose", "measure", "meter", or "total"), in the most recent c1_pack_units call
  * ("pack_units"), or in the most recent decode from frame fields -- c1_decode_fields_*, c1_dec_stream_push_fields or a
  * unit push that follows one ("decode_fields") -- or in the from-state kernel of the most recent c1_*_frames_from_states*
  * call ("from_state") -- from HIP events on the context's stream; c1_ctx_set_profiling(ctx, 1)
@@ -499,6 +499,56 @@ int c1_encode_measured_masked_batch(c1_ctx *ctx, const float *const *pcm, int ch
                                     uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
                                     int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                     double *energy /* host, or NULL */, double *weights /* host, or NULL */);
+
+/* ---- the coding error of given sound units against their PCM -----------------------------------------------------------------
+ * The calls above report the measured error of the units they are about to pack.  This call takes sound units that already
+ * exist -- the reference's at any bias, the output of any entry point above, a file another encoder wrote, a stream after a bit
+ * error -- and scores them with the same yardstick, from the bytes.  It encodes nothing and changes no state.
+ * channels 1 or 2, unit index = frame * channels + channel; pcm and the halo as for c1_encode_modes_*.  For unit u:
+ *   Fields.  deserializeFrame (serialization.js:111-176) of units[u], exactly as c1_unpack_units reports them: nBfu from
+ *     BFU_AMOUNTS, wl 0 .. 15, sfi 0 .. 63, sign-extended mantissas, bits past the unit's end as that call reads them.
+ *   Mode byte.  low | mid << 2 | high << 4 of the unit's block_modes.  The host call rejects a unit whose byte is outside the
+ *     domain of c1_encode_modes_* (a block mode the encoder never writes): C1_ERR_ARG naming frame, channel (of two) and field,
+ *     nothing written.  The device call brings the byte into the domain as the other device entry points do (low and mid: the
+ *     byte & 2 and & 8; high 3 when bits 4-5 are both set, else 0).
+ *   Coefficients.  x are the Float32 MDCT coefficients quantizationStage receives (encoder.js:365) for that frame under the
+ *     unit's own block modes: the exact kernels', whatever the speculation mode.  They do not depend on the modes of the frames
+ *     before (see c1_encode_best_modes_*), so halo frames need no units.
+ *   Dequantized values.  d is what dequantizationStage (decoder.js:52-98) makes of the fields, c1_dequantize_frames' arithmetic:
+ *     Float32((q * SCALE_FACTORS[sfi]) / range); +0 where b >= nBfu, wl = 0 or sfi = 0.
+ *   Sums, in binary64 with no fused operation, for all 52 BFUs, with W_b and the BFU geometry of c1_encode_measured_*:
+ *     noise[52u + b]  = W_b * sum_j (x_b[j] - d_b[j])^2        signal[52u + b] = W_b * sum_j x_b[j]^2        j ascending
+ *     P_b = c1_encode_measured_masked_*'s weight with E_c = signal[52u + c] when mask_floor is given (mask_spread optional), else
+ *     exactly 1.0;  weights[52u + b] = P_b
+ *     totals[2u] = sum_b P_b * noise[52u + b]     totals[2u + 1] = sum_b P_b * signal[52u + b]     b ascending, each product
+ *     rounded before it is added.
+ * For the units c1_encode_measured_*, _sf_ and _masked_ write, totals[2u] is their distortion[2u + taken[u]], totals[2u + 1]
+ * their energy[u] and weights their weights, bit for bit, under the same tables; for the units of a plain encode totals[2u] is
+ * distortion[2u] of a measure-only call.
+ * mask_floor, mask_spread: HOST memory in both calls, validated as for c1_encode_measured_masked_* (same messages) and copied
+ * into the same buffer of the context under the same stream-order contract.  Every output may be NULL; all four NULL is
+ * C1_ERR_ARG, as are weights or mask_spread without mask_floor and a NULL units or pcm with frames to process.  A rejected call
+ * writes nothing.  No output depends on the speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP, the halo
+ * (given the same real history) or on which outputs are asked for, and the same inputs give the same bits.  Non-finite PCM gives
+ * non-finite outputs.  No byte pattern of a unit makes any access leave the buffers: every index read from a unit is a masked
+ * bit field.
+ * device-resident: pcm[c] (16-byte aligned), units (4-byte aligned) and the outputs are DEVICE pointers; limits on frames,
+ * chunking, asynchrony and the caller's-stream contract are c1_encode_measured_device's.  Per chunk the units' mode bytes are
+ * formed into workspace, the exact analysis under given modes runs as far as the coefficients (no allocation, no packing), then
+ * one kernel reads bytes and coefficients back.  c1_ctx_kernel_ms counts that kernel under "meter" and the analysis under
+ * "analysis". */
+int c1_measure_units_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                            const uint8_t *units /* device, frames*channels*212 */,
+                            const double *mask_floor /* HOST, 52, or NULL: P_b = 1 */, const double *mask_spread /* HOST, 52*52, or NULL */,
+                            double *noise /* device, frames*channels*52, or NULL */, double *signal /* device, frames*channels*52, or NULL */,
+                            double *totals /* device, frames*channels*2, or NULL */, double *weights /* device, frames*channels*52, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The tables, the outputs and every unit's mode byte are validated before the
+ * context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a device the
+ * call then returns C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per channel. */
+int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                           const uint8_t *units /* host */, const double *mask_floor /* host, or NULL */,
+                           const double *mask_spread /* host, or NULL */, double *noise /* host, or NULL */,
+                           double *signal /* host, or NULL */, double *totals /* host, or NULL */, double *weights /* host, or NULL */);
 
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
