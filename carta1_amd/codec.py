@@ -399,6 +399,37 @@ class Context:
             noise.ctypes.data, signal.ctypes.data, totals.ctypes.data, None if weights is None else weights.ctypes.data))
         return (noise, signal, totals, weights) if return_weights else (noise, signal, totals)
 
+    def measure_pcm(self, channels, units, halo_frames=0, halo_units=0):
+        """The error of the decoded PCM of sound units against the PCM they were made from (c1_measure_pcm_batch), per unit and
+        per 32-sample segment.  channels: the PCM as for encode() (halo_frames frames of real history first); units: uint8
+        [(halo_units + frames) * channels, 212], unit index = frame * channels + channel, the unit(s) of frame -1 first when
+        halo_units is 1 (the decoder starts from a fresh pool otherwise).  Returns (noise float64 [units, 16], signal float64
+        [units, 16], totals float64 [units, 2]): with y the exact decode of the units and x the input PCM_DELAY = 266 samples
+        earlier (zero before the history given), noise[u, s] = sum (y - x)^2 and signal[u, s] = sum x^2 over the samples 32 s ..
+        32 s + 31 of the unit's frame, and totals[u] their sums over the segments."""
+        chans = [np.ascontiguousarray(c) for c in channels]
+        if len(chans) not in (1, 2):
+            raise ValueError('channels must be 1 or 2 arrays')
+        if any(c.dtype != np.float32 or c.ndim != 1 for c in chans):
+            raise ValueError('channels must be one-dimensional float32 arrays')
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        if halo_frames not in (0, 1, 2) or n // 512 < halo_frames:
+            raise ValueError('halo_frames must be 0, 1 or 2 frames of the PCM given')
+        if halo_units not in (0, 1):
+            raise ValueError('halo_units must be 0 or 1')
+        frames = n // 512 - halo_frames
+        u = check_pcm_units(units, frames + halo_units, len(chans))
+        noise = np.zeros((frames * len(chans), PCM_SEGMENTS), dtype=np.float64)
+        signal = np.zeros((frames * len(chans), PCM_SEGMENTS), dtype=np.float64)
+        totals = np.zeros((frames * len(chans), 2), dtype=np.float64)
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_measure_pcm_batch(self._h, ptrs, len(chans), frames, halo_frames,
+                                                    u.ctypes.data + halo_units * len(chans) * 212, halo_units,
+                                                    noise.ctypes.data, signal.ctypes.data, totals.ctypes.data))
+        return noise, signal, totals
+
     def decode(self, units, channels, halo_units=0, out=None):
         """units: uint8 [(halo_units + frames) * channels, 212].  Returns a list of float32 arrays (`out`: optional
         preallocated list of them, see encode())."""
@@ -506,6 +537,16 @@ class Context:
             self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, vp(units_ptr),
             None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
             vp(noise_ptr), vp(signal_ptr), vp(totals_ptr), vp(weights_ptr)))
+
+    def measure_pcm_device(self, pcm_ptrs, frames, units_ptr, noise_ptr=None, signal_ptr=None, totals_ptr=None, halo_frames=0,
+                           halo_units=0):
+        """c1_measure_pcm_device: pcm_ptrs = frame 0 of every channel on the device (16-byte aligned, halo_frames frames of
+        real PCM before it), units_ptr = unit 0 of frames * channels sound units on the device (4-byte aligned, the unit(s) of
+        frame -1 before it when halo_units is 1); outputs on the device, each may be None, not all: noise and signal float64
+        [units, 16], totals float64 [units, 2]."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        capi.check(capi.load().c1_measure_pcm_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
+                                                     vp(units_ptr), halo_units, vp(noise_ptr), vp(signal_ptr), vp(totals_ptr)))
 
     def decode_device(self, units_ptr, channels, frames, pcm_ptrs, halo_units=0):
         capi.check(capi.load().c1_decode_device(self._h, C.c_void_p(units_ptr), channels, frames, halo_units,
@@ -1304,6 +1345,23 @@ def check_measured_units(units, frames, channels):
             if int(m[i, k]) not in (0, other):
                 raise ValueError('%s: %s block mode of the unit is %d, not 0 or %d' % (where, name, int(m[i, k]), other))
     return u
+
+
+# ---- the decoded PCM error of given sound units (c1_measure_pcm_*) ----------------------------------------------------------
+PCM_DELAY = 266       # samples between a sample going into encode() and coming out of decode()
+PCM_SEGMENTS = 16     # 32-sample segments of a frame
+
+
+def check_pcm_units(units, count, channels):
+    """the units of Context.measure_pcm -> contiguous uint8 [count * channels, 212]; ValueError for another dtype or size.  Any
+    bytes are units to the decoder: nothing else is checked."""
+    u = np.ascontiguousarray(units)
+    if u.dtype != np.uint8:
+        raise ValueError('units must be uint8')
+    if u.size != count * channels * 212:
+        raise ValueError('units must hold (halo_units + frames) * channels = %d sound units of 212 bytes, got %d bytes'
+                         % (count * channels, u.size))
+    return u.reshape(-1, 212)
 
 
 # ---- the allocation bias per sound unit: a palette of option sets and one index byte per unit (c1_encode_biases_*) -----

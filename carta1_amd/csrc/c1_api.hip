@@ -411,8 +411,8 @@ struct Timing {
   hipEvent_t start, stop;
   int kind;
 };
-enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_CHOOSE, K_MEASURE, K_METER, K_KINDS };
-const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts", "choose", "measure", "meter"};
+enum { K_ANALYSIS = 0, K_ALLOCATE, K_PACK, K_DECODE, K_REDO, K_PACK_UNITS, K_DECODE_FIELDS, K_FROM_STATE, K_SIGNAL_STARTS, K_CHOOSE, K_MEASURE, K_METER, K_METER_PCM, K_KINDS };
+const char *const kKindNames[K_KINDS] = {"analysis", "allocate", "pack", "decode", "redo", "pack_units", "decode_fields", "from_state", "signal_starts", "choose", "measure", "meter", "meter_pcm"};
 
 }  // namespace
 
@@ -3079,6 +3079,104 @@ int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
   if (totals) HIP_TRY(hipMemcpyAsync(totals, d_totals, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (weights) HIP_TRY(hipMemcpyAsync(weights, d_weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+// ---- the decoded PCM error of given sound units (c1_measure_pcm_*) ----------------------------------------------------------
+// what the arguments of both calls decide alone, before a context is looked at
+static int check_measure_pcm_args(const char *what, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                  const uint8_t *units, int halo_units, const double *noise, const double *signal, const double *totals) {
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "%s: frames must be 0 .. 2^22, got %lld", what, (long long)frames);
+  if (halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "%s: halo_frames must be 0 .. 2, got %d", what, halo_frames);
+  if (halo_units < 0 || halo_units > 1) return fail(C1_ERR_ARG, "%s: halo_units must be 0 or 1, got %d", what, halo_units);
+  if (!noise && !signal && !totals) return fail(C1_ERR_ARG, "%s: noise, signal and totals are all NULL", what);
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "%s: pcm is NULL", what);
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "%s: pcm[%d] is NULL", what, c);
+    if (!units) return fail(C1_ERR_ARG, "%s: units is NULL", what);
+  }
+  return C1_OK;
+}
+
+int c1_measure_pcm_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames, const uint8_t *units,
+                          int halo_units, double *noise, double *signal, double *totals) {
+  const char *const what = "c1_measure_pcm_device";
+  int rc = check_measure_pcm_args(what, pcm, channels, frames, halo_frames, units, halo_units, noise, signal, totals);
+  if (rc) return rc;
+  for (int c = 0; c < channels && frames > 0; c++)
+    if ((uintptr_t)pcm[c] & 15) return fail(C1_ERR_ARG, "%s: pcm[%d] must be 16-byte aligned on the device", what, c);
+  if ((uintptr_t)units & 3) return fail(C1_ERR_ARG, "%s: units must be 4-byte aligned on the device", what);
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if (frames == 0) return C1_OK;
+  C1MeasurePcmLaunch L;
+  memset(&L, 0, sizeof L);
+  L.units = units;
+  L.channels = channels;
+  L.frames = frames;
+  L.halo_units = halo_units;
+  L.halo_frames = halo_frames;
+  L.tables = ctx->d_tables;
+  for (int c = 0; c < channels; c++) L.pcm[c] = pcm[c];
+  L.noise = noise;
+  L.signal = signal;
+  L.totals = totals;
+  { ScopedTiming t(ctx, K_METER_PCM); c1k_launch_measure_pcm(L, ctx->stream); }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
+int c1_measure_pcm_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames, const uint8_t *units,
+                         int halo_units, double *noise, double *signal, double *totals) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_measure_pcm_batch";
+  int rc = check_measure_pcm_args(what, pcm, channels, frames, halo_frames, units, halo_units, noise, signal, totals);
+  if (rc) return rc;
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // Chunks of the context's chunk length (C1_CHUNK_FRAMES), each with its halos from the batch itself: one frame of PCM covers
+  // the 266 samples of history, one unit rebuilds the decoder's state.  Per chunk one copy in, the device call, one copy out per
+  // output; the kernel's time adds up over the chunks
+  const int64_t chunk = std::max<int64_t>(1, std::min(ctx->chunk_frames, kMaxModesBatchFrames));
+  const int64_t cf = std::min(frames, chunk);
+  const size_t ch_bytes = (size_t)(cf + 2) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), noise_off = up256(unit_off + (size_t)(cf + 1) * channels * C1_UNIT_BYTES),
+               signal_off = up256(noise_off + (size_t)cf * channels * 16 * sizeof(double)),
+               totals_off = up256(signal_off + (size_t)cf * channels * 16 * sizeof(double));
+  if ((rc = ensure_io(ctx, totals_off + (size_t)cf * channels * 2 * sizeof(double)))) return rc;
+  StreamDrain drain(ctx);
+  double *d_noise = reinterpret_cast<double *>((char *)ctx->d_io + noise_off), *d_signal = reinterpret_cast<double *>((char *)ctx->d_io + signal_off),
+         *d_totals = reinterpret_cast<double *>((char *)ctx->d_io + totals_off);
+  for (int64_t f0 = 0, n = 0; f0 < frames; f0 += n) {
+    n = std::min(chunk, frames - f0);
+    const int hf = f0 > 0 ? 1 : halo_frames, hu = f0 > 0 ? 1 : halo_units;
+    const size_t n_units = (size_t)n * channels, at = (size_t)f0 * channels;
+    const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+    for (int c = 0; c < channels; c++) {
+      float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+      HIP_TRY(hipMemcpyAsync(d, pcm[c] + (f0 - hf) * 512, (size_t)(n + hf) * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      dptr[c] = d + (size_t)hf * 512;
+    }
+    const size_t halo_bytes = (size_t)hu * channels * C1_UNIT_BYTES;   // a multiple of 4
+    uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off;
+    HIP_TRY(hipMemcpyAsync(d_units, units + at * C1_UNIT_BYTES - halo_bytes, n_units * C1_UNIT_BYTES + halo_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = c1_measure_pcm_device(ctx, dptr, channels, n, hf, d_units + halo_bytes, hu, noise ? d_noise : nullptr, signal ? d_signal : nullptr,
+                                    totals ? d_totals : nullptr))) return rc;
+    if (noise) HIP_TRY(hipMemcpyAsync(noise + at * 16, d_noise, n_units * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (signal) HIP_TRY(hipMemcpyAsync(signal + at * 16, d_signal, n_units * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (totals) HIP_TRY(hipMemcpyAsync(totals + at * 2, d_totals, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
   return C1_OK;
 }
 

@@ -155,6 +155,20 @@ struct C1DecodeLaunch {
   int run_frames;        // consecutive units of one channel a wave decodes (set by the launcher)
 };
 
+// c1_measure_pcm_device: the decoder's inputs, the PCM the units were made from (halo_frames whole frames in front of the
+// pointers) and the three outputs (each may be null)
+struct C1MeasurePcmLaunch {
+  const uint8_t *units;
+  int channels;
+  int64_t frames;
+  int halo_units;
+  int halo_frames;
+  const C1DevTables *tables;
+  const float *pcm[C1_MAX_CHANNELS];
+  double *noise, *signal, *totals;   // frames*channels*16, frames*channels*16, frames*channels*2
+  int run_frames;        // consecutive units of one channel a wave decodes (set by the launcher)
+};
+
 // frame fields in the layout c1_unpack_units writes: unit u at nbfu[u], modes[3u], sfi[52u], wl[52u], q[512u] (q 16-byte aligned)
 struct C1FieldPtrs {
   const int32_t *nbfu, *modes, *sfi, *wl, *q;
@@ -377,6 +391,9 @@ void c1k_launch_unit_mode_bytes(const uint8_t *units, int64_t n, uint8_t *modes,
 // c1k_launch_measured_masked, or null: P_b = 1.0.  noise, signal, weights (n * 52) and totals (n * 2) may each be null
 void c1k_launch_measure_units(const C1DevTables *tables, const float *coefs, const uint8_t *units, int64_t n, const double *mask,
                               bool has_spread, double *noise, double *signal, double *totals, double *weights, hipStream_t stream);
+// the error of the decoded PCM of given sound units against the delayed input (c1_k_measure_pcm.hip; the definition is
+// include/carta1_hip.h's): k_decode<double>'s walk over the units, the comparison in place of the PCM stores
+void c1k_launch_measure_pcm(const C1MeasurePcmLaunch &L, hipStream_t stream);
 void c1k_launch_pack(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // all_long: every unit has modes [0,0,0]
 void c1k_launch_pack_spec(const C1EncodeLaunch &L, bool all_long, hipStream_t stream);   // binary32 quantization with the guard band; fills the redo list
 // running totals (c1_ctx::d_spec_totals) and their page-locked mirror; kind 0 speculative call (counts = list head), 1 binary32

@@ -594,6 +594,45 @@ napi_value MeasureUnits(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// measurePcm(ctx, [Float32Array...], haloFrames, Uint8Array units, haloUnits) -> { noise, signal: Float64Array(frames*channels*16),
+// totals: Float64Array(frames*channels*2) }: the error of the decoded PCM of given sound units against their PCM, per 32 samples,
+// c1_measure_pcm_batch.  units holds the haloUnits unit(s) of frame -1 first
+napi_value MeasurePcm(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_bytes = 0;
+  int32_t halo = 0, halo_units = 0;
+  void *units = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_typed(env, argv[3], napi_uint8_array, &units, &n_bytes)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[4], &halo_units));
+  if (halo < 0 || halo > 2 || halo_units < 0 || halo_units > 1) { napi_throw_type_error(env, nullptr, "haloFrames must be 0 .. 2 and haloUnits 0 or 1"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size(), halo_bytes = (size_t)halo_units * ch.size() * C1_UNIT_BYTES;
+  if (n_bytes != n_units * C1_UNIT_BYTES + halo_bytes) { napi_throw_type_error(env, nullptr, "units: 212 bytes per frame and channel, the halo unit(s) first"); return nullptr; }
+  const char *const names[3] = {"noise", "signal", "totals"};
+  const size_t width[3] = {16, 16, 2};
+  napi_value arrays[3];
+  void *data[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; k++) {
+    napi_value ab;
+    NAPI_OK(napi_create_arraybuffer(env, n_units * width[k] * sizeof(double), &data[k], &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * width[k], ab, 0, &arrays[k]));
+  }
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_measure_pcm_batch(ctx, p, (int)ch.size(), frames, halo, static_cast<const uint8_t *>(units) + halo_bytes, halo_units,
+                                      static_cast<double *>(data[0]), static_cast<double *>(data[1]), static_cast<double *>(data[2]));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  for (int k = 0; k < 3; k++) NAPI_OK(napi_set_named_property(env, obj, names[k], arrays[k]));
+  return obj;
+}
+
 // decodeBatch(ctx, Uint8Array units, channels, haloUnits) -> [Float32Array...]
 napi_value DecodeBatch(napi_env env, napi_callback_info info) {
   napi_value argv[4];
@@ -1430,6 +1469,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measureUnits", nullptr, MeasureUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"measurePcm", nullptr, MeasurePcm, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeWav16Batch", nullptr, DecodeWav16Batch, nullptr, nullptr, nullptr, napi_default, nullptr},

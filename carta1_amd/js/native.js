@@ -209,3 +209,33 @@ export function measureUnits(channels, units, options = {}, ctx = context()) {
   const tables = options.masking === null || options.masking === undefined ? null : checkMasking(options.masking)
   return native().measureUnits(ctx, channels, haloFrames, units, tables ? tables.floor : null, tables ? tables.spread : null)
 }
+
+// c1_measure_pcm_batch on the default context: the error of the decoded PCM of sound units against the PCM they were made from,
+// per unit and per 32-sample segment.  channels: one or two Float32Arrays of (haloFrames + frames) * 512 samples; units:
+// Uint8Array of (haloUnits + frames) * channels * 212 bytes (frame-major, channels interleaved), the unit(s) of frame -1 first
+// when haloUnits is 1 (the decoder starts from a fresh pool otherwise); any bytes are units to the decoder.  options:
+// { haloFrames: 0 .. 2, haloUnits: 0 or 1 }.  With y the exact decode of the units and x the input PCM_DELAY = 266 samples
+// earlier (zero before the history given), returns { noise, signal: Float64Array(frames * channels * 16), the sums of (y - x)^2
+// and of x^2 over the samples 32 s .. 32 s + 31 of every unit's frame, totals: Float64Array(frames * channels * 2), their sums
+// over the sixteen segments }.  Arguments that break these rules are a TypeError naming the argument, raised before any native call.
+export const PCM_DELAY = 266
+export function measurePcm(channels, units, options = {}, ctx = context()) {
+  if (options === null || typeof options !== 'object') throw new TypeError('options must be an object { haloFrames, haloUnits }')
+  const haloFrames = options.haloFrames === undefined ? 0 : options.haloFrames
+  const haloUnits = options.haloUnits === undefined ? 0 : options.haloUnits
+  if (!Array.isArray(channels) || channels.length < 1 || channels.length > 2 || channels.some((c) => !(c instanceof Float32Array))) {
+    throw new TypeError('channels must be an array of one or two Float32Array')
+  }
+  if (!Number.isInteger(haloFrames) || haloFrames < 0 || haloFrames > 2) throw new TypeError(`haloFrames must be 0, 1 or 2, got ${haloFrames}`)
+  if (haloUnits !== 0 && haloUnits !== 1) throw new TypeError(`haloUnits must be 0 or 1, got ${haloUnits}`)
+  const samples = channels[0].length
+  if (channels.some((c) => c.length !== samples) || samples % 512 || samples / 512 < haloFrames) {
+    throw new TypeError('channels must have equal length, a multiple of 512 that covers haloFrames')
+  }
+  const count = (samples / 512 - haloFrames + haloUnits) * channels.length
+  if (!(units instanceof Uint8Array)) throw new TypeError('units must be a Uint8Array')
+  if (units.length !== count * 212) {
+    throw new TypeError(`units must hold (haloUnits + frames) * channels = ${count} sound units of 212 bytes, got ${units.length} bytes`)
+  }
+  return native().measurePcm(ctx, channels, haloFrames, units, haloUnits)
+}

@@ -550,6 +550,47 @@ int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
                            const double *mask_spread /* host, or NULL */, double *noise /* host, or NULL */,
                            double *signal /* host, or NULL */, double *totals /* host, or NULL */, double *weights /* host, or NULL */);
 
+/* ---- the error of the decoded PCM of given sound units against their PCM, per 32 samples ---------------------------------------
+ * c1_measure_units_* compares coefficients; this call compares what a listener gets: it decodes the units exactly as
+ * c1_decode_device does and reports how far the decoded PCM is from the PCM that went in, per unit and per 32-sample segment, in
+ * one launch.  No decoded PCM is written anywhere; it encodes nothing and changes no state.
+ *   Geometry.  channels 1 or 2, unit index u = frame * channels + channel.
+ *   PCM and its halo.  pcm[c] is planar Float32; halo_frames (0 .. 2) whole frames of real PCM sit in front of the pointers, as
+ *     for c1_encode_modes_*; samples before that are zero.  Only the last 266 samples of history are ever read.
+ *   Unit halo.  halo_units (0 or 1): the unit(s) of frame -1 precede `units`, as for c1_decode_device; otherwise the decoder
+ *     starts from a fresh pool.
+ *   Decoded PCM.  y[c][t], t = 0 .. 512 * frames - 1, is the Float32 PCM c1_decode_device writes for these units, channels,
+ *     frames and halo_units, bit for bit: the exact (binary64) decoder whatever c1_ctx_set_decode_precision says.
+ *   Delayed input.  x[c][t] = pcm[c][t - 266] (the codec delay); zero where t - 266 < -512 * halo_frames.
+ *   Sums, in binary64 with no fused operation.  For unit u (frame f, channel c) and segment s = 0 .. 15, t = 512 f + 32 s + i,
+ *     i ascending over 0 .. 31:   e = (double)y - (double)x
+ *     noise[16u + s] = sum_i e * e          signal[16u + s] = sum_i x * x
+ *     each square rounded before it is added, each sum starting from +0;
+ *     totals[2u] = sum_s noise[16u + s]     totals[2u + 1] = sum_s signal[16u + s]     s ascending.
+ *     Segment s of frame f covers the input samples 512 f + 32 s - 266 .. 512 f + 32 s - 266 + 31.
+ * Any of noise, signal, totals may be NULL; all three NULL is C1_ERR_ARG, as are a NULL units or pcm with frames to process and
+ * channels, frames, halo_frames or halo_units out of range.  These are decided before the context is looked at, and a rejected
+ * call writes nothing.  frames == 0 is success with nothing written.
+ * No output depends on the run length, chunking, the halos (given the same real history), the decode-precision setting or on
+ * which outputs are asked for, and the same inputs give the same bits.  Non-finite PCM gives non-finite noise and signal in the
+ * segments it falls in (and the unit's totals), and nowhere else.  No byte pattern of a unit makes any access leave the buffers
+ * (c1_decode_device's property).  No PCM read lies before pcm[c] - 512 * halo_frames or at or after pcm[c] + 512 * frames - 266.
+ * device-resident: pcm[c] (16-byte aligned), units (4-byte aligned) and the outputs are DEVICE pointers; asynchronous on the
+ * context's stream under c1_decode_device's caller's-stream contract; frames 0 .. 2^22 per channel; no workspace and so no
+ * chunking.  c1_ctx_kernel_ms counts the kernel under "meter_pcm". */
+int c1_measure_pcm_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                          const uint8_t *units /* device, frames*channels*212 */, int halo_units,
+                          double *noise /* device, frames*channels*16, or NULL */, double *signal /* device, frames*channels*16, or NULL */,
+                          double *totals /* device, frames*channels*2, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The arguments are validated before the context is looked at or any device
+ * work is done (C1_ERR_ARG, nothing written); without a context and without a device the call then returns C1_ERR_NO_DEVICE.
+ * One copy in, the device call, one copy out per output; batches longer than the context's chunk length (C1_CHUNK_FRAMES) go in
+ * chunks, each with its halos taken from the batch itself, and the result equals the unchunked one bit for bit.  frames
+ * 0 .. 2^22 per channel. */
+int c1_measure_pcm_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                         const uint8_t *units /* host */, int halo_units, double *noise /* host, or NULL */,
+                         double *signal /* host, or NULL */, double *totals /* host, or NULL */);
+
 /* The same batch sharded over several devices of this host (the hot loop of processor.js:119-136 has no
  * dependency between frames beyond a bounded PCM history): contiguous frame ranges, one per entry of `devices`, each
  * encoded by its own host thread on a context of that device from its 2 frames of real PCM history; no collective, the
