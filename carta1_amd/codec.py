@@ -370,6 +370,43 @@ class Context:
                                                         None if energy is None else energy.ctypes.data))
         return (units, taken, dist, energy) if return_distortion else (units, taken)
 
+    def encode_measured_modes(self, channels, candidates, options=None, halo_frames=0, scale_factor_offsets=None,
+                              return_distortion=False, return_shifts=False):
+        """encode_measured() with the block modes of every sound unit chosen among `candidates` by the final error of the measured
+        allocation under each (c1_encode_measured_modes_batch; opt-in like encode_measured()).  candidates: as for
+        encode_best_modes(); scale_factor_offsets: as for encode_measured(), None for the plain measured allocation (offsets
+        (0,)).  Per (unit, candidate) the figures are those of encode_measured(modes=constant byte, ...); the candidate of least
+        T_final = taken ? T(n*) : T_ref wins, the first on a tie.  Of `options` only the allocation bias (or biased table) is used.
+        Returns (units, choice uint8 [units], modes uint8 [units], taken uint8 [units]), then with return_shifts shifts int8
+        [units, 52] (the winner's), then with return_distortion distortion float64 [units, n, 2] (T_ref, T(n*)) and energy
+        float64 [units, n]; units are what encode_measured(modes=modes, ...) gives.  The dearest encode of the library: one
+        greedy allocation per unit and candidate."""
+        opts = (options or EncoderOptions()).to_c()
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = max(n // 512 - halo_frames, 0)
+        cand = mode_candidates(candidates)
+        count = len(cand)
+        offs = check_scale_factor_offsets((0,) if scale_factor_offsets is None else scale_factor_offsets)
+        total = frames * len(chans)
+        units = np.zeros((total, 212), dtype=np.uint8)
+        choice = np.zeros(total, dtype=np.uint8)
+        modes = np.zeros(total, dtype=np.uint8)
+        taken = np.zeros(total, dtype=np.uint8)
+        shifts = np.zeros((total, 52), dtype=np.int8) if return_shifts else None
+        dist = np.zeros((total, count, 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros((total, count), dtype=np.float64) if return_distortion else None
+        ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        capi.check(capi.load().c1_encode_measured_modes_batch(
+            self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts), cand.ctypes.data, count, offs.ctypes.data,
+            len(offs), units.ctypes.data, choice.ctypes.data, modes.ctypes.data, taken.ctypes.data,
+            None if shifts is None else shifts.ctypes.data, None if dist is None else dist.ctypes.data,
+            None if energy is None else energy.ctypes.data))
+        out = (units, choice, modes, taken) + ((shifts,) if return_shifts else ())
+        return out + (dist, energy) if return_distortion else out
+
     def measure_units(self, channels, units, masking=None, halo_frames=0, return_weights=False):
         """The coding error of sound units that already exist against their PCM (c1_measure_units_batch): any encoder's units,
         scored from the bytes with the yardstick of encode_measured().  channels: the PCM as for encode() (halo_frames frames of
@@ -490,6 +527,22 @@ class Context:
         capi.check(capi.load().c1_encode_best_modes_device(self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames,
                                                            C.byref(opts), cand.ctypes.data, len(cand), vp(units_ptr), vp(choice_ptr),
                                                            vp(modes_ptr), vp(distortion_ptr), vp(energy_ptr)))
+
+    def encode_measured_modes_device(self, pcm_ptrs, frames, candidates, units_ptr=None, choice_ptr=None, modes_ptr=None, taken_ptr=None,
+                                     shifts_ptr=None, distortion_ptr=None, energy_ptr=None, options=None, halo_frames=0,
+                                     scale_factor_offsets=None):
+        """c1_encode_measured_modes_device: candidates as for encode_best_modes_device and scale_factor_offsets as for
+        encode_measured_device (host values; checked by the library: C1_ERR_ARG), None for offsets (0,); outputs on the device,
+        each may be None (units_ptr None: measure only), not all; choice, modes and taken are uint8 [units], shifts int8 [units,
+        52], distortion float64 [units, n, 2] and energy float64 [units, n]."""
+        opts = (options or EncoderOptions()).to_c()
+        cand = mode_candidates(candidates, check=False)
+        offs = check_scale_factor_offsets((0,) if scale_factor_offsets is None else scale_factor_offsets, check=False)
+        vp = lambda p: C.c_void_p(p) if p else None
+        capi.check(capi.load().c1_encode_measured_modes_device(
+            self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, C.byref(opts), cand.ctypes.data if len(cand) else None,
+            len(cand), offs.ctypes.data if len(offs) else None, len(offs), vp(units_ptr), vp(choice_ptr), vp(modes_ptr), vp(taken_ptr),
+            vp(shifts_ptr), vp(distortion_ptr), vp(energy_ptr)))
 
     def encode_measured_device(self, pcm_ptrs, frames, units_ptr=None, taken_ptr=None, distortion_ptr=None, energy_ptr=None,
                                modes_ptr=None, options=None, halo_frames=0, scale_factor_offsets=None, shifts_ptr=None, masking=None,

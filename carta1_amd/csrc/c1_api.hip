@@ -796,6 +796,13 @@ struct BestModesCall {
   const uint8_t *cand;
   uint8_t *choice, *modes_out;
   double *distortion, *energy;
+  // c1_encode_measured_modes_device: the candidates are judged by the measured allocation's final error (k_measured_modes in
+  // k_choose_modes' place); the offsets (host memory, validated) and the winner's outputs.  distortion then holds two values per
+  // (unit, candidate)
+  const int8_t *sf_offsets = nullptr;
+  int n_offsets = 0;
+  uint8_t *taken = nullptr;
+  int8_t *shifts = nullptr;
 };
 
 // One call of c1_encode_best_bias_device: the palette's size and the call's outputs (device memory, each may be null)
@@ -974,7 +981,8 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
   // bm (c1_encode_best_modes_device): the front end of given_modes under a constant byte, at most twice (all long into the
   // chunk's workspace, all short into planes of its own); per candidate its side record composed from the two and the allocation
   // run over all units into the candidate's trial records; k_choose_modes measures every (unit, candidate) and leaves the
-  // winner's coefficients, side record and allocation where packing reads them.  One workspace half: not pipelined
+  // winner's coefficients, side record and allocation where packing reads them.  One workspace half: not pipelined.  With
+  // offsets (c1_encode_measured_modes_device) k_measured_modes stands in k_choose_modes' place, on the same workspace
   if (bm && (rc = ensure_trial_allocs(ctx, std::min(frames, chunk) * channels, bm->n))) return rc;
   if (bm && (rc = ensure_best_modes_planes(ctx, std::min(frames, chunk) * channels))) return rc;
   bool bm_long = false, bm_short = false;                     // some candidate codes a band long / short
@@ -1166,11 +1174,21 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
         A.alloc = ctx->d_trial + (size_t)k * trial_stride;
         c1k_launch_allocate(A, sB);
       }
-      ScopedTiming t(ctx, K_CHOOSE, sB);
-      c1k_launch_choose_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, L.units != nullptr,
-                              bm->choice ? bm->choice + f0 * channels : nullptr, bm->modes_out ? bm->modes_out + f0 * channels : nullptr,
-                              bm->distortion ? bm->distortion + f0 * channels * bm->n : nullptr,
-                              bm->energy ? bm->energy + f0 * channels * bm->n : nullptr, sB);
+      if (bm->sf_offsets) {
+        ScopedTiming t(ctx, K_MEASURE, sB);
+        c1k_launch_measured_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, bm->sf_offsets, bm->n_offsets,
+                                  L.units != nullptr, bm->choice ? bm->choice + f0 * channels : nullptr,
+                                  bm->modes_out ? bm->modes_out + f0 * channels : nullptr, bm->taken ? bm->taken + f0 * channels : nullptr,
+                                  bm->shifts ? bm->shifts + f0 * channels * 52 : nullptr,
+                                  bm->distortion ? bm->distortion + f0 * channels * bm->n * 2 : nullptr,
+                                  bm->energy ? bm->energy + f0 * channels * bm->n : nullptr, sB);
+      } else {
+        ScopedTiming t(ctx, K_CHOOSE, sB);
+        c1k_launch_choose_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, L.units != nullptr,
+                                bm->choice ? bm->choice + f0 * channels : nullptr, bm->modes_out ? bm->modes_out + f0 * channels : nullptr,
+                                bm->distortion ? bm->distortion + f0 * channels * bm->n : nullptr,
+                                bm->energy ? bm->energy + f0 * channels * bm->n : nullptr, sB);
+      }
     } else if (best) {
       const int64_t trial_stride = ctx->trial_units * kAllocBytes;
       {
@@ -3276,6 +3294,97 @@ int c1_encode_best_modes_batch(c1_ctx *ctx, const float *const *pcm, int channel
   if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
   if (modes_out) HIP_TRY(hipMemcpyAsync(modes_out, d_modes, n_units, hipMemcpyDeviceToHost, ctx->stream));
   if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+int c1_encode_measured_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                    const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                    int n_offsets, uint8_t *units, uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts,
+                                    double *distortion, double *energy) {
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_modes_device", opts, false))) return rc;
+  if ((rc = check_mode_candidates("c1_encode_measured_modes_device", cand_modes, n_cand))) return rc;
+  if ((rc = check_sf_offsets("c1_encode_measured_modes_device", sf_offsets, n_offsets))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy)
+    return fail(C1_ERR_ARG, "c1_encode_measured_modes_device: units, choice, modes_out, taken, shifts, distortion and energy are all NULL");
+  c1_encode_options base = *opts;                              // the modes are the candidates': neither threshold nor fixed modes are read
+  base.transient_threshold = 1.0;
+  base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  BestModesCall mc = {n_cand, nullptr, choice, modes_out, distortion, energy};
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's arrays may change once the call has returned
+  int8_t offs[C1_MAX_SF_OFFSETS];
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  memcpy(offs, sf_offsets, (size_t)n_offsets);
+  mc.cand = cand;
+  mc.sf_offsets = offs;
+  mc.n_offsets = n_offsets;
+  mc.taken = taken;
+  mc.shifts = shifts;
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            nullptr, nullptr, nullptr, &mc);
+}
+
+int c1_encode_measured_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                   const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                   int n_offsets, uint8_t *units, uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts,
+                                   double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts("c1_encode_measured_modes_batch", opts, false))) return rc;
+  if ((rc = check_mode_candidates("c1_encode_measured_modes_batch", cand_modes, n_cand))) return rc;
+  if ((rc = check_sf_offsets("c1_encode_measured_modes_batch", sf_offsets, n_offsets))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy)
+    return fail(C1_ERR_ARG, "c1_encode_measured_modes_batch: units, choice, modes_out, taken, shifts, distortion and energy are all NULL");
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "c1_encode_measured_modes_batch: no HIP device available; this library has no CPU path"); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), choice_off = up256(unit_off + n_units * C1_UNIT_BYTES), modes_off = up256(choice_off + n_units),
+               taken_off = up256(modes_off + n_units), shift_off = up256(taken_off + n_units), dist_off = up256(shift_off + n_units * 52),
+               energy_off = up256(dist_off + n_units * n_cand * 2 * sizeof(double));
+  if ((rc = ensure_io(ctx, energy_off + n_units * n_cand * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_choice = (uint8_t *)ctx->d_io + choice_off, *d_modes = (uint8_t *)ctx->d_io + modes_off,
+          *d_taken = (uint8_t *)ctx->d_io + taken_off;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>((char *)ctx->d_io + shift_off);
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off);
+  if ((rc = c1_encode_measured_modes_device(ctx, dptr, channels, frames, halo_frames, opts, cand_modes, n_cand, sf_offsets, n_offsets,
+                                            units ? d_units : nullptr, choice ? d_choice : nullptr, modes_out ? d_modes : nullptr,
+                                            taken ? d_taken : nullptr, shifts ? d_shifts : nullptr, distortion ? d_dist : nullptr,
+                                            energy ? d_energy : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (modes_out) HIP_TRY(hipMemcpyAsync(modes_out, d_modes, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (shifts) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_cand * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;

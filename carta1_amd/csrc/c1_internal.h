@@ -352,6 +352,16 @@ void c1k_launch_compose_side(const uint8_t *side_long, const uint8_t *side_short
 void c1k_launch_choose_modes(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
                              int64_t trial_stride, const uint8_t *cand, int n_cand, bool finalize, uint8_t *choice, uint8_t *modes_out,
                              double *distortion, double *energy, hipStream_t stream);
+// the block modes chosen per unit by the error of the measured allocation (c1_k_measured_modes.hip; the definition is
+// include/carta1_hip.h's).  The planes, the trial records and cand as for c1k_launch_choose_modes; sf_offsets as for
+// c1k_launch_measured_sf.  Per (unit, candidate) what c1k_launch_measured_sf reports under that constant byte: distortion (units *
+// n_cand * 2, unit-major: T_ref, T(n*)) and energy (units * n_cand); choice = the smallest k of least T_final, modes_out = its
+// byte, taken and shifts (units * 52) the winner's; finalize: the winner's coefficients, side record (with the chosen indices)
+// and allocation are left in L.coefs, L.side and L.alloc, where the packing kernels read them.  Every output may be null
+void c1k_launch_measured_modes(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
+                               int64_t trial_stride, const uint8_t *cand, int n_cand, const int8_t *sf_offsets, int n_offsets, bool finalize,
+                               uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion, double *energy,
+                               hipStream_t stream);
 // the word lengths allocated by the measured coding error (c1_k_measured.hip; the definition is include/carta1_hip.h's).  L.coefs,
 // L.side: the analysis' planes; L.alloc: the record c1k_launch_allocate left for every unit.  Per unit the table e(b, w), the
 // greedy allocation for each of the eight amounts, T_ref over the record and T(n*) over the best greedy one; taken = T(n*) <

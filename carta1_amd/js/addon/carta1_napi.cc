@@ -487,6 +487,57 @@ napi_value EncodeMeasuredSf(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// encodeMeasuredModes(ctx, [Float32Array...], haloFrames, options, Uint8Array candidates, Int8Array offsets)
+// -> { units: Uint8Array(frames*channels*212), choice, modes, taken: Uint8Array(frames*channels), shifts:
+// Int8Array(frames*channels*52), distortion: Float64Array(frames*channels*n*2) (unit-major: T_ref, T(n*) per candidate), energy:
+// Float64Array(frames*channels*n) }: c1_encode_measured_modes_batch, n = 1..8 distinct mode bytes
+napi_value EncodeMeasuredModes(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_cand = 0, n_offsets = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *cand = nullptr, *offsets = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o) || !get_typed(env, argv[4], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  if (!get_typed(env, argv[5], napi_int8_array, &offsets, &n_offsets)) return nullptr;
+  if (n_cand < 1 || n_cand > C1_MAX_MODE_CANDIDATES) { napi_throw_range_error(env, nullptr, "candidates must hold 1 to 8 mode bytes"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  if (n_offsets > 64) n_offsets = 64;                           // the library's own check names the limit
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  uint8_t *units, *choice, *modes, *taken;
+  napi_value out_units = make_u8(env, n_units * C1_UNIT_BYTES, &units), out_choice = make_u8(env, n_units, &choice),
+             out_modes = make_u8(env, n_units, &modes), out_taken = make_u8(env, n_units, &taken);
+  if (!out_units || !out_choice || !out_modes || !out_taken) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  napi_value ab_s, ab_d, ab_e, out_shifts, out_dist, out_energy;
+  void *shifts, *dist, *energy;
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52, &shifts, &ab_s));
+  NAPI_OK(napi_create_typedarray(env, napi_int8_array, n_units * 52, ab_s, 0, &out_shifts));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * 2 * sizeof(double), &dist, &ab_d));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand * 2, ab_d, 0, &out_dist));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * sizeof(double), &energy, &ab_e));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand, ab_e, 0, &out_energy));
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_measured_modes_batch(ctx, p, (int)ch.size(), frames, halo, &o, static_cast<const uint8_t *>(cand), (int)n_cand,
+                                                static_cast<const int8_t *>(offsets), (int)n_offsets, units, choice, modes, taken,
+                                                static_cast<int8_t *>(shifts), static_cast<double *>(dist), static_cast<double *>(energy));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_set_named_property(env, obj, "units", out_units));
+  NAPI_OK(napi_set_named_property(env, obj, "choice", out_choice));
+  NAPI_OK(napi_set_named_property(env, obj, "modes", out_modes));
+  NAPI_OK(napi_set_named_property(env, obj, "taken", out_taken));
+  NAPI_OK(napi_set_named_property(env, obj, "shifts", out_shifts));
+  NAPI_OK(napi_set_named_property(env, obj, "distortion", out_dist));
+  NAPI_OK(napi_set_named_property(env, obj, "energy", out_energy));
+  return obj;
+}
+
 // encodeMeasuredMasked(ctx, [Float32Array...], haloFrames, options, Uint8Array modes | null, Int8Array offsets, Float64Array floor,
 // Float64Array spread | null) -> encodeMeasuredSf's object and weights: Float64Array(frames*channels*52), the reciprocal masking
 // threshold of every BFU: c1_encode_measured_masked_batch
@@ -1467,6 +1518,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeBestModes", nullptr, EncodeBestModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasured", nullptr, EncodeMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeMeasuredModes", nullptr, EncodeMeasuredModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measureUnits", nullptr, MeasureUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measurePcm", nullptr, MeasurePcm, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -56,7 +56,12 @@ export async function encodeAeaPcm(channels, options = {}) {
   // options.masking (with measuredAllocation: true only, else TypeError): true (the packaged tables, MASKING_DEFAULT) or { floor,
   // spread } as for encodeMeasured.  The measured allocation then minimises every BFU's error divided by a masking threshold
   // computed from the unit's own spectrum and these tables (c1_encode_measured_masked_batch)
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, scaleFactorOffsets, masking, ...encoderValues } = options
+  // options.measuredModeCandidates (with measuredAllocation: true only, else TypeError): an array or Uint8Array of 1 to 8 distinct
+  // mode bytes (or triples) as for blockModeCandidates: every sound unit is encoded under the candidate whose measured allocation
+  // leaves the least error (c1_encode_measured_modes_batch).  scaleFactorOffsets combines with it; mutually exclusive with
+  // blockModes, blockModeCandidates and masking (TypeError naming both).  The dearest encode of all: one greedy allocation per
+  // unit and candidate
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, measuredModeCandidates, scaleFactorOffsets, masking, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
@@ -81,6 +86,19 @@ export async function encodeAeaPcm(channels, options = {}) {
   }
   if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
     throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
+  }
+  const haveMeasuredModes = measuredModeCandidates !== undefined && measuredModeCandidates !== null
+  if (haveMeasuredModes) {
+    if (!measuredAllocation) throw new TypeError('measuredModeCandidates needs measuredAllocation: true; blockModeCandidates is the search under the reference\'s allocation')
+    for (const [name, value, why] of [['blockModes', blockModes, 'give the modes of every frame, or the candidates to choose among'],
+      ['blockModeCandidates', blockModeCandidates, 'one search per call'],
+      ['masking', masking === false ? null : masking, 'thresholds of different block modes are not comparable']]) {
+      if (value !== undefined && value !== null) throw new TypeError(`measuredModeCandidates and ${name} are mutually exclusive: ${why}`)
+    }
+    const n = measuredModeCandidates.length
+    if (!(Array.isArray(measuredModeCandidates) || measuredModeCandidates instanceof Uint8Array) || n < 1 || n > 8) {
+      throw new RangeError(`measuredModeCandidates must hold 1 to 8 mode bytes, got ${n}`)
+    }
   }
   if (measuredAllocation) {
     for (const [name, value] of [['allocationBiases', allocationBiases], ['allocationBiasCandidates', allocationBiasCandidates], ['blockModeCandidates', blockModeCandidates]]) {
@@ -149,7 +167,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && measuredAllocation) {
+  if (frames > 0 && haveMeasuredModes) {
+    image.set(encodeMeasuredModes(padded, encoderOptions.toNative(), measuredModeCandidates, haveOffsets ? scaleFactorOffsets : null).units, AEA_HEADER_SIZE)
+  } else if (frames > 0 && measuredAllocation) {
     image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null, haveOffsets ? scaleFactorOffsets : null, haveMasking ? masking : null).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && haveModeCandidates) {
     image.set(encodeBestModes(padded, encoderOptions.toNative(), blockModeCandidates).units, AEA_HEADER_SIZE)

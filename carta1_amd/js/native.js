@@ -168,6 +168,28 @@ export function encodeMeasured(channels, nativeOptions, modes = null, scaleFacto
   return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }
 
+// c1_encode_measured_modes_batch on the default context: encodeMeasured with the block modes of every sound unit chosen among the
+// candidates by the final error of the measured allocation under each -- per (unit, candidate) the figures of encodeMeasured under
+// that constant byte, the candidate of least T_final = taken ? T(n*) : T_ref wins, the first on a tie.  nativeOptions:
+// EncoderOptions.toNative(), of which only the allocation bias is used; candidates: as for encodeBestModes; scaleFactorOffsets:
+// null (the plain measured allocation) or as for encodeMeasured.  Returns { units, choice: Uint8Array(frames * channels) indexing
+// candidates, modes: the chosen bytes, taken, shifts: Int8Array(frames * channels * 52) (the winner's), distortion:
+// Float64Array(frames * channels * n * 2) unit-major (T_ref, T(n*) per candidate), energy: Float64Array(frames * channels * n) };
+// units are what encodeMeasured gives under `modes`.  The dearest encode of the library: one greedy allocation per unit and
+// candidate.
+export function encodeMeasuredModes(channels, nativeOptions, candidates, scaleFactorOffsets = null, haloFrames = 0, ctx = context()) {
+  const bytes = Uint8Array.from(Array.from(candidates), (c) => {
+    if (Array.isArray(c)) {
+      if (c.length !== 3 || c.some((m) => !Number.isInteger(m) || m < 0 || m > 3)) throw new TypeError('candidates: a triple holds three block modes 0..3')
+      return c[0] | (c[1] << 2) | (c[2] << 4)
+    }
+    if (!Number.isInteger(c) || c < 0 || c > 255) throw new TypeError('candidates: mode bytes 0..255 or triples [low, mid, high]')
+    return c
+  })
+  const offsets = scaleFactorOffsets === null || scaleFactorOffsets === undefined ? Int8Array.of(0) : checkScaleFactorOffsets(scaleFactorOffsets)
+  return native().encodeMeasuredModes(ctx, channels, haloFrames, nativeOptions, bytes, offsets)
+}
+
 // c1_measure_units_batch on the default context: the coding error of sound units that already exist -- any encoder's -- against
 // their PCM, scored from the bytes with the yardstick of encodeMeasured.  channels: one or two Float32Arrays of (haloFrames +
 // frames) * 512 samples; units: Uint8Array of frames * channels * 212 bytes (frame-major, channels interleaved), every unit's

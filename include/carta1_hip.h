@@ -449,6 +449,61 @@ int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channe
                                 int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                 double *energy /* host, or NULL */);
 
+/* ---- the block modes of every sound unit chosen from candidates by the error of the measured allocation ---------------------
+ * c1_encode_best_modes_* ranks its candidates by the error of the reference's allocation under them, and c1_encode_measured_*
+ * and c1_encode_measured_sf_* take the block modes as given.  The first ranking is a poor guide to the second: on the test
+ * material the candidate of least measured error is not c1_encode_best_modes_*'s in three units of four.  This call joins the
+ * two loops.  OPT-IN like c1_encode_measured_*; the units are ordinary sound units.
+ *   Arguments.  cand_modes and n_cand are c1_encode_best_modes_*'s exactly (HOST memory, 1 .. C1_MAX_MODE_CANDIDATES distinct
+ *     bytes of the domain, checked by both calls, C1_ERR_ARG naming the entry); sf_offsets and n_offsets are
+ *     c1_encode_measured_sf_*'s exactly, and {0} gives the plain measured allocation of c1_encode_measured_*.  Of opts only what
+ *     c1_encode_measured_* reads under given modes is read.
+ *   Definition, by composition.  For unit u and candidate k take what c1_encode_measured_sf_* reports for u under the constant
+ *     modes cand_modes[k], the same opts and offsets: T_ref(u,k), T*(u,k) = T(n*), taken(u,k) = T*(u,k) < T_ref(u,k),
+ *     energy(u,k), and the record that call would pack.  T_final(u,k) = taken(u,k) ? T*(u,k) : T_ref(u,k).  choice[u] is the
+ *     smallest k with T_final(u,k) <= T_final(u,j) for all j, on the values computed: a NaN never wins, and if every T_final is
+ *     NaN the choice is 0.  The T of different candidates are comparable because W_b makes each the PCM error energy up to one
+ *     constant (c1_encode_best_modes_* above), and a candidate's figures do not depend on the modes of the frames before it.
+ *   Outputs.  units[u]: byte for byte what c1_encode_measured_sf_* writes with modes[u] = modes_out[u]; modes_out[u] =
+ *     cand_modes[choice[u]]; taken[u] and shifts[52 u + b]: the winner's, as that call defines them; distortion[(u * n_cand + k)
+ *     * 2 + 0] = T_ref(u,k), [.. + 1] = T*(u,k); energy[u * n_cand + k] = energy(u,k).  All of them are bit for bit the
+ *     per-candidate calls' values: the orders of summation are theirs (slot order within a BFU, BFU order for the totals,
+ *     binary64, no fused operation).  Each may be NULL (units NULL: measure only, no packing runs and no record of the context is
+ *     touched); all seven NULL is C1_ERR_ARG.  With one candidate the call is c1_encode_measured_sf_* under a constant byte.
+ * Limits, alignment, chunking, asynchrony, the caller's-stream contract, repeatability, and invariance under the speculation
+ * mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP and the halo are c1_encode_best_modes_device's, and so are the
+ * front end (the exact analysis at most twice, one trial allocation per candidate) and the workspace.  One kernel then runs the
+ * measured allocation under every candidate, a wave per unit.  c1_ctx_kernel_ms counts it under "measure", the analyses and
+ * the composing under "analysis" and the trial allocations under "allocate".
+ * Cost: n_cand greedy passes per unit, about 270 ms each on 2^21 units with five offsets.  This is the library's dearest encode
+ * by far.  On 2^21 units it costs 0.67 (two candidates) to 0.88 (eight) of the loop it replaces -- n measure-only calls, the
+ * minimum on the host, one final call.  The workgroup-per-unit kernel that c1_encode_measured_* takes for launches of a few
+ * thousand units is not used, so small launches are slower than that loop: 2.3 times at 256 units, 1.1 times at 8 192 (eight
+ * candidates, five offsets).
+ * Not done: masking weights in this search (each candidate's thresholds come from another spectrum, and nothing has shown
+ * their ratios comparable across modes), pruning of candidates, a streaming form. */
+int c1_encode_measured_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                    const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
+                                    const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
+                                    uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                                    uint8_t *choice /* device, frames*channels, or NULL */,
+                                    uint8_t *modes_out /* device, frames*channels, or NULL: cand_modes[choice[u]] */,
+                                    uint8_t *taken /* device, frames*channels, or NULL */,
+                                    int8_t *shifts /* device, frames*channels*52, or NULL */,
+                                    double *distortion /* device, frames*channels*n_cand*2 (unit-major): T_ref, T(n*), or NULL */,
+                                    double *energy /* device, frames*channels*n_cand (unit-major), or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The options, the candidates, the offsets and the outputs are validated
+ * before the context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a
+ * device the call then returns C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per
+ * channel. */
+int c1_encode_measured_modes_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                   const c1_encode_options *opts, const uint8_t *cand_modes /* host */, int n_cand,
+                                   const int8_t *sf_offsets /* host */, int n_offsets,
+                                   uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
+                                   uint8_t *modes_out /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                   int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                   double *energy /* host, or NULL */);
+
 /* ---- the measured allocation with every BFU's error weighted by a masking threshold ------------------------------------------
  * c1_encode_measured_sf_* minimises the plain squared error of the coefficients, so its greedy spends bits where the signal is
  * loud.  This call divides every BFU's error by a threshold computed per sound unit from the unit's own spectrum and two tables
