@@ -28,8 +28,13 @@ def candidates_of(material, sf):
 
 
 def candidate_case(byte, material, sf):
-    """the per-candidate model: scale_factor_choice_lib's under OFFSETS, or measured_alloc_lib's"""
-    return SF.case(byte, material) if sf else MA.case(byte, material)
+    """the per-candidate model: scale_factor_choice_lib's under OFFSETS, or measured_alloc_lib's.  material: 'pink' / 'white' (the
+    shared, cached cases) or the channels of any other material (states from zero; computed here, not cached)"""
+    if isinstance(material, str):
+        return SF.case(byte, material) if sf else MA.case(byte, material)
+    import block_modes_lib as BM
+    ref = BM.oracle_encode_modes(material, np.full((len(material[0]) // 512, len(material)), byte, dtype=np.uint8), BMO.BIAS)[0]
+    return SF.model(material, ref, OFFSETS) if sf else MA.model(material, ref)
 
 
 def final(m):
@@ -37,30 +42,38 @@ def final(m):
     return np.where(m['taken'] != 0, m['D'][:, 1], m['D'][:, 0])
 
 
+def compose(cand, per, sf):
+    """the joint model of the candidate bytes `cand` from their per-candidate models `per`, in that order -> case's dict"""
+    D = np.stack([m['D'] for m in per], axis=1)
+    E = np.stack([m['E'] for m in per], axis=1)
+    fin = np.stack([final(m) for m in per], axis=1)
+    choice = np.where(np.isnan(fin), np.inf, fin).argmin(axis=1)
+    ar = np.arange(len(choice))
+    pick = lambda name: np.stack([m[name] for m in per], axis=1)[ar, choice]
+    shifts = pick('shifts') if sf else np.zeros((len(choice), 52), dtype=np.int8)
+    out = {'cand': np.asarray(cand, dtype=np.uint8), 'D': D, 'E': E, 'final': fin, 'choice': choice.astype(np.uint8),
+           'modes': np.asarray(cand, dtype=np.uint8)[choice], 'taken': pick('taken'), 'shifts': shifts, 'units': pick('units'),
+           'coefs': pick('coefs')}
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
 _cases = {}
 
 
-def case(material, sf, candidates=None):
+def case(material, sf, candidates=None, per=None):
     """-> dict: 'cand' (the bytes), 'D' float64 [U, n, 2], 'E' [U, n], 'final' [U, n], 'choice' [U], 'modes' uint8 [U], 'taken'
-    uint8 [U], 'shifts' int8 [U, 52], 'units' uint8 [U, 212] (the winner's), 'coefs' float32 [U, 512] (the winner's).  Computed
-    once per process, shared, never written"""
-    cand = list(candidates_of(material, sf) if candidates is None else candidates)
+    uint8 [U], 'shifts' int8 [U, 52], 'units' uint8 [U, 212] (the winner's), 'coefs' float32 [U, 512] (the winner's).
+    material: 'pink' / 'white' -- computed once per process, shared, never written -- or the channels of any other material, whose
+    per-candidate models may be handed in as `per` (one per candidate, in order); the caller caches those"""
+    named = isinstance(material, str)
+    cand = list(candidates_of(material if named else None, sf) if candidates is None else candidates)
+    if not named:
+        return compose(cand, [candidate_case(b, material, sf) for b in cand] if per is None else list(per), sf)
     key = (material, bool(sf), tuple(cand))
     if key not in _cases:
-        per = [candidate_case(b, material, sf) for b in cand]
-        D = np.stack([m['D'] for m in per], axis=1)
-        E = np.stack([m['E'] for m in per], axis=1)
-        fin = np.stack([final(m) for m in per], axis=1)
-        choice = np.where(np.isnan(fin), np.inf, fin).argmin(axis=1)
-        ar = np.arange(len(choice))
-        pick = lambda name: np.stack([m[name] for m in per], axis=1)[ar, choice]
-        shifts = pick('shifts') if sf else np.zeros((len(choice), 52), dtype=np.int8)
-        out = {'cand': np.asarray(cand, dtype=np.uint8), 'D': D, 'E': E, 'final': fin, 'choice': choice.astype(np.uint8),
-               'modes': np.asarray(cand, dtype=np.uint8)[choice], 'taken': pick('taken'), 'shifts': shifts, 'units': pick('units'),
-               'coefs': pick('coefs')}
-        for a in out.values():
-            a.setflags(write=False)
-        _cases[key] = out
+        _cases[key] = compose(cand, [candidate_case(b, material, sf) for b in cand], sf)
     return _cases[key]
 
 
@@ -75,6 +88,19 @@ def unique_margin(fin):
 def admissible(fin):
     """bool [units, n]: the candidates whose model T_final is within CHOICE_REL of the unit's model minimum"""
     return fin <= fin.min(axis=1, keepdims=True) * (1.0 + CHOICE_REL)
+
+
+def first_of_exact_ties(fin):
+    """admissible(fin), but where every admissible candidate of a unit has bit for bit the least T_final only the first of them:
+    an exact tie comes from candidates that differ only in bands whose coefficients are all zero, so the same e(b, w) are summed in
+    the same order under each, and the header's rule (the smallest k) decides.  With one admissible candidate nothing changes"""
+    with np.errstate(invalid='ignore'):
+        ok = admissible(fin)
+        least = fin == fin.min(axis=1, keepdims=True)
+    exact = (ok == least).all(axis=1) & least.any(axis=1)
+    first = np.zeros_like(ok)
+    first[np.arange(len(fin)), least.argmax(axis=1)] = True
+    return np.where(exact[:, None], first, ok)
 
 
 def sequence_choice(material, cand):
@@ -96,7 +122,12 @@ def check_outputs(material, sf, out, columns=None):
     the candidates candidates_of(material, sf)[columns] in that order: None, or what is wrong"""
     base = candidates_of(material, sf)
     cand = base if columns is None else [base[k] for k in columns]
-    m = case(material, sf, cand)
+    return check_case(case(material, sf, cand), out)
+
+
+def check_case(m, out):
+    """the same against any model `m` of case's form"""
+    cand = m['cand']
     if out['distortion'].shape != m['D'].shape or out['energy'].shape != m['E'].shape:
         return 'shapes %r %r' % (out['distortion'].shape, out['energy'].shape)
     for name, got, want in (('distortion', out['distortion'], m['D']), ('energy', out['energy'], m['E'])):
@@ -106,7 +137,7 @@ def check_outputs(material, sf, out, columns=None):
             return '%s at %r: %r against the model %r' % (name, at.tolist(), got[tuple(at)], want[tuple(at)])
         if ((want == 0) & (got != 0)).any():
             return '%s: an exact zero of the model is not zero' % name
-    ok = admissible(m['final'])
+    ok = first_of_exact_ties(m['final'])
     if (ok.sum(axis=1) != 1).any():
         return 'the model leaves more than one admissible candidate for some unit'
     choice = np.asarray(out['choice'])
