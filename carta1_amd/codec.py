@@ -1154,6 +1154,40 @@ class EncoderStream:
         out = out + (dist, energy) if return_distortion else out
         return out + (weights,) if return_weights else out
 
+    def push_measured_modes(self, channels, candidates, scale_factor_offsets=None, return_distortion=False, return_shifts=False):
+        """push_measured() with the block modes of every pushed unit chosen among `candidates` by the final error of the measured
+        allocation under each: Context.encode_measured_modes on a live stream (c1_enc_stream_push_measured_modes).  Per (unit,
+        candidate) the figures are push_measured(modes=constant byte, ...)'s on a twin stream; the units are
+        push_measured(modes=modes, ...)'s, and the stream afterwards is what it is after push(modes=modes), so the kinds of push
+        may be mixed.  For a stream pushed from its start the rows are Context.encode_measured_modes' over the whole signal.
+        candidates, scale_factor_offsets, the return_* flags, their ValueErrors and the result -- (units, choice, modes,
+        taken[, shifts][, distortion, energy]) -- are Context.encode_measured_modes'."""
+        chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
+        if len(chans) != self.channels:
+            raise ValueError('expected %d channels' % self.channels)
+        n = len(chans[0])
+        if any(len(c) != n for c in chans) or n % 512:
+            raise ValueError('channels must have equal length, a multiple of 512')
+        frames = n // 512
+        cand = mode_candidates(candidates)
+        count = len(cand)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
+        total = frames * self.channels
+        units = np.zeros((total, 212), dtype=np.uint8)
+        choice = np.zeros(total, dtype=np.uint8)
+        modes = np.zeros(total, dtype=np.uint8)
+        taken = np.zeros(total, dtype=np.uint8)
+        shifts = np.zeros((total, 52), dtype=np.int8) if return_shifts else None
+        dist = np.zeros((total, count, 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros((total, count), dtype=np.float64) if return_distortion else None
+        data = lambda a: None if a is None else a.ctypes.data
+        capi.check(capi.load().c1_enc_stream_push_measured_modes(
+            self._h, capi.ptr_array([c.ctypes.data for c in chans]), frames, cand.ctypes.data, count, data(offs),
+            0 if offs is None else len(offs), units.ctypes.data, choice.ctypes.data, modes.ctypes.data, taken.ctypes.data, data(shifts),
+            data(dist), data(energy)))
+        out = (units, choice, modes, taken) + ((shifts,) if return_shifts else ())
+        return out + (dist, energy) if return_distortion else out
+
     def set_options(self, options):
         """The options of every channel from the next push on, as the reference's encode() reads them on every call; the
         stream goes on (include/carta1_hip.h, c1_enc_stream_set_options).  Invalid options raise and change nothing."""

@@ -918,6 +918,22 @@ void launch_measured(c1_ctx *ctx, const C1EncodeLaunch &L, bool all_long, const 
   }
 }
 
+// The mode search of one launch, in k_choose_modes' place: L.coefs / L.side hold the all-long analysis, d_bm_coefs / d_bm_side the
+// all-short one, trial record k the reference's allocation under candidate k; bm's outputs start at unit `at` of the call's.  The
+// workgroup-per-unit kernel (c1_k_measured_modes_wide.hip, the same outputs bit for bit) for a launch of at most
+// kMeasuredModesWideUnits units; C1_MEASURED_WIDE overrides as in launch_measured
+void launch_measured_modes(c1_ctx *ctx, const C1EncodeLaunch &L, const uint8_t *trial, int64_t trial_stride, const BestModesCall *bm,
+                           int64_t at, hipStream_t stream) {
+  ScopedTiming t(ctx, K_MEASURE, stream);
+  const int64_t units = L.frames * L.channels;
+  const bool wide = ctx->measured_wide < 0 ? units <= kMeasuredModesWideUnits : ctx->measured_wide != 0;
+  (wide ? c1k_launch_measured_modes_wide : c1k_launch_measured_modes)(
+      L, ctx->d_bm_coefs, ctx->d_bm_side, trial, trial_stride, bm->cand, bm->n, bm->sf_offsets, bm->n_offsets, L.units != nullptr,
+      bm->choice ? bm->choice + at : nullptr, bm->modes_out ? bm->modes_out + at : nullptr, bm->taken ? bm->taken + at : nullptr,
+      bm->shifts ? bm->shifts + at * 52 : nullptr, bm->distortion ? bm->distortion + at * bm->n * 2 : nullptr,
+      bm->energy ? bm->energy + at * bm->n : nullptr, stream);
+}
+
 int check_channels(int channels) {
   if (channels != 1 && channels != 2) return fail(C1_ERR_ARG, "channels must be 1 or 2, got %d", channels);
   return C1_OK;
@@ -1175,13 +1191,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
         c1k_launch_allocate(A, sB);
       }
       if (bm->sf_offsets) {
-        ScopedTiming t(ctx, K_MEASURE, sB);
-        c1k_launch_measured_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, bm->sf_offsets, bm->n_offsets,
-                                  L.units != nullptr, bm->choice ? bm->choice + f0 * channels : nullptr,
-                                  bm->modes_out ? bm->modes_out + f0 * channels : nullptr, bm->taken ? bm->taken + f0 * channels : nullptr,
-                                  bm->shifts ? bm->shifts + f0 * channels * 52 : nullptr,
-                                  bm->distortion ? bm->distortion + f0 * channels * bm->n * 2 : nullptr,
-                                  bm->energy ? bm->energy + f0 * channels * bm->n : nullptr, sB);
+        launch_measured_modes(ctx, L, ctx->d_trial, trial_stride, bm, f0 * channels, sB);
       } else {
         ScopedTiming t(ctx, K_CHOOSE, sB);
         c1k_launch_choose_modes(L, ctx->d_bm_coefs, ctx->d_bm_side, ctx->d_trial, trial_stride, bm->cand, bm->n, L.units != nullptr,
@@ -1438,7 +1448,8 @@ int c1_ctx_create(int device, void *hip_stream, c1_ctx **out) {
     ctx->pipeline = pl ? atoi(pl) != 0 : false;   // measured: no gain while one kernel's grid already owns every CU's LDS
   }
   // C1_MEASURED_WIDE: 0 never takes the workgroup-per-unit measured kernel, 1 always; unset: launches of at most
-  // kMeasuredWideUnits units take it.  The outputs are the same bits either way
+  // kMeasuredWideUnits units take it; the mode search's kernels likewise, by kMeasuredModesWideUnits (6q).  The
+  // outputs are the same bits either way
   const char *mw = getenv("C1_MEASURED_WIDE");
   ctx->measured_wide = mw ? (atoi(mw) != 0 ? 1 : 0) : -1;
   const char *env = getenv("C1_CHUNK_FRAMES");
@@ -3989,6 +4000,95 @@ int encode_from_states_impl(c1_ctx *ctx, int64_t n, const float *pcm, int64_t pc
   return C1_OK;
 }
 
+// a mode-search call's outputs from unit `at` on
+void bm_outputs_at(const BestModesCall &bm, int64_t at, BestModesCall *part) {
+  *part = bm;
+  if (part->choice) part->choice += at;
+  if (part->modes_out) part->modes_out += at;
+  if (part->taken) part->taken += at;
+  if (part->shifts) part->shifts += at * 52;
+  if (part->distortion) part->distortion += at * bm.n * 2;
+  if (part->energy) part->energy += at * bm.n;
+}
+
+// the options of a call whose modes are the candidates': neither threshold nor fixed modes are read
+void modes_call_opts(const c1_encode_options &opts, c1_encode_options *base) {
+  *base = opts;
+  base->transient_threshold = 1.0;
+  base->fixed_block_modes[0] = base->fixed_block_modes[1] = base->fixed_block_modes[2] = -1;
+}
+
+// encode_from_states_impl with the mode search of c1_encode_measured_modes_device (bm, offsets set, outputs at its pointers): the
+// front end of that call on the from-state workspace.  The from-state kernel runs under all-long options into the workspace's
+// planes and under all-short options into the mode search's own (a plane no candidate needs is not made); the pools advance once,
+// with the last of the two (delay lines and overlap do not depend on the modes, and under fixed modes the magnitudes stay).  Then
+// per candidate the composed side record and the allocation into its trial records, launch_measured_modes, packing.  n is a
+// stream's channel count: one chunk
+int encode_from_states_modes(c1_ctx *ctx, int64_t n, const float *pcm, int64_t pcm_stride, float *state, const c1_encode_options *base,
+                             uint8_t *units, const BestModesCall *bm) {
+  int rc;
+  bool bm_long = false, bm_short = false;                      // some candidate codes a band long / short
+  for (int k = 0; k < bm->n; k++) {
+    if ((bm->cand[k] & 0x3f) != 0x3a) bm_long = true;
+    if ((bm->cand[k] & 0x3f) != 0) bm_short = true;
+  }
+  if ((rc = join_tail(ctx))) return rc;
+  if ((rc = ensure_workspace(ctx, n))) return rc;
+  if ((rc = ensure_trial_allocs(ctx, n, bm->n))) return rc;
+  if ((rc = ensure_best_modes_planes(ctx, n))) return rc;
+  bool first = true;
+  for (int pass = 0; pass < 2; pass++) {                       // 0: all long, 1: all short
+    if (!(pass ? bm_short : bm_long)) continue;
+    c1_encode_options one = *base;
+    one.fixed_block_modes[0] = one.fixed_block_modes[1] = pass ? 2 : 0;
+    one.fixed_block_modes[2] = pass ? 3 : 0;
+    if ((rc = upload_opts(ctx, &one))) return rc;
+    if (first && ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+    first = false;
+    C1EncStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.pcm = pcm;
+    K.pcm_stride = pcm_stride;
+    K.in = state;
+    K.out = (pass == 1 || !bm_short) ? state : nullptr;        // the last pass leaves the pools
+    K.n = n;
+    K.tables = ctx->d_tables;
+    K.opts = ctx->d_opts;
+    K.coefs = pass ? ctx->d_bm_coefs : ctx->d_coefs[0];
+    K.side = pass ? ctx->d_bm_side : ctx->d_side[0];
+    K.detect = -1;
+    ScopedTiming t(ctx, K_FROM_STATE);
+    c1k_launch_encode_from_states(K, ctx->stream);
+  }
+  C1EncodeLaunch L;
+  memset(&L, 0, sizeof L);
+  L.channels = 1;
+  L.frames = n;
+  L.tables = ctx->d_tables;
+  L.opts = ctx->d_opts;
+  L.coefs = ctx->d_coefs[0];
+  L.side = ctx->d_side[0];
+  L.alloc = ctx->d_alloc[0];
+  L.cand = ctx->d_cand[0];
+  L.work_count = ctx->d_work[0];
+  L.work_list = ctx->d_work[0] + 4;
+  L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
+  L.units = units;
+  const int64_t trial_stride = ctx->trial_units * kAllocBytes;
+  for (int k = 0; k < bm->n; k++) {                            // one chain after the other: they share the side plane and the scratch
+    { ScopedTiming t(ctx, K_ANALYSIS); c1k_launch_compose_side(L.side, ctx->d_bm_side, n, bm->cand[k], ctx->d_bm_cand_side, ctx->stream); }
+    ScopedTiming t(ctx, K_ALLOCATE);
+    C1EncodeLaunch A = L;
+    A.side = ctx->d_bm_cand_side;
+    A.alloc = ctx->d_trial + (size_t)k * trial_stride;
+    c1k_launch_allocate(A, ctx->stream);
+  }
+  launch_measured_modes(ctx, L, ctx->d_trial, trial_stride, bm, 0, ctx->stream);
+  { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
 // the first non-finite entry of `count` states of `floats` floats each: C1_ERR_ARG naming pool (or channel) and field
 struct StateField { const char *name; int first, count; };
 const StateField kEncStateFields[] = {{"qmf_low", 0, 46}, {"qmf_mid", 46, 46}, {"qmf_high", 92, 39}, {"mdct_overlap", 131, 96}, {"transient_mags", 227, 256}};
@@ -4067,7 +4167,8 @@ int enc_stream_freeze_history(c1_enc_stream *s) {
 
 int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
                          const c1_encode_options *palette = nullptr, int n_palette = 0, const uint8_t *bias_index = nullptr,
-                         const MeasuredCall *mc = nullptr, const MeasuredCall *mc_host = nullptr);
+                         const MeasuredCall *mc = nullptr, const MeasuredCall *mc_host = nullptr, const BestModesCall *bm = nullptr,
+                         const BestModesCall *bm_host = nullptr);
 }  // namespace
 
 int c1_enc_stream_create(c1_ctx *ctx, int channels, const c1_encode_options *opts, c1_enc_stream **out) {
@@ -4125,6 +4226,18 @@ int c1_enc_stream_push_biases(c1_enc_stream *s, const float *const *pcm, int64_t
   return enc_stream_push_impl(s, pcm, frames, modes, units, palette, n_palette, bias_index);
 }
 
+// the staging of a measured push's per-unit outputs: one block of kMeasBlockBytes per unit, grown to the largest push so far
+constexpr size_t kMeasBlockBytes = 52 * sizeof(double) + 3 * sizeof(double) + 52 + 8;
+static int enc_stream_meas_block(c1_enc_stream *s, int64_t n_units) {
+  if (n_units <= s->meas_units) return C1_OK;
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  if (s->d_meas) (void)hipFree(s->d_meas);
+  s->d_meas = nullptr; s->meas_units = 0;
+  HIP_TRY(hipMalloc(&s->d_meas, (size_t)n_units * kMeasBlockBytes));
+  s->meas_units = n_units;
+  return C1_OK;
+}
+
 int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes,
                                 const int8_t *sf_offsets, int n_offsets, const double *mask_floor, const double *mask_spread,
                                 uint8_t *units, uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights) {
@@ -4150,13 +4263,7 @@ int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm, int64
   if (modes && (rc = check_mode_bytes(what, modes, frames, s->channels))) return rc;
   // from here on only the device can fail.  The outputs' staging: one block, grown to the largest push so far
   const int64_t n_units = frames * s->channels;
-  if (n_units > s->meas_units) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (s->d_meas) (void)hipFree(s->d_meas);
-    s->d_meas = nullptr; s->meas_units = 0;
-    HIP_TRY(hipMalloc(&s->d_meas, (size_t)n_units * (52 * sizeof(double) + 3 * sizeof(double) + 52 + 8)));
-    s->meas_units = n_units;
-  }
+  if ((rc = enc_stream_meas_block(s, n_units))) return rc;
   char *block = static_cast<char *>(s->d_meas);
   const size_t cap = (size_t)s->meas_units;
   double *d_weights = reinterpret_cast<double *>(block), *d_dist = d_weights + cap * 52, *d_energy = d_dist + cap * 2;
@@ -4183,18 +4290,67 @@ int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm, int64
   return C1_OK;
 }
 
+int c1_enc_stream_push_measured_modes(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *cand_modes, int n_cand,
+                                      const int8_t *sf_offsets, int n_offsets, uint8_t *units, uint8_t *choice, uint8_t *modes_out,
+                                      uint8_t *taken, int8_t *shifts, double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a stream nor a device
+  const char *const what = "c1_enc_stream_push_measured_modes";
+  int rc;
+  if (frames < 0) return fail(C1_ERR_ARG, "%s: frames must be >= 0", what);
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "%s: at most %lld frames per call", what, (long long)kMaxModesBatchFrames);
+  if ((rc = check_mode_candidates(what, cand_modes, n_cand))) return rc;
+  if (!sf_offsets && n_offsets != 0) return fail(C1_ERR_ARG, "%s: n_offsets = %d, but sf_offsets is NULL", what, n_offsets);
+  if (sf_offsets && (rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if (frames > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "%s: pcm or units is NULL", what);
+  if (!s) return fail(C1_ERR_ARG, "%s: stream is NULL", what);
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if ((rc = check_measured_opts(what, &s->opts, false))) return rc;
+  if (frames == 0) return C1_OK;
+  for (int c = 0; c < s->channels; c++)
+    if (!pcm[c]) return fail(C1_ERR_ARG, "%s: pcm[%d] is NULL", what, c);
+  // from here on only the device can fail.  The outputs' staging: c1_enc_stream_push_measured's block, which holds these as well
+  static_assert(kMeasBlockBytes >= C1_MAX_MODE_CANDIDATES * 3 * sizeof(double) + 52 + 3, "the staging block holds a mode search's outputs");
+  const int64_t n_units = frames * s->channels;
+  if ((rc = enc_stream_meas_block(s, n_units))) return rc;
+  const size_t cap = (size_t)s->meas_units;
+  double *d_dist = static_cast<double *>(s->d_meas), *d_energy = d_dist + cap * C1_MAX_MODE_CANDIDATES * 2;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>(d_energy + cap * C1_MAX_MODE_CANDIDATES);
+  uint8_t *d_choice = reinterpret_cast<uint8_t *>(d_shifts + cap * 52), *d_modes = d_choice + cap, *d_taken = d_modes + cap;
+  static const int8_t kOwnIndex[1] = {0};                      // no offsets: the search over the plain measured allocation
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's arrays may change while the call runs
+  int8_t offs[C1_MAX_SF_OFFSETS];
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  if (sf_offsets) memcpy(offs, sf_offsets, (size_t)n_offsets);
+  BestModesCall bm = {n_cand, cand, choice ? d_choice : nullptr, modes_out ? d_modes : nullptr, distortion ? d_dist : nullptr,
+                      energy ? d_energy : nullptr};
+  bm.sf_offsets = sf_offsets ? offs : kOwnIndex;
+  bm.n_offsets = sf_offsets ? n_offsets : 1;
+  bm.taken = taken ? d_taken : nullptr;
+  bm.shifts = shifts ? d_shifts : nullptr;                     // a single offset 0 moves no index: zeros
+  BestModesCall host = {n_cand, cand, choice, modes_out, distortion, energy};
+  host.taken = taken;
+  host.shifts = shifts;
+  return enc_stream_push_impl(s, pcm, frames, nullptr, units, nullptr, 0, nullptr, nullptr, nullptr, &bm, &host);
+}
+
 namespace {
 // modes null: the stream's options decide.  Else the frames behave as if the options had been switched to fixed block modes
 // for them, frame by frame and channel by channel, and back afterwards: the detector does not run, and on a stream under
 // detection its history stays where c1_enc_stream_set_options would have frozen it.
 // palette non-null (c1_enc_stream_push_biases): unit u allocates under the table of palette[bias_index[u]] instead of the
 // stream's; nothing else of the entries is read, and the stream's options and state are as after the same push without it
+// bm non-null (c1_enc_stream_push_measured_modes, everything validated): the frames behave as under given modes, which the mode
+// search of c1_encode_measured_modes_device chooses: that call's chain with halo 2 on the usual path, encode_from_states_modes
+// for the frames encoded from the explicit state; there is no detection frame and no switch frame.  bm's outputs are device
+// memory over the push's units and are copied to bm_host's with the units
 // mc non-null (c1_enc_stream_push_measured, everything validated and the tables uploaded): the measured allocation runs between
 // allocation and packing on whichever of the three paths a frame takes; mc's outputs are device memory over the push's units and
 // are copied to mc_host's with the units.  It keeps no state: the stream is as after the same push without it
 int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *modes, uint8_t *units,
                          const c1_encode_options *palette, int n_palette, const uint8_t *bias_index, const MeasuredCall *mc,
-                         const MeasuredCall *mc_host) {
+                         const MeasuredCall *mc_host, const BestModesCall *bm, const BestModesCall *bm_host) {
   if (!s) return fail(C1_ERR_ARG, "stream is NULL");
   c1_ctx *ctx = s->ctx;
   CTX_GUARD(ctx);
@@ -4208,8 +4364,8 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   if (palette && (rc = check_index_bytes("c1_enc_stream_push_biases", bias_index, frames, s->channels, n_palette))) return rc;
   if (modes && (rc = check_mode_bytes(palette ? "c1_enc_stream_push_biases" : "c1_enc_stream_push_modes", modes, frames, s->channels))) return rc;   // the stream is as it was
   if (palette && (rc = upload_palette(ctx, "c1_enc_stream_push_biases", palette, n_palette))) return rc;
-  if (modes && opts_detect(s->opts) && s->state_frames == 0 && (rc = enc_stream_freeze_history(s))) return rc;
-  const bool detect = !modes && opts_detect(s->opts);
+  if ((modes || bm) && opts_detect(s->opts) && s->state_frames == 0 && (rc = enc_stream_freeze_history(s))) return rc;
+  const bool detect = !modes && !bm && opts_detect(s->opts);
   // frames of this push that are encoded from the explicit state: the first two after a restore, or the first under
   // detection when the detection history is a set of magnitudes only the state holds
   int64_t from_state = std::min<int64_t>(frames, s->state_frames);
@@ -4252,6 +4408,14 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   // the frames that are not encoded from the explicit state: the stream's options, or the given modes in their place
   auto encode_rest = [&](const float *const *p, int64_t first, int64_t n) {
     uint8_t *out = s->d_units + (size_t)first * s->channels * C1_UNIT_BYTES;
+    if (bm) {                                                  // c1_encode_measured_modes_device with halo 2, the outputs from unit first * channels on
+      BestModesCall part;
+      c1_encode_options base;
+      bm_outputs_at(*bm, first * s->channels, &part);
+      modes_call_opts(s->opts, &base);
+      return encode_device_impl(ctx, p, s->channels, n, 2, &base, out, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr,
+                                &part);
+    }
     if (!modes && !palette && !mc) return encode_device_joined(ctx, p, s->channels, n, 2, &s->opts, out);
     MeasuredCall part;
     if (mc) {                                                  // the call's outputs from unit first * channels on
@@ -4270,6 +4434,15 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
   };
   if (from_state > 0) {
     for (int64_t f = 0; f < from_state; f++) {   // frame after frame: each continues the pool the one before left
+      if (bm) {
+        BestModesCall part;
+        c1_encode_options base;
+        bm_outputs_at(*bm, f * s->channels, &part);
+        modes_call_opts(s->opts, &base);
+        if ((rc = encode_from_states_modes(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &base,
+                                           s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, &part))) return rc;
+        continue;
+      }
       if (!modes && !palette) {
         if ((rc = encode_from_states_impl(ctx, s->channels, dptr[0] + f * 512, (int64_t)stride, s->d_state, &s->opts,
                                           s->d_units + (size_t)f * s->channels * C1_UNIT_BYTES, s->d_state, mc, f * s->channels))) return rc;
@@ -4309,6 +4482,15 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
     if (mc_host->distortion) HIP_TRY(hipMemcpyAsync(mc_host->distortion, mc->distortion, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (mc_host->energy) HIP_TRY(hipMemcpyAsync(mc_host->energy, mc->energy, n_units * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (mc_host->weights) HIP_TRY(hipMemcpyAsync(mc_host->weights, mc->weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (bm && bm_host) {
+    const size_t n_units = (size_t)s->channels * frames;
+    if (bm_host->choice) HIP_TRY(hipMemcpyAsync(bm_host->choice, bm->choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->modes_out) HIP_TRY(hipMemcpyAsync(bm_host->modes_out, bm->modes_out, n_units, hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->taken) HIP_TRY(hipMemcpyAsync(bm_host->taken, bm->taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->shifts) HIP_TRY(hipMemcpyAsync(bm_host->shifts, bm->shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->distortion) HIP_TRY(hipMemcpyAsync(bm_host->distortion, bm->distortion, n_units * bm->n * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->energy) HIP_TRY(hipMemcpyAsync(bm_host->energy, bm->energy, n_units * bm->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   s->pushed += frames;

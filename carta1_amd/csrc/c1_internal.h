@@ -362,6 +362,17 @@ void c1k_launch_measured_modes(const C1EncodeLaunch &L, const float *coefs_short
                                int64_t trial_stride, const uint8_t *cand, int n_cand, const int8_t *sf_offsets, int n_offsets, bool finalize,
                                uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion, double *energy,
                                hipStream_t stream);
+// c1k_launch_measured_modes for few units (c1_k_measured_modes_wide.hip): a workgroup of eight waves per unit, one all-long and
+// one all-short table instead of one per candidate, the 8 x n_cand greedy chains dealt over the waves; the same arguments, the
+// same workspace, every output bit for bit
+void c1k_launch_measured_modes_wide(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
+                                    int64_t trial_stride, const uint8_t *cand, int n_cand, const int8_t *sf_offsets, int n_offsets,
+                                    bool finalize, uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion,
+                                    double *energy, hipStream_t stream);
+// launches of at most this many units take c1k_launch_measured_modes_wide: the largest count of DESIGN.md 6q's sweep (1 .. 8 192
+// units, two candidates at offset 0 and eight at five offsets), at every one of which it was the faster kernel (10 times at up to
+// 256 units with eight candidates, 1.4 to 2.4 times at 8 192); C1_MEASURED_WIDE overrides
+constexpr int64_t kMeasuredModesWideUnits = 8192;
 // the word lengths allocated by the measured coding error (c1_k_measured.hip; the definition is include/carta1_hip.h's).  L.coefs,
 // L.side: the analysis' planes; L.alloc: the record c1k_launch_allocate left for every unit.  Per unit the table e(b, w), the
 // greedy allocation for each of the eight amounts, T_ref over the record and T(n*) over the best greedy one; taken = T(n*) <

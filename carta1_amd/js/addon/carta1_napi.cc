@@ -1054,6 +1054,34 @@ napi_value EncStreamPushMeasured(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encStreamPushMeasuredModes(stream, [Float32Array...], Uint8Array candidates, Int8Array offsets | null) -> Uint8Array units:
+// encStreamPush with the block modes of every unit chosen among the candidates by the measured allocation's final error, as
+// encodeMeasuredModes chooses them (offsets null: the plain measured allocation): c1_enc_stream_push_measured_modes
+napi_value EncStreamPushMeasuredModes(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  c1_enc_stream *s;
+  std::vector<float *> ch;
+  size_t samples = 0, n_cand = 0, n_off = 0;
+  void *cand = nullptr, *off = nullptr;
+  if (!get_external(env, argv[0], &s) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  if (!get_typed(env, argv[2], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  napi_valuetype t;
+  NAPI_OK(napi_typeof(env, argv[3], &t));
+  if (t != napi_null && t != napi_undefined && !get_typed(env, argv[3], napi_int8_array, &off, &n_off)) return nullptr;
+  if (samples % 512) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  if (n_cand > 64) n_cand = 64;                                 // the library's own checks name the limits
+  if (n_off > 64) n_off = 64;
+  const int64_t frames = (int64_t)(samples / 512);
+  uint8_t *units;
+  napi_value out = make_u8(env, (size_t)frames * ch.size() * C1_UNIT_BYTES, &units);
+  const float *p[2] = {ch[0], ch.size() > 1 ? ch[1] : nullptr};
+  const int rc = c1_enc_stream_push_measured_modes(s, p, frames, static_cast<const uint8_t *>(cand), (int)n_cand,
+                                                   static_cast<const int8_t *>(off), off ? (int)n_off : 0, units, nullptr, nullptr, nullptr,
+                                                   nullptr, nullptr, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 // encStreamSetOptions(stream, packedOptions): the options of the next push on (c1_enc_stream_set_options)
 napi_value EncStreamSetOptions(napi_env env, napi_callback_info info) {
   napi_value argv[2];
@@ -1532,6 +1560,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPushMeasured", nullptr, EncStreamPushMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamPushMeasuredModes", nullptr, EncStreamPushMeasuredModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamGetState", nullptr, StreamGetState<c1_enc_stream, c1_enc_state, c1_enc_stream_get_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetState", nullptr, StreamSetState<c1_enc_stream, c1_enc_state, c1_enc_stream_set_state>, nullptr, nullptr, nullptr, napi_default, nullptr},

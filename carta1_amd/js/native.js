@@ -168,6 +168,19 @@ export function encodeMeasured(channels, nativeOptions, modes = null, scaleFacto
   return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }
 
+// mode candidates as the mode-search calls take them (a Uint8Array or an array; an entry may be a triple [low, mid, high]) ->
+// Uint8Array of mode bytes; the library checks domain, count and repeats
+export function modeCandidateBytes(candidates) {
+  return Uint8Array.from(Array.from(candidates), (c) => {
+    if (Array.isArray(c)) {
+      if (c.length !== 3 || c.some((m) => !Number.isInteger(m) || m < 0 || m > 3)) throw new TypeError('candidates: a triple holds three block modes 0..3')
+      return c[0] | (c[1] << 2) | (c[2] << 4)
+    }
+    if (!Number.isInteger(c) || c < 0 || c > 255) throw new TypeError('candidates: mode bytes 0..255 or triples [low, mid, high]')
+    return c
+  })
+}
+
 // c1_encode_measured_modes_batch on the default context: encodeMeasured with the block modes of every sound unit chosen among the
 // candidates by the final error of the measured allocation under each -- per (unit, candidate) the figures of encodeMeasured under
 // that constant byte, the candidate of least T_final = taken ? T(n*) : T_ref wins, the first on a tie.  nativeOptions:

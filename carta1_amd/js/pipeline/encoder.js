@@ -7,27 +7,41 @@ import { EncoderOptions } from '../core/options.js'
 import { BufferPool } from '../core/buffers.js'
 import { SAMPLES_PER_FRAME, SCALE_FACTORS, SPECS_PER_BFU } from '../core/constants.js'
 import { deserializeFrame } from '../io/serialization.js'
-import { native, context, checkScaleFactorOffsets, checkMasking } from '../native.js'
+import { native, context, checkScaleFactorOffsets, checkMasking, modeCandidateBytes } from '../native.js'
 import { throwError } from '../utils.js'
 
 // measured (not in the reference; optional, read per call as `options` is): { measuredAllocation: true, scaleFactorOffsets,
 // masking } allocates the frame's word lengths -- with scaleFactorOffsets its scale-factor indices too, with masking under a
 // masking threshold -- by the measured coding error, as encodeAeaPcm's options of the same names do (include/carta1_hip.h,
-// c1_enc_stream_push_measured).  The measured allocation keeps no state, so frames with and without it may alternate on one
-// pool.  Without the object, or with measuredAllocation falsy, the closure is the reference's, byte for byte; scaleFactorOffsets
-// or masking without measuredAllocation: true is encodeAeaPcm's TypeError.
+// c1_enc_stream_push_measured).  measuredModeCandidates (with measuredAllocation: true only; scaleFactorOffsets combines with it,
+// masking does not: encodeAeaPcm's TypeErrors) chooses the frame's block modes among 1 to 8 mode bytes or triples by the measured
+// allocation's final error under each (c1_enc_stream_push_measured_modes); the fields' blockModes are then the unit's, whatever
+// options.fixedBlockModes says.  Neither keeps any state, so frames with and without them may alternate on one pool.  Without the
+// object, or with measuredAllocation falsy, the closure is the reference's, byte for byte; scaleFactorOffsets, masking or
+// measuredModeCandidates without measuredAllocation: true is encodeAeaPcm's TypeError.
 function measuredArguments(measured) {
   if (measured === undefined || measured === null) return null
-  const { measuredAllocation, scaleFactorOffsets, masking } = measured
+  const { measuredAllocation, measuredModeCandidates, scaleFactorOffsets, masking } = measured
   if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
     throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
   }
+  const haveMasking = masking !== undefined && masking !== null && masking !== false
+  const haveCandidates = measuredModeCandidates !== undefined && measuredModeCandidates !== null
+  let candidates = null
+  if (haveCandidates) {
+    if (!measuredAllocation) throw new TypeError('measuredModeCandidates needs measuredAllocation: true; blockModeCandidates is the search under the reference\'s allocation')
+    if (haveMasking) throw new TypeError('measuredModeCandidates and masking are mutually exclusive: thresholds of different block modes are not comparable')
+    const n = measuredModeCandidates.length
+    if (!(Array.isArray(measuredModeCandidates) || measuredModeCandidates instanceof Uint8Array) || n < 1 || n > 8) {
+      throw new RangeError(`measuredModeCandidates must hold 1 to 8 mode bytes, got ${n}`)
+    }
+    candidates = modeCandidateBytes(measuredModeCandidates)
+  }
   const haveOffsets = scaleFactorOffsets !== undefined && scaleFactorOffsets !== null
   if (haveOffsets && !measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
-  const haveMasking = masking !== undefined && masking !== null && masking !== false
   if (haveMasking && !measuredAllocation) throw new TypeError('masking needs measuredAllocation: true; no other path weighs its errors')
   if (!measuredAllocation) return null
-  return { offsets: haveOffsets ? checkScaleFactorOffsets(scaleFactorOffsets) : null, tables: haveMasking ? checkMasking(masking) : { floor: null, spread: null } }
+  return { candidates, offsets: haveOffsets ? checkScaleFactorOffsets(scaleFactorOffsets) : null, tables: haveMasking ? checkMasking(masking) : { floor: null, spread: null } }
 }
 
 export function encode(options = new EncoderOptions(), bufferPool = new BufferPool(), measured = undefined) {
@@ -54,11 +68,15 @@ export function encode(options = new EncoderOptions(), bufferPool = new BufferPo
       addon.encStreamSetOptions(bufferPool.encoderStream, packed)
       bufferPool.encoderOptionsKey = key
     }
-    const unit = how
-      ? addon.encStreamPushMeasured(bufferPool.encoderStream, [pcmSamples], how.offsets, how.tables.floor, how.tables.spread)
-      : addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
+    const searched = how !== null && how.candidates !== null
+    const unit = searched
+      ? addon.encStreamPushMeasuredModes(bufferPool.encoderStream, [pcmSamples], how.candidates, how.offsets)
+      : how
+        ? addon.encStreamPushMeasured(bufferPool.encoderStream, [pcmSamples], how.offsets, how.tables.floor, how.tables.spread)
+        : addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
     const fields = deserializeFrame(unit)
-    if (options.fixedBlockModes) fields.blockModes = options.fixedBlockModes // same array, as encoder.js:131-132
+    // same array, as encoder.js:131-132; modes the candidates chose are the unit's own
+    if (options.fixedBlockModes && !searched) fields.blockModes = options.fixedBlockModes
     return fields
   }
 }

@@ -473,15 +473,20 @@ int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channe
  * Limits, alignment, chunking, asynchrony, the caller's-stream contract, repeatability, and invariance under the speculation
  * mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP and the halo are c1_encode_best_modes_device's, and so are the
  * front end (the exact analysis at most twice, one trial allocation per candidate) and the workspace.  One kernel then runs the
- * measured allocation under every candidate, a wave per unit.  c1_ctx_kernel_ms counts it under "measure", the analyses and
- * the composing under "analysis" and the trial allocations under "allocate".
+ * measured allocation under every candidate.  c1_ctx_kernel_ms counts it under "measure", one launch per launch of the chain,
+ * the analyses and the composing under "analysis" and the trial allocations under "allocate".
+ * Which kernel measures: a launch of at most 8 192 sound units -- of this call or of c1_enc_stream_push_measured_modes -- takes a
+ * kernel that spends a workgroup of eight waves on every unit, builds the error table twice (from the all-long and from the
+ * all-short analysis) instead of once per candidate and runs the 8 x n_cand greedy chains beside each other; larger launches a
+ * wave per unit.  The outputs are the same bits.  C1_MEASURED_WIDE, read when a context is created, overrides this as it does
+ * for c1_encode_measured_*: 0 never the workgroup kernel, 1 always.
  * Cost: n_cand greedy passes per unit, about 270 ms each on 2^21 units with five offsets.  This is the library's dearest encode
  * by far.  On 2^21 units it costs 0.67 (two candidates) to 0.88 (eight) of the loop it replaces -- n measure-only calls, the
- * minimum on the host, one final call.  The workgroup-per-unit kernel that c1_encode_measured_* takes for launches of a few
- * thousand units is not used, so small launches are slower than that loop: 2.3 times at 256 units, 1.1 times at 8 192 (eight
- * candidates, five offsets).
+ * minimum on the host, one final call.  Small launches: at 256 units, eight candidates and five offsets the search takes 0.30 ms
+ * in the workgroup kernel against 2.98 ms a wave per unit, and the whole call 1.54 ms against 2.72 ms for that loop (DESIGN.md
+ * 6q).
  * Not done: masking weights in this search (each candidate's thresholds come from another spectrum, and nothing has shown
- * their ratios comparable across modes), pruning of candidates, a streaming form. */
+ * their ratios comparable across modes), pruning of candidates.  The streaming form is c1_enc_stream_push_measured_modes. */
 int c1_encode_measured_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                                     const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
                                     const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
@@ -750,6 +755,32 @@ int c1_enc_stream_push_measured(c1_enc_stream *s, const float *const *pcm /* hos
                                 uint8_t *units /* host, frames*channels*212 */, uint8_t *taken /* host, or NULL */,
                                 int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                 double *energy /* host, or NULL */, double *weights /* host, or NULL */);
+/* The block modes of the pushed frames chosen from candidates by the error of the measured allocation: the streaming form of
+ * c1_encode_measured_modes_* (above), OPT-IN like it.
+ * Definition, by composition.  For unit u and candidate k the figures (T_ref, T*, taken, energy) are what
+ * c1_enc_stream_push_measured(modes = the constant cand_modes[k], sf_offsets, no tables) reports for the same PCM on a twin stream
+ * in the same state; choice, modes_out and T_final are c1_encode_measured_modes_*'s; units, taken and shifts are byte for byte
+ * c1_enc_stream_push_measured(modes = modes_out)'s.  After the push the stream is bit for bit what it is after
+ * c1_enc_stream_push_modes of the same PCM -- c1_enc_stream_get_state, the detection history and the count of pushed frames: the
+ * QMF delay lines and the MDCT overlap do not depend on the modes, and on a stream under detection the frames behave as a
+ * temporary switch to fixed modes.  So for a stream pushed from its start the rows are those of c1_encode_measured_modes_batch
+ * over the whole signal, whatever the stream's block-mode options are, and all kinds of push mix freely on one stream.  The
+ * first two frames after c1_enc_stream_set_state run that call's front end on the restored pools (the from-state analysis under
+ * all-long and all-short modes, the pools advanced once); there is no detection frame and no switch frame.
+ * Arguments.  Every pointer is HOST memory.  units is required; choice, modes_out, taken (frames*channels), shifts
+ * (frames*channels*52), distortion (frames*channels*n_cand*2) and energy (frames*channels*n_cand) may each be NULL and have the
+ * shapes and meanings of c1_encode_measured_modes_batch.  sf_offsets NULL with n_offsets 0 gives the plain measured allocation
+ * (shifts is then zeros); n_offsets != 0 with sf_offsets NULL is C1_ERR_ARG.  The candidates and the offsets are validated as in
+ * the whole-buffer call, with the same messages, the stream's options as that call validates its own.  What the arguments alone
+ * decide is decided before the stream is looked at.  A rejected call leaves the stream and every output as they were.  frames
+ * 0 .. 2^22 per call.  "measure" in c1_ctx_kernel_ms counts the search, one launch per launch of the chain. */
+int c1_enc_stream_push_measured_modes(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
+                                      const uint8_t *cand_modes /* host, n_cand bytes */, int n_cand,
+                                      const int8_t *sf_offsets /* host, n_offsets values, or NULL */, int n_offsets,
+                                      uint8_t *units /* host, frames*channels*212 */, uint8_t *choice /* host, or NULL */,
+                                      uint8_t *modes_out /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                      int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                      double *energy /* host, or NULL */);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
