@@ -1029,6 +1029,69 @@ class Context:
             C.c_void_p(states_ptr) if states_ptr else None, C.byref(opts), C.c_void_p(units_ptr),
             C.c_void_p(out_states_ptr) if out_states_ptr else None))
 
+    def encode_signals_measured(self, signals, modes=None, options=None, states=None, return_states=False, in_place=False,
+                                scale_factor_offsets=None, masking=None, return_distortion=False, return_shifts=False,
+                                return_weights=False):
+        """encode_signals() with the measured allocation of encode_measured() (c1_encode_signals_measured): signal i's rows are
+        what EncoderStream.push_measured reports for it in one push on a mono stream restored to states[i] (or fresh).  modes:
+        None, or one array of mode bytes per signal, one byte per frame (as for encode_modes()).  scale_factor_offsets, masking,
+        the return_* flags and their ValueErrors are encode_measured()'s.  Returns per-signal lists in encode_measured()'s result
+        order -- (units, taken[, shifts][, distortion, energy][, weights]) -- and last, with return_states or in_place, the
+        (n, 483) pools after every signal's last frame."""
+        pcm, off = signals_layout([pad_signal(x) for x in signals])
+        n = off.size - 1
+        total = int(off[-1])
+        st = None if states is None else _state_rows(states, capi.ENC_STATE_FLOATS, n)
+        if in_place and st is None:
+            raise ValueError('in_place needs states')
+        m = None
+        if modes is not None:
+            if len(modes) != n:
+                raise ValueError('modes must hold one array of mode bytes per signal: %d arrays for %d signals' % (len(modes), n))
+            rows = [check_block_modes(modes[i], int(off[i + 1] - off[i]), 1).reshape(-1) for i in range(n)]
+            m = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        if return_shifts and scale_factor_offsets is None:
+            raise ValueError('return_shifts needs scale_factor_offsets')
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
+        out = st if in_place else (np.zeros((n, capi.ENC_STATE_FLOATS), dtype=np.float32) if return_states else None)
+        units = np.zeros((total, 212), dtype=np.uint8)
+        taken = np.zeros(total, dtype=np.uint8)
+        shifts = np.zeros((total, 52), dtype=np.int8) if return_shifts else None
+        dist = np.zeros((total, 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros(total, dtype=np.float64) if return_distortion else None
+        weights = np.zeros((total, 52), dtype=np.float64) if return_weights else None
+        opts = (options or EncoderOptions()).to_c()
+        data = lambda a: None if a is None else a.ctypes.data
+        capi.check(capi.load().c1_encode_signals_measured(
+            self._h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), pcm.ctypes.data, data(st), C.byref(opts), data(m), data(offs),
+            0 if offs is None else len(offs), None if mask is None else mask[0].ctypes.data, None if mask is None else data(mask[1]),
+            units.ctypes.data, data(out), taken.ctypes.data, data(shifts), data(dist), data(energy), data(weights)))
+        res = (split_rows(units, off), split_rows(taken, off)) + ((split_rows(shifts, off),) if return_shifts else ())
+        res = res + (split_rows(dist, off), split_rows(energy, off)) if return_distortion else res
+        res = res + (split_rows(weights, off),) if return_weights else res
+        return res + (out,) if (return_states or in_place) else res
+
+    def encode_signals_measured_device(self, frame_offsets, pcm_ptr, units_ptr=None, states_ptr=None, out_states_ptr=None, options=None,
+                                       modes_ptr=None, scale_factor_offsets=None, masking=None, taken_ptr=None, shifts_ptr=None,
+                                       distortion_ptr=None, energy_ptr=None, weights_ptr=None):
+        """c1_encode_signals_measured_device: raw device pointers as for encode_signals_device; frame_offsets, the offsets and the
+        masking tables are host values (as for encode_measured_device, the library's own checks decide).  Every output may be
+        None, not all; modes_ptr = one mode byte per frame of the concatenation on the device, or None.  Asynchronous on the
+        context's stream."""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        opts = (options or EncoderOptions()).to_c()
+        vp = lambda p: C.c_void_p(p) if p else None
+        mask = None if masking is None else check_masking(masking, check=False)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets, check=False)
+        capi.check(capi.load().c1_encode_signals_measured_device(
+            self._h, off.size - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), vp(pcm_ptr), vp(states_ptr), C.byref(opts), vp(modes_ptr),
+            offs.ctypes.data if offs is not None and len(offs) else None, 0 if offs is None else len(offs),
+            None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
+            vp(units_ptr), vp(out_states_ptr), vp(taken_ptr), vp(shifts_ptr), vp(distortion_ptr), vp(energy_ptr), vp(weights_ptr)))
+
     def decode_signals_device(self, frame_offsets, units_ptr, pcm_ptr, states_ptr=None, out_states_ptr=None):
         off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
         capi.check(capi.load().c1_decode_signals_device(
@@ -1724,16 +1787,24 @@ def aea_image_units(data):
     return units, nch
 
 
-def encode_aea_pcm_many(items, options=None, ctx=None):
+def encode_aea_pcm_many(items, options=None, ctx=None, measured_allocation=False, scale_factor_offsets=None, masking=None):
     """encode_aea_pcm for many items in one device call: items is a list of [L] or [L, R]; options.title may be one string
-    or one per item.  Every result is byte for byte what encode_aea_pcm returns for that item alone."""
+    or one per item.  Every result is byte for byte what encode_aea_pcm returns for that item alone.
+    measured_allocation: the units of every item are Context.encode_measured's for that item alone (with scale_factor_offsets
+    and masking as there, which need it), through Context.encode_signals_measured."""
     options = dict(options or {})
     title = options.pop('title', 'encoded by carta1')
     titles = [title] * len(items) if isinstance(title, str) else list(title)
     if len(titles) != len(items):
         raise ValueError('title must be one string or one per item')
+    if not measured_allocation and (scale_factor_offsets is not None or masking is not None):
+        raise ValueError('scale_factor_offsets and masking need measured_allocation')
     signals, counts = items_to_signals(items)
-    units = _ctx(ctx).encode_signals(signals, EncoderOptions(options))
+    if measured_allocation:
+        units = _ctx(ctx).encode_signals_measured(signals, options=EncoderOptions(options), scale_factor_offsets=scale_factor_offsets,
+                                                  masking=masking)[0]
+    else:
+        units = _ctx(ctx).encode_signals(signals, EncoderOptions(options))
     return [aea_header(t, u.shape[0], nch) + u.tobytes() for t, u, nch in zip(titles, interleave_item_units(units, counts), counts)]
 
 

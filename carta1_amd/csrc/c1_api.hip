@@ -406,6 +406,7 @@ constexpr int64_t kSpecMinUnits = 64;                  // default mode: calls be
 constexpr int kListHead = 8;                           // uint32 counters in front of the speculative path's lists
 constexpr int64_t kMaxModesBatchFrames = (int64_t)1 << 22;   // c1_encode_modes_batch: one staging buffer for the whole call
 constexpr int64_t kMaxChunkFrames = (int64_t)1 << 27;   // x 2 channels = 2^28 units per chunk < 2^29
+constexpr bool kSignalStartsFused = false;             // c1_encode_signals_measured*'s default route; C1_SIGNAL_STARTS overrides
 
 struct Timing {
   hipEvent_t start, stop;
@@ -487,6 +488,7 @@ struct c1_ctx {
   int64_t chunk_frames = 0;
   bool pipeline = true;
   int measured_wide = -1;                         // C1_MEASURED_WIDE: -1 unset (the threshold decides), 0 never, 1 always
+  bool signal_starts_fused = false;               // C1_SIGNAL_STARTS: the route of c1_encode_signals_measured*'s signal starts
   hipStream_t s_ana = nullptr, s_rest = nullptr;  // internal streams of the two pipeline halves
   hipEvent_t ev_in = nullptr, ev_ana[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_end[2] = {nullptr, nullptr};
   // profiling
@@ -1452,6 +1454,10 @@ int c1_ctx_create(int device, void *hip_stream, c1_ctx **out) {
   // outputs are the same bits either way
   const char *mw = getenv("C1_MEASURED_WIDE");
   ctx->measured_wide = mw ? (atoi(mw) != 0 ? 1 : 0) : -1;
+  // C1_SIGNAL_STARTS: how c1_encode_signals_measured* redoes the first two frames of every signal: 0 in two passes of the row
+  // kernel, 1 in one pass of k_encode_signal_starts; unset: kSignalStartsFused.  The outputs are the same bits
+  const char *ss = getenv("C1_SIGNAL_STARTS");
+  ctx->signal_starts_fused = ss ? atoi(ss) != 0 : kSignalStartsFused;
   const char *env = getenv("C1_CHUNK_FRAMES");
   ctx->chunk_frames = env ? atoll(env) : (int64_t)1 << 24;   // chunk_for_call() cuts it down to what fits
   if (ctx->chunk_frames < 16) ctx->chunk_frames = 16;
@@ -4898,8 +4904,63 @@ int upload_rows(c1_ctx *ctx, uint32_t *dst, size_t words) {
 // One fix-up pass of the encoder: `rows` frames, row r the PCM frame src[r] from state in[in_rows[r]] (in_rows null: in[r];
 // bcast: in[0]) to state out[out_rows[r]] (null: out[r]; out null: no state), through the from-state kernel into the
 // workspace, the encoder's own allocation and packing on it, and the units scattered to units[src[r]].  W rows at a time.
+// mc (c1_encode_signals_measured*): the measured allocation of the rows runs between their allocation and packing, its outputs
+// go to the rows' staging `st` and one scatter launch moves unit and outputs to their places; units (and row_units) may then be
+// null: nothing is packed
+struct RowStage {            // per-row staging of a measured signals call, carved from c1_ctx::d_sig
+  uint8_t *taken;
+  int8_t *shifts;
+  double *distortion, *energy, *weights;
+};
+// allocation, the measured step (mc non-null), packing and the move of m workspace rows to units dst_rows[0 .. m) of the call
+void rows_chain(c1_ctx *ctx, int64_t m, const uint32_t *dst_rows, uint8_t *units, uint8_t *row_units, const MeasuredCall *mc,
+                const RowStage *st) {
+  C1EncodeLaunch L;
+  memset(&L, 0, sizeof L);
+  L.channels = 1;
+  L.frames = m;
+  L.tables = ctx->d_tables;
+  L.opts = ctx->d_opts;
+  L.coefs = ctx->d_coefs[0];
+  L.side = ctx->d_side[0];
+  L.alloc = ctx->d_alloc[0];
+  L.cand = ctx->d_cand[0];
+  L.work_count = ctx->d_work[0];
+  L.work_list = ctx->d_work[0] + 4;
+  L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
+  L.units = row_units;
+  { ScopedTiming t(ctx, K_ALLOCATE); c1k_launch_allocate(L, ctx->stream); }
+  if (mc) {
+    MeasuredCall sm = *mc;                                     // the same definition, the outputs at the rows' staging
+    sm.taken = mc->taken ? st->taken : nullptr;
+    sm.shifts = mc->shifts ? st->shifts : nullptr;
+    sm.distortion = mc->distortion ? st->distortion : nullptr;
+    sm.energy = mc->energy ? st->energy : nullptr;
+    sm.weights = mc->weights ? st->weights : nullptr;
+    launch_measured(ctx, L, false, &sm, 0, ctx->stream);       // the side records carry the rows' mode bytes
+  }
+  if (row_units) { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
+  ScopedTiming t(ctx, K_SIGNAL_STARTS);
+  if (!mc) {
+    c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(units), dst_rows, reinterpret_cast<const uint32_t *>(row_units), nullptr, 0, m, kUnitDwords, ctx->stream);
+    return;
+  }
+  C1ScatterRowsLaunch X;
+  memset(&X, 0, sizeof X);
+  X.dst_rows = dst_rows;
+  X.n = m;
+  if (row_units) { X.units_src = reinterpret_cast<const uint32_t *>(row_units); X.units_dst = reinterpret_cast<uint32_t *>(units); }
+  if (mc->taken) { X.taken_src = st->taken; X.taken_dst = mc->taken; }
+  if (mc->shifts) { X.shifts_src = reinterpret_cast<const uint32_t *>(st->shifts); X.shifts_dst = reinterpret_cast<uint32_t *>(mc->shifts); }
+  if (mc->distortion) { X.distortion_src = reinterpret_cast<const uint32_t *>(st->distortion); X.distortion_dst = reinterpret_cast<uint32_t *>(mc->distortion); }
+  if (mc->energy) { X.energy_src = reinterpret_cast<const uint32_t *>(st->energy); X.energy_dst = reinterpret_cast<uint32_t *>(mc->energy); }
+  if (mc->weights) { X.weights_src = reinterpret_cast<const uint32_t *>(st->weights); X.weights_dst = reinterpret_cast<uint32_t *>(mc->weights); }
+  c1k_launch_scatter_signal_rows(X, ctx->stream);
+}
+
 int encode_rows_pass(c1_ctx *ctx, const float *pcm, const uint32_t *src, const float *in, const uint32_t *in_rows, bool bcast,
-                     float *out, const uint32_t *out_rows, int64_t rows, int64_t W, uint8_t *units, uint8_t *row_units) {
+                     float *out, const uint32_t *out_rows, int64_t rows, int64_t W, uint8_t *units, uint8_t *row_units,
+                     const MeasuredCall *mc = nullptr, const RowStage *st = nullptr) {
   for (int64_t r0 = 0; r0 < rows; r0 += W) {
     const int64_t m = std::min(W, rows - r0);
     C1EncStateLaunch K;
@@ -4918,24 +4979,7 @@ int encode_rows_pass(c1_ctx *ctx, const float *pcm, const uint32_t *src, const f
     K.side = ctx->d_side[0];
     K.detect = -1;
     { ScopedTiming t(ctx, K_SIGNAL_STARTS); c1k_launch_encode_rows(K, ctx->stream); }
-    C1EncodeLaunch L;
-    memset(&L, 0, sizeof L);
-    L.channels = 1;
-    L.frames = m;
-    L.tables = ctx->d_tables;
-    L.opts = ctx->d_opts;
-    L.coefs = ctx->d_coefs[0];
-    L.side = ctx->d_side[0];
-    L.alloc = ctx->d_alloc[0];
-    L.cand = ctx->d_cand[0];
-    L.work_count = ctx->d_work[0];
-    L.work_list = ctx->d_work[0] + 4;
-    L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
-    L.units = row_units;
-    { ScopedTiming t(ctx, K_ALLOCATE); c1k_launch_allocate(L, ctx->stream); }
-    { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
-    { ScopedTiming t(ctx, K_SIGNAL_STARTS);
-      c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(units), src + r0, reinterpret_cast<const uint32_t *>(row_units), nullptr, 0, m, kUnitDwords, ctx->stream); }
+    rows_chain(ctx, m, src + r0, units, row_units, mc, st);
   }
   return C1_OK;
 }
@@ -5028,6 +5072,223 @@ int encode_signals_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const float 
     // empty signals: the pool passes through
     if (copy_empty)
       c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(out), dz_sig, reinterpret_cast<const uint32_t *>(in ? in : zero), in ? dz_sig : nullptr,
+                           in ? 0 : 1, nZ, kEncStateFloats, ctx->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
+// a mode byte in blockSelectorStage's domain, as the kernels bring it there, and its number 0 .. 7 among the domain's eight
+int mode_byte_in_domain(int b) { return (b & 0x02) | (b & 0x08) | ((b & 0x30) == 0x30 ? 0x30 : 0); }
+int mode_byte_number(int b) { return ((b >> 1) & 1) | (((b >> 3) & 1) << 1) | ((b & 0x30) == 0x30 ? 4 : 0); }
+
+// encode_signals_impl with the measured allocation: device pointers but frame_offsets; arguments checked by the
+// callers.  d_modes: one byte per frame of the concatenation (device memory) or null; h_modes: the same bytes in host memory
+// when the caller has them (the two-pass route sorts its rows by them).  mc: the call's definition and outputs, over the units
+// of the concatenation.  units may be null
+int encode_signals_measured_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const float *pcm, const float *in, const c1_encode_options *opts,
+                                 const uint8_t *d_modes, const uint8_t *h_modes, const MeasuredCall *mc, uint8_t *units, float *out) {
+  int rc;
+  TimingScope scope(ctx);
+  const int64_t total = off[n];
+  const bool fused = ctx->signal_starts_fused;
+  // with given modes neither threshold nor fixed modes are read
+  c1_encode_options base = *opts;
+  if (d_modes) {
+    base.transient_threshold = 1.0;
+    base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  }
+  const bool detect = !d_modes && opts->fixed_block_modes[0] < 0;
+  std::vector<uint8_t> fetched;
+  if (d_modes && !fused && !h_modes && total > 0) {            // the row kernel takes one triple per launch: the bytes decide the launches
+    fetched.resize((size_t)total);
+    HIP_TRY(hipMemcpyAsync(fetched.data(), d_modes, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    h_modes = fetched.data();
+  }
+  // 1. the whole concatenation as one mono stream, as c1_encode_measured_*_device runs it: every row but those of the first two
+  //    frames of a signal is final
+  const float *chan[1] = {pcm};
+  if ((rc = encode_device_impl(ctx, chan, 1, total, 0, &base, units, nullptr, nullptr, nullptr, nullptr, false, total > 0 ? d_modes : nullptr,
+                               nullptr, nullptr, nullptr, total > 0 ? mc : nullptr))) return rc;
+  int64_t nA = 0, nB = 0, nC = 0, nZ = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t len = off[i + 1] - off[i];
+    nA += len >= 1; nB += len >= 2; nC += len >= 3; nZ += len == 0;
+  }
+  const bool copy_empty = out && out != in && nZ > 0;
+  if (nA == 0 && !copy_empty) return C1_OK;
+  if (!out) nC = 0;
+  const int64_t nR = nA + nB;
+  // index lists.  Two passes: encode_signals_impl's (A, B, C, Z), with A and B sorted by the mode byte of their frame when modes
+  // are given.  Fused: per signal of >= 1 frame its first frame, index, frame count and first row; per row its unit; C and Z
+  const size_t words = fused ? (size_t)(4 * nA + nR + 2 * nC + nZ) : (size_t)(2 * nA + 3 * nB + 3 * nC + nZ);
+  uint32_t *h;
+  if ((rc = rows_image(ctx, words, &h))) return rc;
+  uint32_t *a_src = h, *a_sig = a_src + nA;
+  uint32_t *a_cnt = nullptr, *a_first = nullptr, *row_dst = nullptr, *b_src = nullptr, *b_sig = nullptr, *b_row = nullptr, *c_src0, *c_src1 = nullptr, *c_sig, *z_sig;
+  if (fused) { a_cnt = a_sig + nA; a_first = a_cnt + nA; row_dst = a_first + nA; c_src0 = row_dst + nR; c_sig = c_src0 + nC; z_sig = c_sig + nC; }
+  else { b_src = a_sig + nA; b_sig = b_src + nB; b_row = b_sig + nB; c_src0 = b_row + nB; c_src1 = c_src0 + nC; c_sig = c_src1 + nC; z_sig = c_sig + nC; }
+  int64_t a_group[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, b_group[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // rows of A / B before mode byte number g
+  const bool by_mode = !fused && d_modes;
+  if (by_mode) {
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t f0 = off[i], len = off[i + 1] - f0;
+      if (len >= 1) a_group[mode_byte_number(h_modes[f0]) + 1]++;
+      if (len >= 2) b_group[mode_byte_number(h_modes[f0 + 1]) + 1]++;
+    }
+    for (int g = 0; g < 8; g++) { a_group[g + 1] += a_group[g]; b_group[g + 1] += b_group[g]; }
+  }
+  {
+    int64_t a = 0, b = 0, c = 0, z = 0, row = 0;
+    int64_t a_at[8], b_at[8];
+    for (int g = 0; g < 8; g++) { a_at[g] = a_group[g]; b_at[g] = b_group[g]; }
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t f0 = off[i], len = off[i + 1] - f0;
+      if (len == 0) { z_sig[z++] = (uint32_t)i; continue; }
+      if (len >= 3 && out) { c_src0[c] = (uint32_t)(f0 + len - 2); if (c_src1) c_src1[c] = (uint32_t)(f0 + len - 1); c_sig[c] = (uint32_t)i; c++; }
+      if (fused) {
+        a_src[a] = (uint32_t)f0; a_sig[a] = (uint32_t)i; a_cnt[a] = len >= 2 ? 2u : 1u; a_first[a] = (uint32_t)row;
+        row_dst[row++] = (uint32_t)f0;
+        if (len >= 2) row_dst[row++] = (uint32_t)(f0 + 1);
+        a++;
+        continue;
+      }
+      const int64_t ai = by_mode ? a_at[mode_byte_number(h_modes[f0])]++ : a++;
+      a_src[ai] = (uint32_t)f0; a_sig[ai] = (uint32_t)i;
+      if (len >= 2) {
+        const int64_t bi = by_mode ? b_at[mode_byte_number(h_modes[f0 + 1])]++ : b++;
+        b_src[bi] = (uint32_t)(f0 + 1); b_sig[bi] = (uint32_t)i; b_row[bi] = (uint32_t)ai;
+      }
+    }
+  }
+  int64_t W = 0;
+  if (nA > 0) {
+    if ((rc = join_tail(ctx))) return rc;
+    const int64_t rows = fused ? nR : nA;
+    W = std::max<int64_t>(2, std::min(rows, chunk_for_call(ctx, rows, 1, false)));
+    if ((rc = ensure_workspace(ctx, W))) return rc;
+  }
+  SigCarve cv;
+  const size_t o_zero = cv.take(sizeof(c1_enc_state)), o_lists = cv.take(words * sizeof(uint32_t)),
+               o_tmp = cv.take((out || fused) ? 0 : (size_t)nA * sizeof(c1_enc_state)), o_tmp2 = cv.take(fused ? 0 : (size_t)nC * sizeof(c1_enc_state)),
+               o_units = cv.take((size_t)W * C1_UNIT_BYTES), o_taken = cv.take((size_t)W), o_shifts = cv.take((size_t)W * 52),
+               o_dist = cv.take((size_t)W * 2 * sizeof(double)), o_energy = cv.take((size_t)W * sizeof(double)),
+               o_weights = cv.take(mc->weights ? (size_t)W * 52 * sizeof(double) : 0);
+  if ((rc = ensure_sig(ctx, cv.bytes))) return rc;
+  uint8_t *base_p = static_cast<uint8_t *>(ctx->d_sig);
+  float *zero = reinterpret_cast<float *>(base_p + o_zero), *tmp = reinterpret_cast<float *>(base_p + o_tmp), *tmp2 = reinterpret_cast<float *>(base_p + o_tmp2);
+  const uint32_t *d = reinterpret_cast<uint32_t *>(base_p + o_lists);
+  const RowStage st = {base_p + o_taken, reinterpret_cast<int8_t *>(base_p + o_shifts), reinterpret_cast<double *>(base_p + o_dist),
+                       reinterpret_cast<double *>(base_p + o_energy), reinterpret_cast<double *>(base_p + o_weights)};
+  uint8_t *row_units = units ? base_p + o_units : nullptr;
+  HIP_TRY(hipMemsetAsync(zero, 0, sizeof(c1_enc_state), ctx->stream));
+  if ((rc = upload_rows(ctx, const_cast<uint32_t *>(d), words))) return rc;
+  auto dev = [&](const uint32_t *host_list) { return host_list ? d + (host_list - h) : nullptr; };
+  if (fused) {
+    // 2. frames 0 and 1 of every signal in one pass: the pool between them stays in the kernel; a chunk of W rows never splits a pair
+    for (int64_t a0 = 0; a0 < nA;) {
+      const int64_t r0 = a_first[a0];
+      int64_t a1 = a0, m = 0;
+      while (a1 < nA && m + a_cnt[a1] <= W) m += a_cnt[a1++];
+      C1SignalStartsLaunch K;
+      memset(&K, 0, sizeof K);
+      K.pcm = pcm;
+      K.src_rows = dev(a_src) + a0;
+      K.in = in ? in : zero;
+      K.in_rows = in ? dev(a_sig) + a0 : nullptr;
+      K.in_broadcast = in ? 0 : 1;
+      K.out = out;
+      K.out_rows = dev(a_sig) + a0;
+      K.counts = dev(a_cnt) + a0;
+      K.first_rows = dev(a_first) + a0;
+      K.row_base = r0;
+      K.n = a1 - a0;
+      K.tables = ctx->d_tables;
+      K.opts = ctx->d_opts;
+      K.coefs = ctx->d_coefs[0];
+      K.side = ctx->d_side[0];
+      K.detect = -1;
+      K.modes = d_modes;
+      { ScopedTiming t(ctx, K_SIGNAL_STARTS); c1k_launch_signal_starts(K, ctx->stream); }
+      rows_chain(ctx, m, dev(row_dst) + r0, units, row_units, mc, &st);
+      a0 = a1;
+    }
+  } else {
+    // the pools in flight live in `out` at their signal's index, or in scratch at their row of list A when out is NULL
+    float *S = out ? out : tmp;
+    for (int pass = 0; pass < 2; pass++) {
+      // 2. frame 0 of every signal from in[i] (a fresh pool when in is NULL); 3. frame 1 from the pool step 2 left, in place.
+      //    With given modes once per mode byte present, over that byte's rows, under that byte's fixed modes
+      for (int g = 0; g < (by_mode ? 8 : 1); g++) {
+        const int64_t g0 = by_mode ? (pass ? b_group[g] : a_group[g]) : 0;
+        const int64_t rows = by_mode ? (pass ? b_group[g + 1] : a_group[g + 1]) - g0 : (pass ? nB : nA);
+        if (rows == 0) continue;
+        if (by_mode) {
+          c1_encode_options one = *opts;
+          one.fixed_block_modes[0] = (g & 1) ? 2 : 0; one.fixed_block_modes[1] = (g & 2) ? 2 : 0; one.fixed_block_modes[2] = (g & 4) ? 3 : 0;
+          if ((rc = upload_opts(ctx, &one))) return rc;
+        }
+        if (pass == 0) {
+          const bool keep = out || nB;
+          float *o = !keep ? nullptr : (out ? out : tmp + g0 * kEncStateFloats);
+          rc = encode_rows_pass(ctx, pcm, dev(a_src) + g0, in ? in : zero, in ? dev(a_sig) + g0 : nullptr, !in, o, out ? dev(a_sig) + g0 : nullptr, rows, W,
+                                units, row_units, mc, &st);
+        } else {
+          const uint32_t *at = (out ? dev(b_sig) : dev(b_row)) + g0;
+          rc = encode_rows_pass(ctx, pcm, dev(b_src) + g0, S, at, false, S, at, rows, W, units, row_units, mc, &st);
+        }
+        if (rc) return rc;
+      }
+    }
+  }
+  if (out) {
+    // 4. signals of three frames and more: the pool after the last frame is a function of the last two frames (state only, from
+    //    zeros: c1_enc_stream_get_state does the same); without detection transient_mags keeps what steps 2 and 3 passed through
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    if (fused) {
+      C1SignalStartsLaunch K;
+      memset(&K, 0, sizeof K);
+      K.pcm = pcm;
+      K.src_rows = dev(c_src0);
+      K.count_all = 2;
+      K.in = zero;
+      K.in_broadcast = 1;
+      K.out = out;
+      K.out_rows = dev(c_sig);
+      K.n = nC;
+      K.tables = ctx->d_tables;
+      K.opts = ctx->d_opts;
+      K.state_only = 1;
+      K.detect = detect ? 1 : 0;
+      K.keep_mags = detect ? 0 : 1;
+      c1k_launch_signal_starts(K, ctx->stream);
+    } else {
+      C1EncStateLaunch K;
+      memset(&K, 0, sizeof K);
+      K.pcm = pcm;
+      K.src_rows = dev(c_src0);
+      K.in = zero;
+      K.in_broadcast = 1;
+      K.out = tmp2;
+      K.n = nC;
+      K.tables = ctx->d_tables;
+      K.opts = ctx->d_opts;
+      K.state_only = 1;
+      K.detect = 0;                                          // the zero pool's magnitudes pass through: every float of tmp2 is written
+      c1k_launch_encode_rows(K, ctx->stream);
+      K.src_rows = dev(c_src1);
+      K.in = tmp2;
+      K.in_broadcast = 0;
+      K.out = out;
+      K.out_rows = dev(c_sig);
+      K.detect = detect ? 1 : 0;
+      K.keep_mags = detect ? 0 : 1;
+      c1k_launch_encode_rows(K, ctx->stream);
+    }
+    // empty signals: the pool passes through
+    if (copy_empty)
+      c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(out), dev(z_sig), reinterpret_cast<const uint32_t *>(in ? in : zero), in ? dev(z_sig) : nullptr,
                            in ? 0 : 1, nZ, kEncStateFloats, ctx->stream);
   }
   HIP_TRY(hipGetLastError());
@@ -5163,6 +5424,122 @@ int c1_encode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, cons
   if (T) HIP_TRY(hipMemcpyAsync(units, du, T * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
+namespace {
+// what the measured arguments of c1_encode_signals_measured* decide alone, as c1_enc_stream_push_measured judges them
+int check_signals_measured_args(const char *what, const c1_encode_options *opts, bool have_modes, const int8_t *sf_offsets, int n_offsets,
+                                const double *mask_floor, const double *mask_spread, const double *weights) {
+  int rc;
+  if (mask_spread && !mask_floor) return fail(C1_ERR_ARG, "%s: mask_spread is given without mask_floor", what);
+  if (weights && !mask_floor) return fail(C1_ERR_ARG, "%s: weights is given without mask_floor", what);
+  if (!sf_offsets && n_offsets != 0) return fail(C1_ERR_ARG, "%s: n_offsets = %d, but sf_offsets is NULL", what, n_offsets);
+  if (sf_offsets && (rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if (mask_floor && (rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  return check_measured_opts(what, opts, !have_modes);
+}
+}  // namespace
+
+int c1_encode_signals_measured_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                                      const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                                      const double *mask_floor, const double *mask_spread, uint8_t *units, c1_enc_state *out,
+                                      uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights) {
+  const char *const what = "c1_encode_signals_measured_device";
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_signals_measured_args(what, opts, modes != nullptr, sf_offsets, n_offsets, mask_floor, mask_spread, weights))) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets(what, n, frame_offsets, kMaxSignalFrames, &total))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy && !weights) return fail(C1_ERR_ARG, "%s: units, taken, shifts, distortion, energy and weights are all NULL", what);
+  if (total > 0 && !pcm) return fail(C1_ERR_ARG, "%s: pcm is NULL", what);
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "%s: pcm must be 16-byte aligned on the device", what);
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)units | (uintptr_t)shifts) & 3) return fail(C1_ERR_ARG, "%s: units, states and shifts must be 4-byte aligned on the device", what);
+  if (((uintptr_t)distortion | (uintptr_t)energy | (uintptr_t)weights) & 7) return fail(C1_ERR_ARG, "%s: distortion, energy and weights must be 8-byte aligned on the device", what);
+  int8_t offs[C1_MAX_SF_OFFSETS];                              // the caller's array may change while the call runs
+  if (sf_offsets) memcpy(offs, sf_offsets, (size_t)n_offsets);
+  static const int8_t kOwnIndex[1] = {0};                      // tables without offsets: the masked call with the single offset 0
+  MeasuredCall mc = {taken, distortion, energy};
+  if (sf_offsets || mask_floor) {
+    mc.sf_offsets = sf_offsets ? offs : kOwnIndex;
+    mc.n_offsets = sf_offsets ? n_offsets : 1;
+    mc.shifts = shifts;
+  } else if (shifts && total > 0) {
+    HIP_TRY(hipMemsetAsync(shifts, 0, (size_t)total * 52, ctx->stream));   // c1_encode_measured_*: no index moves
+  }
+  if (mask_floor) {
+    if (total > 0 && (rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+    mc.mask = ctx->d_mask;
+    mc.has_spread = mask_spread != nullptr;
+    mc.weights = weights;
+  }
+  return encode_signals_measured_impl(ctx, n, frame_offsets, pcm, reinterpret_cast<const float *>(in), opts, total > 0 ? modes : nullptr, nullptr, &mc,
+                                      units, reinterpret_cast<float *>(out));
+}
+
+int c1_encode_signals_measured(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                               const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                               const double *mask_floor, const double *mask_spread, uint8_t *units, c1_enc_state *out,
+                               uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_encode_signals_measured";
+  int rc;
+  if ((rc = check_signals_measured_args(what, opts, modes != nullptr, sf_offsets, n_offsets, mask_floor, mask_spread, weights))) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets(what, n, frame_offsets, kMaxSignalFramesHost, &total))) return rc;
+  if (!units && !taken && !shifts && !distortion && !energy && !weights) return fail(C1_ERR_ARG, "%s: units, taken, shifts, distortion, energy and weights are all NULL", what);
+  if (total > 0 && !pcm) return fail(C1_ERR_ARG, "%s: pcm is NULL", what);
+  if (modes && total > 0 && (rc = check_mode_bytes(what, modes, total, 1))) return rc;
+  if (in && (rc = check_states_finite(what, "signal", in, n, kEncStateFloats, kEncStateFields, 5))) return rc;
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (n == 0) return C1_OK;
+  // from here on only the device can fail
+  DeviceScratch ds;
+  float *dp, *dst = nullptr; uint8_t *du = nullptr, *dm = nullptr, *d_taken = nullptr; int8_t *d_shifts = nullptr;
+  double *d_dist = nullptr, *d_energy = nullptr, *d_weights = nullptr;
+  const size_t T = (size_t)total, N = (size_t)n;
+  if ((rc = ds.alloc(&dp, T * 512))) return rc;
+  if (units && (rc = ds.alloc(&du, T * C1_UNIT_BYTES))) return rc;
+  if (modes && T && (rc = ds.alloc(&dm, T))) return rc;
+  if ((in || out) && (rc = ds.alloc(&dst, N * kEncStateFloats))) return rc;
+  if (taken && (rc = ds.alloc(&d_taken, T))) return rc;
+  if (shifts && (sf_offsets || mask_floor) && (rc = ds.alloc(&d_shifts, T * 52))) return rc;
+  if (distortion && (rc = ds.alloc(&d_dist, T * 2))) return rc;
+  if (energy && (rc = ds.alloc(&d_energy, T))) return rc;
+  if (weights && (rc = ds.alloc(&d_weights, T * 52))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(dp, pcm, T * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (dm) HIP_TRY(hipMemcpyAsync(dm, modes, T, hipMemcpyHostToDevice, ctx->stream));
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_enc_state), hipMemcpyHostToDevice, ctx->stream));
+  static const int8_t kOwnIndex[1] = {0};                      // tables without offsets: the masked call with the single offset 0
+  MeasuredCall mc = {d_taken, d_dist, d_energy};
+  if (sf_offsets || mask_floor) {
+    mc.sf_offsets = sf_offsets ? sf_offsets : kOwnIndex;
+    mc.n_offsets = sf_offsets ? n_offsets : 1;
+    mc.shifts = d_shifts;
+  }
+  if (mask_floor) {
+    if (T && (rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+    mc.mask = ctx->d_mask;
+    mc.has_spread = mask_spread != nullptr;
+    mc.weights = d_weights;
+  }
+  if ((rc = encode_signals_measured_impl(ctx, n, frame_offsets, dp, in ? dst : nullptr, opts, dm, dm ? modes : nullptr, &mc, du, out ? dst : nullptr))) return rc;
+  if (units && T) HIP_TRY(hipMemcpyAsync(units, du, T * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_taken && T) HIP_TRY(hipMemcpyAsync(taken, d_taken, T, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_shifts && T) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, T * 52, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_dist && T) HIP_TRY(hipMemcpyAsync(distortion, d_dist, T * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (d_energy && T) HIP_TRY(hipMemcpyAsync(energy, d_energy, T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (d_weights && T) HIP_TRY(hipMemcpyAsync(weights, d_weights, T * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (shifts && !d_shifts && T) memset(shifts, 0, T * 52);     // c1_encode_measured_*: no index moves
   return C1_OK;
 }
 

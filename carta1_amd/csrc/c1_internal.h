@@ -222,6 +222,41 @@ struct C1DecStateLaunch {
   int in_broadcast;
 };
 
+// The first frames of many signals in one pass (c1_k_signal_starts.hip): wave r walks counts[r] (1 or 2; null: count_all)
+// consecutive PCM frames from pcm + src_rows[r] * 512 on, starting from the state in[in_rows[r]], and writes the coefficients
+// and side record of frame f to workspace row first_rows[r] - row_base + f and the state after the last frame to
+// out[out_rows[r]] (out null: no state).  Null lists, in_broadcast, detect, state_only and keep_mags as in C1EncStateLaunch;
+// state_only reads no first_rows.  modes (one byte per frame of pcm, device memory, any value: brought into blockSelectorStage's
+// domain): frame src_rows[r] + f takes its block modes from its byte, the detector does not run and transient_mags pass through
+struct C1SignalStartsLaunch {
+  const float *pcm;      // 16-byte aligned
+  const float *in;
+  float *out;
+  int64_t n;
+  const C1DevTables *tables;
+  const C1DevEncOpts *opts;
+  float *coefs;
+  uint8_t *side;
+  int detect, state_only;
+  const uint32_t *src_rows, *in_rows, *out_rows, *counts, *first_rows;
+  int64_t row_base;
+  int in_broadcast, keep_mags, count_all;
+  const uint8_t *modes;
+};
+// The rows of a signals call to their places (k_scatter_signal_rows): row r of every *_src plane (row-major staging; 53 dwords of a
+// sound unit, one taken byte, 13 dwords of shifts, 4 of distortion, 2 of energy, 104 of weights) to unit dst_rows[r] of the plane
+// *_dst.  A null *_dst plane is not moved; the dword planes are 4-byte aligned
+struct C1ScatterRowsLaunch {
+  const uint32_t *dst_rows;
+  int64_t n;
+  const uint32_t *units_src; uint32_t *units_dst;
+  const uint8_t *taken_src; uint8_t *taken_dst;
+  const uint32_t *shifts_src; uint32_t *shifts_dst;
+  const uint32_t *distortion_src; uint32_t *distortion_dst;
+  const uint32_t *energy_src; uint32_t *energy_dst;
+  const uint32_t *weights_src; uint32_t *weights_dst;
+};
+
 // Run length of the frame-walking kernels: consecutive frames of one channel a wave walks, carrying the filter state
 // (one extra warm-up frame per run).  Measured on MI355X (1 M stereo frames, A/B in one session): 64-frame runs beat
 // runs sized to fill the wave slots exactly once (205 frames: every wave then finishes at the same moment, and the
@@ -440,6 +475,9 @@ void c1k_launch_decode_rows(const C1DecStateLaunch &L, hipStream_t stream);
 // src row 0.  Rows of one launch must not overlap each other
 void c1k_launch_copy_rows(uint32_t *dst, const uint32_t *dst_rows, const uint32_t *src, const uint32_t *src_rows, int src_broadcast,
                           int64_t n, int dwords, hipStream_t stream);
+// the first one or two frames of n signals in one pass, and the rows of a signals call to their places (c1_k_signal_starts.hip)
+void c1k_launch_signal_starts(const C1SignalStartsLaunch &L, hipStream_t stream);
+void c1k_launch_scatter_signal_rows(const C1ScatterRowsLaunch &L, hipStream_t stream);
 // performFFT's magnitudes of `rows` stored band rows (512 floats each) into the transient_mags of states[0 .. rows)
 void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_t rows, float *states, hipStream_t stream);
 // kind_mask: bit k = fill the 512-frame segments with (segment & 3) == k (15 = all)

@@ -747,6 +747,39 @@ napi_value EncodeSignals(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encodeSignalsMeasured(ctx, Float32Array pcm, Float64Array frameOffsets, options, Int8Array offsets | null, Float64Array floor |
+// null, Float64Array spread | null) -> Uint8Array(frames * 212): encodeSignals with the measured allocation of encodeMeasured
+// (offsets and tables null), encodeMeasuredSf (offsets) or encodeMeasuredMasked (tables; without offsets the single offset 0),
+// every signal from a fresh pool: c1_encode_signals_measured
+napi_value EncodeSignalsMeasured(napi_env env, napi_callback_info info) {
+  napi_value argv[7];
+  if (!get_args(env, info, 7, argv)) return nullptr;
+  c1_ctx *ctx;
+  void *d;
+  size_t samples, n[3] = {0, 0, 0};
+  void *data[3] = {nullptr, nullptr, nullptr};
+  std::vector<int64_t> off;
+  c1_encode_options o;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &samples) ||
+      !get_frame_offsets(env, argv[2], &off) || !get_options(env, argv[3], &o)) return nullptr;
+  const napi_typedarray_type kinds[3] = {napi_int8_array, napi_float64_array, napi_float64_array};
+  for (int k = 0; k < 3; k++) {
+    napi_valuetype t;
+    NAPI_OK(napi_typeof(env, argv[4 + k], &t));
+    if (t != napi_null && t != napi_undefined && !get_typed(env, argv[4 + k], kinds[k], &data[k], &n[k])) return nullptr;
+  }
+  if ((data[1] && n[1] != 52) || (data[2] && n[2] != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (samples % 512 || (uint64_t)off.back() != samples / 512) { napi_throw_type_error(env, nullptr, "pcm must hold frameOffsets[n] frames of 512 samples"); return nullptr; }
+  if (n[0] > 64) n[0] = 64;                                     // the library's own check names the limit
+  uint8_t *units;
+  napi_value out = make_u8(env, (samples / 512) * C1_UNIT_BYTES, &units);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_encode_signals_measured(ctx, (int64_t)off.size() - 1, off.data(), static_cast<const float *>(d), nullptr, &o, nullptr,
+                                            static_cast<const int8_t *>(data[0]), data[0] ? (int)n[0] : 0, static_cast<const double *>(data[1]),
+                                            static_cast<const double *>(data[2]), units, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 // decodeSignals(ctx, Uint8Array units, Float64Array frameOffsets) -> Float32Array(frames * 512)
 napi_value DecodeSignals(napi_env env, napi_callback_info info) {
   napi_value argv[3];
@@ -1556,6 +1589,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeBatchAsync", nullptr, EncodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatchAsync", nullptr, DecodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeSignals", nullptr, EncodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeSignalsMeasured", nullptr, EncodeSignalsMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeSignals", nullptr, DecodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, checkScaleFactorOffsets, checkMasking } from '../native.js'
+import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, encodeSignalsMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -281,8 +281,29 @@ function imageBody(input) {
 
 // encodeAeaPcm for many items at once: every channel of every item is one signal of ONE native call (c1_encode_signals).
 // options.title: one string, or one per item.  Each image is byte for byte what encodeAeaPcm returns for that item alone.
+// options.measuredAllocation: true, with scaleFactorOffsets and masking as for encodeAeaPcm (they need it, TypeError): the
+// measured allocation of every item in the same one call (c1_encode_signals_measured).  blockModes, measuredModeCandidates and
+// the candidate searches of encodeAeaPcm are not supported for many items (TypeError)
 export async function encodeAeaPcmMany(items, options = {}) {
-  const { title = 'encoded by carta1', ...encoderValues } = options
+  const { title = 'encoded by carta1', measuredAllocation, scaleFactorOffsets, masking, ...encoderValues } = options
+  for (const name of ['blockModes', 'measuredModeCandidates', 'blockModeCandidates', 'allocationBiases', 'allocationBiasCandidates']) {
+    if (encoderValues[name] !== undefined && encoderValues[name] !== null) {
+      throw new TypeError(`${name} is not supported by encodeAeaPcmMany: encode the items one by one with encodeAeaPcm`)
+    }
+  }
+  if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
+    throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
+  }
+  const haveOffsets = scaleFactorOffsets !== undefined && scaleFactorOffsets !== null
+  if (haveOffsets) {
+    if (!measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
+    checkScaleFactorOffsets(scaleFactorOffsets)
+  }
+  const haveMasking = masking !== undefined && masking !== null && masking !== false
+  if (haveMasking) {
+    if (!measuredAllocation) throw new TypeError('masking needs measuredAllocation: true; no other path weighs its errors')
+    checkMasking(masking)
+  }
   const { signals, counts, frameOffsets } = itemsToSignals(items)
   const titles = Array.isArray(title) ? title : items.map(() => title)
   if (titles.length !== items.length || titles.some((t) => typeof t !== 'string')) {
@@ -290,8 +311,12 @@ export async function encodeAeaPcmMany(items, options = {}) {
   }
   const encoderOptions = new EncoderOptions(encoderValues)
   const total = frameOffsets[signals.length]
-  const units = total > 0 ? native().encodeSignals(context(), concatSignals(signals, frameOffsets), frameOffsets, encoderOptions.toNative())
-    : new Uint8Array(0)
+  let units = new Uint8Array(0)
+  if (total > 0 && measuredAllocation) {
+    units = encodeSignalsMeasured(concatSignals(signals, frameOffsets), frameOffsets, encoderOptions.toNative(), haveOffsets ? scaleFactorOffsets : null, haveMasking ? masking : null)
+  } else if (total > 0) {
+    units = native().encodeSignals(context(), concatSignals(signals, frameOffsets), frameOffsets, encoderOptions.toNative())
+  }
   let first = 0
   return counts.map((nch, k) => {
     const body = interleaveItemUnits(units, frameOffsets, first, nch)

@@ -168,6 +168,17 @@ export function encodeMeasured(channels, nativeOptions, modes = null, scaleFacto
   return native().encodeMeasuredSf(ctx, channels, haloFrames, nativeOptions, modes, checkScaleFactorOffsets(scaleFactorOffsets))
 }
 
+// c1_encode_signals_measured on the default context: encodeMeasured for n independent mono signals of any lengths in one call,
+// every signal from a fresh pool.  pcm: the signals' whole frames back to back; frameOffsets: Float64Array of n + 1 whole numbers,
+// signal i owns frames [frameOffsets[i], frameOffsets[i + 1]).  scaleFactorOffsets and masking as for encodeMeasured (with masking
+// and no offsets the offsets are [0]).  Returns the units, Uint8Array(frames * 212): signal i's are what encodeMeasured gives for
+// it alone.
+export function encodeSignalsMeasured(pcm, frameOffsets, nativeOptions, scaleFactorOffsets = null, masking = null, ctx = context()) {
+  const offsets = scaleFactorOffsets === null || scaleFactorOffsets === undefined ? null : checkScaleFactorOffsets(scaleFactorOffsets)
+  const tables = masking === null || masking === undefined ? null : checkMasking(masking)
+  return native().encodeSignalsMeasured(ctx, pcm, frameOffsets, nativeOptions, offsets, tables ? tables.floor : null, tables ? tables.spread : null)
+}
+
 // mode candidates as the mode-search calls take them (a Uint8Array or an array; an entry may be a triple [low, mid, high]) ->
 // Uint8Array of mode bytes; the library checks domain, count and repeats
 export function modeCandidateBytes(candidates) {

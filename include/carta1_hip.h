@@ -860,6 +860,43 @@ int c1_encode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, cons
 int c1_decode_signals(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const uint8_t *units, const c1_dec_state *in,
                       float *pcm, c1_dec_state *out);
 
+/* c1_encode_signals* with the measured allocation: layout, pools, in / out and empty signals as above; the
+ * measured arguments as in c1_enc_stream_push_measured -- tables and / or offsets select the masked, the sf or the plain
+ * definition, tables alone mean the single offset 0, shifts without offsets are zeros; mask_spread or weights without mask_floor,
+ * and n_offsets != 0 without offsets, are C1_ERR_ARG.  The per-unit outputs are indexed by frame of the concatenation: taken one
+ * entry per unit, shifts 52, distortion 2, energy 1, weights 52; each may be NULL, and so may units, as long as one output is
+ * asked for.  modes: NULL, or one byte per frame of the concatenation (the domain of c1_enc_stream_push_modes); every frame then
+ * behaves as under fixed block modes of its byte, the detector does not run, transient_mags passes from in[i] to out[i], and the
+ * threshold and fixed modes of opts are not read.
+ * Definition, by composition: the rows of signal i -- units and all five outputs, doubles as bit patterns -- are what
+ * c1_enc_stream_push_measured reports for signal i's frames in one push on a mono stream created with opts and restored to in[i]
+ * with c1_enc_stream_set_state (or fresh), under the same modes rows, offsets and tables, and out[i] is that stream's
+ * c1_enc_stream_get_state.  Nothing depends on the neighbouring signals, on chunking, on the speculation mode, or on which
+ * measuring kernel a launch takes.
+ * How: the concatenation runs once as c1_encode_measured_*_device runs it; the first two frames of every signal are computed
+ * again from in[i] with the measured step between allocation and packing, and one launch moves their rows to their places.
+ * C1_SIGNAL_STARTS (read when the context is created) selects how: 0 in two passes of the from-state kernel, frame 1 from the pool
+ * frame 0 left (with modes: once per mode byte present, at most eight times); 1 in one pass of a kernel that keeps that pool
+ * on the chip; unset: two passes (DESIGN.md 6r has the measurements behind that).  The bits are the same.
+ * Device form: device pointers but frame_offsets, sf_offsets, mask_floor and mask_spread, which are HOST pointers read before the
+ * call returns.  Asynchronous on the context's stream under the contracts of c1_encode_signals_device and
+ * c1_encode_measured_masked_device; with modes on the two-pass route the call reads the mode bytes back and waits for the
+ * stream.  Limits, the tighter of the two calls composed: n 0 .. 2^20, frame_offsets[n] 0 .. 2^27; pcm 16-byte aligned; units,
+ * states and shifts 4-byte, distortion, energy and weights 8-byte aligned.  States and mode bytes are not checked (a byte outside
+ * the domain is brought into it). */
+int c1_encode_signals_measured_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets /* host */, const float *pcm,
+                                      const c1_enc_state *in, const c1_encode_options *opts, const uint8_t *modes,
+                                      const int8_t *sf_offsets /* host */, int n_offsets, const double *mask_floor /* host */,
+                                      const double *mask_spread /* host */, uint8_t *units, c1_enc_state *out, uint8_t *taken,
+                                      int8_t *shifts, double *distortion, double *energy, double *weights);
+/* host pointers, synchronous; frame_offsets[n] 0 .. 2^22.  What the arguments alone decide is decided first and needs neither a
+ * context nor a device: the measured arguments, the options, frame_offsets, a mode byte outside the domain (naming its frame), a
+ * non-finite state entry (naming its signal and field), all outputs NULL.  A rejected call writes nothing. */
+int c1_encode_signals_measured(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                               const c1_encode_options *opts, const uint8_t *modes, const int8_t *sf_offsets, int n_offsets,
+                               const double *mask_floor, const double *mask_spread, uint8_t *units, c1_enc_state *out,
+                               uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights);
+
 /* Snapshot and restore of a stream: host pointers, `channels` entries.  get_state returns what the reference's pool would hold
  * after the same calls -- pushes, option changes and earlier restores; every field zero on a fresh stream.  transient_mags is
  * the spectrum of the last frame detection ran on: the last pushed frame while detection is on, the kept frame after a switch
