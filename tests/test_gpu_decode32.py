@@ -1,12 +1,15 @@
 """GPU: the opt-in binary32 decoder (c1_ctx_set_decode_precision(ctx, 1), k_decode<float>).  The task statement asks
 for decoded PCM within 1e-5 RMS of the reference where bit identity is not required; the binary32 decoder stays four
-orders of magnitude inside that on every stream here, and the default (exact) decoder is untouched."""
+orders of magnitude inside that on every stream here, and the default (exact) decoder is untouched.  Beside the absolute limits
+stand the relative ones of decode32_lib (4 x the ceilings of the oracle's binary32 twin): the stream within 24 u relative RMS and,
+on the reference streams, every frame within 72 u of the local peak, u = 2^-24; test_gpu_decode32_pinned.py holds the rest."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import decode32_lib as D
 import oracle_lib as O
 from test_gpu_parity import _patchwork
 
@@ -24,6 +27,14 @@ def ctx():
     c.close()
 
 
+def relative(got, ref, what, per_frame=True):
+    per, rel, loud = D.stream_metrics(got, ref)
+    assert loud == 0, (what, loud)
+    if per_frame:
+        assert per.max() <= D.GPU['frame_max'], (what, 'frame %d' % int(per.argmax()), float(per.max()))
+    assert rel <= D.GPU['stream_rms'], (what, rel)
+
+
 def rms(a, b):
     return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
 
@@ -39,6 +50,7 @@ def test_binary32_decode_of_the_reference_streams(ctx, name):
     for c in range(2):
         assert np.array_equal(exact[c].view(np.uint32), ref[c].view(np.uint32))      # the default decoder is still exact
         assert rms(got[c], ref[c]) < 1e-6 and np.abs(got[c] - ref[c]).max() < 1e-5, (rms(got[c], ref[c]), np.abs(got[c] - ref[c]).max())
+        relative(got[c], ref[c], (name, c))
         assert rms(got[c], ref[c]) > 0                                                # and this really is another arithmetic
 
 
@@ -55,4 +67,8 @@ def test_binary32_decode_of_a_patchwork_stream_every_mode_and_level(ctx):
     for c in range(2):
         scale = max(1.0, float(np.abs(ref[c]).max()))             # the patchwork reaches beyond full scale
         assert rms(got[c], ref[c]) < 1e-6 * scale
+        # the stream bound alone: the patchwork starts loud patches out of silence, where the frame before the onset holds only
+        # the synthesis filter's precursor (1e-8 of the patch) and its peak is no measure of the unit that caused it; the
+        # oracle's binary32 twin is 158 000 u from the oracle there by the per-frame measure, and 6.1 u by this one
+        relative(got[c], ref[c], ('patchwork', c), per_frame=False)
         assert np.array_equal(part[c], got[c][700 * 512:])         # chunk / halo invariance holds in binary32 too
