@@ -9,5 +9,6 @@ from .codec import (Context, EncoderOptions, encode_multi, decode_multi, encode_
                     EncoderStream, DecoderStream, aea_header, parse_aea_header, pinned_empty, encode_aea_pcm_many,
                     decode_aea_pcm_many, pack_block_modes, unpack_block_modes, check_block_modes, candidate_palette,
                     MAX_BIAS_PALETTE, mode_candidates, MAX_MODE_CANDIDATES, check_scale_factor_offsets, SCALE_FACTOR_OFFSETS,
-                    MAX_SCALE_FACTOR_OFFSETS, check_masking, MASKING_DEFAULT, check_measured_units, check_pcm_units, PCM_DELAY, PCM_SEGMENTS)
+                    MAX_SCALE_FACTOR_OFFSETS, check_masking, MASKING_DEFAULT, check_measured_units, check_pcm_units, PCM_DELAY, PCM_SEGMENTS,
+                    DECODE_EXACT, DECODE_BINARY32_BULK, DECODE_BINARY32)
 from .shard import shard_plan, encode_sharded, decode_sharded  # noqa: F401,E402

@@ -67,6 +67,8 @@ SIGNATURES = {
     'c1_ctx_kernel_ms': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     'c1_ctx_set_speculation': (C.c_int, [C.c_void_p, C.c_int]),
     'c1_ctx_set_decode_precision': (C.c_int, [C.c_void_p, C.c_int]),
+    'c1_ctx_set_decode_model': (C.c_int, [C.c_void_p, C.c_int]),
+    'c1_ctx_get_decode_model': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'c1_ctx_speculation_stats': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
     'c1_ctx_speculation_deferred': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     'c1_ctx_quantization_stats': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

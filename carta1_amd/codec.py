@@ -150,6 +150,19 @@ class Context:
         """False (default): bit-identical to the reference; True: binary32 arithmetic, PCM within rounding noise."""
         capi.check(capi.load().c1_ctx_set_decode_precision(self._h, 1 if binary32 else 0))
 
+    def set_decode_model(self, model):
+        """DECODE_EXACT (0, default): bit-identical to the reference on every entry.  DECODE_BINARY32_BULK (1): what
+        set_decode_precision(True) selects: the unit-walking kernel in binary32, everything decoded from frame fields or
+        from decoder states exact.  DECODE_BINARY32 (2): every decode entry of the context, DecoderStream included, in
+        that kernel's binary32 arithmetic: the same units give the same bits through any of them."""
+        capi.check(capi.load().c1_ctx_set_decode_model(self._h, int(model)))
+
+    @property
+    def decode_model(self):
+        m = C.c_int(0)
+        capi.check(capi.load().c1_ctx_get_decode_model(self._h, C.byref(m)))
+        return m.value
+
     def speculation_stats(self, reset=False):
         """(units encoded through the speculative pass, units among them redone by the exact kernels)."""
         u, r = C.c_uint64(0), C.c_uint64(0)
@@ -1664,6 +1677,37 @@ def _ctx(ctx):
     return _default_ctx
 
 
+DECODE_EXACT, DECODE_BINARY32_BULK, DECODE_BINARY32 = 0, 1, 2
+_PRECISIONS = {'exact': DECODE_EXACT, 'binary32': DECODE_BINARY32}
+
+
+def check_precision(precision):
+    """None (the context's model as it is) | 'exact' | 'binary32' -> the decode model of the call, or None"""
+    if precision is None:
+        return None
+    if not isinstance(precision, str) or precision not in _PRECISIONS:
+        raise ValueError("precision must be None, 'exact' or 'binary32', got %r" % (precision,))
+    return _PRECISIONS[precision]
+
+
+class _decode_model:
+    """the context's decode model set for the length of a call and put back afterwards, also on error"""
+
+    def __init__(self, ctx, model):
+        self.ctx, self.model = ctx, model
+
+    def __enter__(self):
+        if self.model is not None:
+            self.before = self.ctx.decode_model
+            self.ctx.set_decode_model(self.model)
+        return self.ctx
+
+    def __exit__(self, *exc):
+        if self.model is not None:
+            self.ctx.set_decode_model(self.before)
+        return False
+
+
 def _check_channels(channels):
     if (not isinstance(channels, (list, tuple)) or len(channels) not in (1, 2)
             or any(not (isinstance(c, np.ndarray) and c.dtype == np.float32) for c in channels)):
@@ -1684,8 +1728,12 @@ def encode_pcm(channels, options=None, ctx=None):
     return _ctx(ctx).encode(padded, options)
 
 
-def decode_units(units, channels, ctx=None):
-    return _ctx(ctx).decode(units, channels)
+def decode_units(units, channels, ctx=None, precision=None):
+    """precision: None (the context's decode model) | 'exact' | 'binary32' (Context.set_decode_model's DECODE_BINARY32) for
+    this call; the context's model is put back afterwards"""
+    model = check_precision(precision)
+    with _decode_model(_ctx(ctx), model) as c:
+        return c.decode(units, channels)
 
 
 def encode_aea_pcm(channels, options=None, ctx=None):
@@ -1808,11 +1856,14 @@ def encode_aea_pcm_many(items, options=None, ctx=None, measured_allocation=False
     return [aea_header(t, u.shape[0], nch) + u.tobytes() for t, u, nch in zip(titles, interleave_item_units(units, counts), counts)]
 
 
-def decode_aea_pcm_many(images, ctx=None):
-    """decode_aea_pcm for many AEA images in one device call -> per image a list of float32 arrays (one per channel)"""
+def decode_aea_pcm_many(images, ctx=None, precision=None):
+    """decode_aea_pcm for many AEA images in one device call -> per image a list of float32 arrays (one per channel).
+    precision: as decode_units"""
+    model = check_precision(precision)
     parsed = [aea_image_units(d) for d in images]
     counts = [nch for _, nch in parsed]
-    pcm = _ctx(ctx).decode_signals(deinterleave_item_units([u for u, _ in parsed], counts))
+    with _decode_model(_ctx(ctx), model) as c:
+        pcm = c.decode_signals(deinterleave_item_units([u for u, _ in parsed], counts))
     out, k = [], 0
     for nch in counts:
         out.append(list(pcm[k:k + nch]))
@@ -1820,10 +1871,13 @@ def decode_aea_pcm_many(images, ctx=None):
     return out
 
 
-def decode_aea_pcm(data, ctx=None):
-    """decodeAeaPcm (processor.js:628-654): bytes / bytearray / ndarray(uint8) -> list of float32 arrays."""
+def decode_aea_pcm(data, ctx=None, precision=None):
+    """decodeAeaPcm (processor.js:628-654): bytes / bytearray / ndarray(uint8) -> list of float32 arrays.
+    precision: as decode_units"""
+    model = check_precision(precision)
     units, nch = aea_image_units(data)
-    return _ctx(ctx).decode(units, nch)
+    with _decode_model(_ctx(ctx), model) as c:
+        return c.decode(units, nch)
 
 
 # ---- sound unit <-> fields: codec/io/serialization.js:41-176 (format code, host side) ----------------

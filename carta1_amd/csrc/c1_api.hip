@@ -447,6 +447,7 @@ struct c1_ctx {
   int spec_mode = 1;                             // 0 exact only, 1 material-local (default), 2 always speculate
   float spec_defer = 1.0f;                       // mode 1: predicted open decisions per unit past which a run goes to the exact kernels
   bool decode_binary32 = false;                  // c1_ctx_set_decode_precision: opt-in binary32 decoder
+  int decode_model = C1_DECODE_EXACT;            // c1_ctx_set_decode_model; decode_binary32 == (decode_model != C1_DECODE_EXACT)
   bool spec_tables_ok = false;
   // transient-detection workspace (allocated on first use): band samples, feature sums, block modes
   int64_t det_units = 0;
@@ -1537,11 +1538,26 @@ int c1_ctx_set_speculation(c1_ctx *ctx, int mode) {
   return C1_OK;
 }
 
-int c1_ctx_set_decode_precision(c1_ctx *ctx, int binary32) {
+int c1_ctx_set_decode_model(c1_ctx *ctx, int model) {
   if (!ctx) return fail(C1_ERR_ARG, "context is NULL");
+  if (model != C1_DECODE_EXACT && model != C1_DECODE_BINARY32_BULK && model != C1_DECODE_BINARY32)
+    return fail(C1_ERR_ARG, "decode model must be 0, 1 or 2, got %d", model);
   CTX_GUARD(ctx);
-  ctx->decode_binary32 = binary32 != 0;
+  ctx->decode_model = model;
+  ctx->decode_binary32 = model != C1_DECODE_EXACT;
   return C1_OK;
+}
+
+int c1_ctx_get_decode_model(c1_ctx *ctx, int *model) {
+  if (!ctx) return fail(C1_ERR_ARG, "context is NULL");
+  if (!model) return fail(C1_ERR_ARG, "model is NULL");
+  CTX_GUARD(ctx);
+  *model = ctx->decode_model;
+  return C1_OK;
+}
+
+int c1_ctx_set_decode_precision(c1_ctx *ctx, int binary32) {
+  return c1_ctx_set_decode_model(ctx, binary32 ? C1_DECODE_BINARY32_BULK : C1_DECODE_EXACT);
 }
 
 int c1_ctx_speculation_stats(c1_ctx *ctx, uint64_t *units, uint64_t *redone, int reset) {
@@ -3478,6 +3494,7 @@ int launch_decode_fields(c1_ctx *ctx, const C1FieldPtrs &cur, const C1FieldPtrs 
   L.frames = frames;
   L.halo_frames = halo_frames;
   L.tables = ctx->d_tables;
+  L.binary32 = ctx->decode_model == C1_DECODE_BINARY32;
   for (int c = 0; c < channels; c++) L.pcm[c] = pcm[c];
   { ScopedTiming t(ctx, K_DECODE_FIELDS); c1k_launch_decode_fields(L, ctx->stream); }
   HIP_TRY(hipGetLastError());
@@ -4552,6 +4569,7 @@ struct c1_dec_stream {
   // from-state kernel; its fields are the history of everything behind it, as after any field push
   bool restored = false;
   float *d_state = nullptr;                    // channels x c1_dec_state, then one zero state per channel, then scratch
+  int prev_model = C1_DECODE_EXACT;            // the context's decode model when the previous frame was decoded
 };
 
 namespace {
@@ -4595,6 +4613,31 @@ int dec_stream_state_buffer(c1_dec_stream *s) {
   HIP_TRY(hipMemsetAsync(s->d_state, 0, bytes, s->ctx->stream));
   return C1_OK;
 }
+// The stream rebuilds the pool before a push from its previous frame, in the arithmetic of the push.  When the context's model
+// went to or from C1_DECODE_BINARY32 since that frame was decoded, the pool is the one the frame left under the model that
+// decoded it: it is made explicit here (as c1_dec_stream_get_state would have returned it), and the push continues from it as
+// after c1_dec_stream_set_state.  A change between the other two models takes no part in this: they share every kernel but
+// k_decode, which rebuilds its halo itself.
+int dec_stream_follow_model(c1_dec_stream *s) {
+  c1_ctx *ctx = s->ctx;
+  const bool was32 = s->prev_model == C1_DECODE_BINARY32, is32 = ctx->decode_model == C1_DECODE_BINARY32;
+  if (s->restored || !s->have_prev || was32 == is32) return C1_OK;
+  int rc;
+  if ((rc = dec_stream_state_buffer(s))) return rc;
+  if ((rc = dec_stream_prev_fields(s))) return rc;
+  C1DecStateLaunch K;
+  memset(&K, 0, sizeof K);
+  K.fields = s->prev_fields;
+  K.in = s->d_state + (size_t)s->channels * kDecStateFloats;
+  K.out = s->d_state;
+  K.n = s->channels;
+  K.tables = ctx->d_tables;
+  K.binary32 = was32;
+  c1k_launch_decode_from_states(K, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  s->restored = true;
+  return C1_OK;
+}
 // decode `frames` frames whose fields are at `cur` (layout over frames * channels units) from the stream's history, then make
 // the last of them the history; downloads the PCM and synchronises
 int dec_stream_decode_fields(c1_dec_stream *s, const C1FieldPtrs &cur, int64_t frames, float *const *pcm) {
@@ -4614,6 +4657,7 @@ int dec_stream_decode_fields(c1_dec_stream *s, const C1FieldPtrs &cur, int64_t f
     K.pcm_stride = s->cap_frames * 512;
     K.n = s->channels;
     K.tables = ctx->d_tables;
+    K.binary32 = ctx->decode_model == C1_DECODE_BINARY32;
     { ScopedTiming t(ctx, K_FROM_STATE); c1k_launch_decode_from_states(K, ctx->stream); }
     HIP_TRY(hipGetLastError());
     if (frames > 1) {
@@ -4627,6 +4671,7 @@ int dec_stream_decode_fields(c1_dec_stream *s, const C1FieldPtrs &cur, int64_t f
   s->fields_next ^= 1;
   s->have_prev = true;
   s->prev_is_unit = false;
+  s->prev_model = ctx->decode_model;
   for (int c = 0; c < s->channels; c++)
     HIP_TRY(hipMemcpyAsync(pcm[c], dptr[c], (size_t)frames * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -4660,6 +4705,7 @@ int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units, int64_t frames, f
   for (int c = 0; c < s->channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
   const size_t ub = (size_t)s->channels * C1_UNIT_BYTES;
   if ((rc = dec_stream_reserve(s, frames))) return rc;
+  if ((rc = dec_stream_follow_model(s))) return rc;
   if (s->restored || (s->have_prev && !s->prev_is_unit)) {
     // the previous frame is held as fields (or the pool is a restored one), which a unit cannot stand in for: unpack this push's units and decode them
     // from fields too (k_unpack_units + k_decode_fields decode any unit exactly as k_decode does)
@@ -4683,6 +4729,7 @@ int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units, int64_t frames, f
   HIP_TRY(hipMemcpyAsync(s->d_prev, s->d_units + ub * frames, ub, hipMemcpyDeviceToDevice, ctx->stream));
   s->have_prev = true;
   s->prev_is_unit = true;
+  s->prev_model = ctx->decode_model;
   s->prev_fields.nbfu = nullptr;
   for (int c = 0; c < s->channels; c++)
     HIP_TRY(hipMemcpyAsync(pcm[c], dptr[c], (size_t)frames * 512 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -4704,6 +4751,7 @@ int c1_dec_stream_push_fields(c1_dec_stream *s, int64_t frames, const int32_t *n
   const int64_t units_n = frames * s->channels;
   if ((rc = check_field_domain("decode fields", units_n, s->channels, 0, nbfu, sfi, wl))) return rc;
   if ((rc = dec_stream_reserve(s, frames))) return rc;
+  if ((rc = dec_stream_follow_model(s))) return rc;
   if (units_n > s->stage_cap) {
     if (s->h_stage) hipHostFree(s->h_stage);
     s->h_stage = nullptr; s->stage_cap = 0;
@@ -4797,6 +4845,7 @@ int decode_from_states_impl(c1_ctx *ctx, int64_t n, const uint8_t *units, const 
     K.pcm_stride = 512;
     K.n = m;
     K.tables = ctx->d_tables;
+    K.binary32 = ctx->decode_model == C1_DECODE_BINARY32;
     { ScopedTiming t(ctx, K_FROM_STATE); c1k_launch_decode_from_states(K, ctx->stream); }
   }
   HIP_TRY(hipGetLastError());
@@ -5349,6 +5398,7 @@ int decode_signals_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const uint8_
     K.dst_rows = da_first + r0;
     K.n = m;
     K.tables = ctx->d_tables;
+    K.binary32 = ctx->decode_model == C1_DECODE_BINARY32;
     c1k_launch_decode_rows(K, ctx->stream);
     if (out) {
       // 3. the pool after a signal is a function of its last unit alone: state only, from zeros (c1_dec_stream_get_state)
@@ -5608,7 +5658,8 @@ int c1_dec_stream_get_state(c1_dec_stream *s, c1_dec_state *out) {
   if ((rc = dec_stream_state_buffer(s))) return rc;
   const float *src = s->d_state;
   if (!s->restored) {
-    // what a frame leaves is a function of that frame alone: decode the previous frame once more, state output only
+    // what a frame leaves is a function of that frame alone: decode the previous frame once more, state output only, in the
+    // arithmetic of the model that decoded it
     if ((rc = dec_stream_prev_fields(s))) return rc;
     float *zero = s->d_state + (size_t)s->channels * kDecStateFloats, *tmp = zero + (size_t)s->channels * kDecStateFloats;
     C1DecStateLaunch K;
@@ -5618,6 +5669,7 @@ int c1_dec_stream_get_state(c1_dec_stream *s, c1_dec_state *out) {
     K.out = tmp;
     K.n = s->channels;
     K.tables = ctx->d_tables;
+    K.binary32 = s->prev_model == C1_DECODE_BINARY32;
     c1k_launch_decode_from_states(K, ctx->stream);
     HIP_TRY(hipGetLastError());
     src = tmp;

@@ -182,6 +182,7 @@ struct C1DecodeFieldsLaunch {
   const C1DevTables *tables;
   float *pcm[C1_MAX_CHANNELS];
   int run_frames;        // consecutive frames of one channel a wave decodes (set by the launcher)
+  int binary32;          // k_decode_fields<float>: k_decode<float>'s arithmetic (C1_DECODE_BINARY32); 0: the reference's
 };
 
 // The frame closures over explicit BufferPool state (c1_k_state.hip): pool i encodes the frame at pcm + i * pcm_stride from
@@ -220,6 +221,7 @@ struct C1DecStateLaunch {
   // pcm + dst_rows[r] * 512 and writes the state out[out_rows[r]]; null lists and in_broadcast as in C1EncStateLaunch
   const uint32_t *dst_rows, *in_rows, *out_rows;
   int in_broadcast;
+  int binary32;          // k_decode_from_state<float, .>: k_decode<float>'s arithmetic (C1_DECODE_BINARY32); 0: the reference's
 };
 
 // The first frames of many signals in one pass (c1_k_signal_starts.hip): wave r walks counts[r] (1 or 2; null: count_all)

@@ -2,7 +2,10 @@
 // run of frames of one channel, as k_decode<double> walks them.  Only the front end is new: each frame reads its fields in the
 // layout c1_unpack_units writes and dequantizes them with the reference's general formula; the IMDCT, the overlap-add, the
 // imdctOverlap tails and the QMF synthesis are k_decode<double>'s own device code (c1_decode_core.h).
-// Number model: the reference's always (binary64 operations, binary32 at every typed-array store).
+// Number model: k_decode_fields<double> the reference's (binary64 operations, binary32 at every typed-array store);
+// k_decode_fields<float> (C1_DECODE_BINARY32) k_decode<float>'s, operation for operation: the same LDS image (binary32 scale
+// factors, RN(1 / range) and window), the step product SF * RN(1 / range) in place of the division, and the later stages in
+// binary32.  Fields unpacked from sound units then decode to k_decode<float>'s bits.
 #include "c1_decode_core.h"
 
 namespace {
@@ -30,8 +33,10 @@ __device__ __forceinline__ FrameFields load_fields(const C1FieldPtrs &P, int64_t
   return F;
 }
 
-__global__ __launch_bounds__(C1_WAVE, 3) void k_decode_fields(C1DecodeFieldsLaunch L) {
-  __shared__ DecodeLds<double> S;
+template <typename R>
+__global__ __launch_bounds__(C1_WAVE, (std::is_same<R, float>::value ? 4 : 3)) void k_decode_fields(C1DecodeFieldsLaunch L) {
+  constexpr bool F32 = std::is_same<R, float>::value;
+  __shared__ DecodeLds<R> S;
   const int lane0 = threadIdx.x;
   const int ch = blockIdx.x % L.channels;
   const int64_t f0 = (int64_t)(blockIdx.x / L.channels) * L.run_frames;
@@ -40,8 +45,14 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_fields(C1DecodeFieldsLaun
   for (int i = lane0; i < 46; i += 64) { S.d1[i] = 0; S.d2[i] = 0; }
   for (int i = lane0; i < 39; i += 64) S.dhi[i] = 0.0f;
   for (int i = lane0; i < 48; i += 64) S.tail[i] = 0.0f;
-  S.sf_tab[lane0] = C1_TABLES(L.tables)->scale_factors[lane0];
-  if (lane0 < 32) S.wtab[lane0] = C1_TABLES(L.tables)->window[lane0];
+  if constexpr (F32) {
+    S.sf_tab[lane0] = (R)C1_TABLES(L.tables)->scale_factors[lane0];
+    if (lane0 < 16) S.inv_tab[lane0] = (R)C1_TABLES(L.tables)->inv_range[lane0];
+    if (lane0 < 32) S.wtab[lane0] = (R)C1_TABLES(L.tables)->win32[lane0];
+  } else {
+    S.sf_tab[lane0] = C1_TABLES(L.tables)->scale_factors[lane0];
+    if (lane0 < 32) S.wtab[lane0] = C1_TABLES(L.tables)->window[lane0];
+  }
   const TablesRsrc RT = tables_rsrc(L.tables);
   wave_fence();
 
@@ -74,7 +85,12 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_fields(C1DecodeFieldsLaun
         const uint32_t d = S.desc[b];
         const int bits = (int)(d & 31u), sf = (int)(d >> 5);
         float v = 0.0f;
-        if (bits != 0 && sf != 0) {                  // quantization.js:65-78: Float32((q * SF) / range), q any int32
+        if constexpr (F32) {
+          // k_decode<float>: q * (SF * RN(1 / range)) with q = 0 where there are no bits; the product also for a silent BFU
+          // (step 0: the zero takes q's sign)
+          const R step = sf != 0 ? S.sf_tab[sf] * S.inv_tab[bits > 0 ? bits - 1 : 0] : (R)0;
+          v = (float)((R)(bits != 0 ? q[m] : 0) * step);
+        } else if (bits != 0 && sf != 0) {           // quantization.js:65-78: Float32((q * SF) / range), q any int32
           const int32_t range = (1 << (bits - 1)) - 1;
           v = f32(((double)q[m] * S.sf_tab[sf]) / (double)range);
         }
@@ -88,17 +104,17 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_fields(C1DecodeFieldsLaun
     // ---------------- imdctStage (decoder.js:116-330) ----------------
     const FrameModes M{F.m0, F.m1, F.m2};
     float *mid = S.u.m.zz.mid;
-    const IMixGeometry IG = imix_geometry<double>(lane, M);
-    imdct_r4<double>(S.cb.coef, S.u.m.zz.z, mid, IG, M.m0 == 0 || M.m1 == 0 || M.m2 == 0, M.m2 == 0, T, RT);
+    const IMixGeometry IG = imix_geometry<R>(lane, M);
+    imdct_r4<R>(S.cb.coef, S.u.m.zz.z, mid, IG, M.m0 == 0 || M.m1 == 0 || M.m2 == 0, M.m2 == 0, T, RT);
     wave_fence();
-    overlap_add_mixed<double>(S, mid, lane, M);
+    overlap_add_mixed<R>(S, mid, lane, M);
     wave_fence();
-    save_imdct_tails<double>(S, mid, lane);
+    save_imdct_tails<R>(S, mid, lane);
     wave_fence();
 
     // ---------------- qmfSynthesisStage (decoder.js:349-389) ----------------
-    double s0[4], s1[4];
-    qmf_synthesis_frame<double>(S, lane, T, s0, s1);
+    R s0[4], s1[4];
+    qmf_synthesis_frame<R>(S, lane, T, s0, s1);
     // the next frame's fields have arrived: nothing waits on a load behind the stores below (loads and stores share one
     // counter on this part, c1_k_decode.hip)
     asm volatile("" : "+v"(next.qa.x), "+v"(next.qb.x), "+v"(next.wl), "+v"(next.sfi));
@@ -118,5 +134,6 @@ void c1k_launch_decode_fields(const C1DecodeFieldsLaunch &L0, hipStream_t stream
   L.run_frames = c1k_pick_run(L.frames, L.channels, 0);
   const int64_t runs = (L.frames + L.run_frames - 1) / L.run_frames;
   const dim3 grid((unsigned)(runs * L.channels)), block(C1_WAVE);
-  hipLaunchKernelGGL(k_decode_fields, grid, block, 0, stream, L);
+  if (L.binary32) hipLaunchKernelGGL((k_decode_fields<float>), grid, block, 0, stream, L);
+  else hipLaunchKernelGGL((k_decode_fields<double>), grid, block, 0, stream, L);
 }

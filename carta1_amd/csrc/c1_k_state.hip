@@ -284,13 +284,22 @@ __device__ __forceinline__ PoolFields load_pool_fields(const C1FieldPtrs &P, int
   return F;
 }
 
-// the LDS image is k_decode_fields' own (DecodeLds<double>): the same stages run on it
-template <bool kRows>
-__global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaunch L) {
-  __shared__ DecodeLds<double> S;
+// the LDS image is k_decode_fields' own (DecodeLds<R>): the same stages run on it.  R = float (C1_DECODE_BINARY32) is
+// k_decode<float>'s arithmetic, operation for operation, as in k_decode_fields<float>; the state's floats enter and leave the
+// binary32 delay lines as they are
+template <typename R, bool kRows>
+__global__ __launch_bounds__(C1_WAVE, (std::is_same<R, float>::value ? 4 : 3)) void k_decode_from_state(C1DecStateLaunch L) {
+  constexpr bool F32 = std::is_same<R, float>::value;
+  __shared__ DecodeLds<R> S;
   const int lane0 = threadIdx.x;
-  S.sf_tab[lane0] = C1_TABLES(L.tables)->scale_factors[lane0];
-  if (lane0 < 32) S.wtab[lane0] = C1_TABLES(L.tables)->window[lane0];
+  if constexpr (F32) {
+    S.sf_tab[lane0] = (R)C1_TABLES(L.tables)->scale_factors[lane0];
+    if (lane0 < 16) S.inv_tab[lane0] = (R)C1_TABLES(L.tables)->inv_range[lane0];
+    if (lane0 < 32) S.wtab[lane0] = (R)C1_TABLES(L.tables)->win32[lane0];
+  } else {
+    S.sf_tab[lane0] = C1_TABLES(L.tables)->scale_factors[lane0];
+    if (lane0 < 32) S.wtab[lane0] = C1_TABLES(L.tables)->window[lane0];
+  }
   const TablesRsrc RT = tables_rsrc(L.tables);
   wave_fence();
   for (int64_t pool = blockIdx.x; pool < L.n; pool += gridDim.x) {
@@ -307,7 +316,7 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaun
     const PoolFields F = load_pool_fields(L.fields, pool, lane);
     const float s_low = in[kDsLow + (lane < 46 ? lane : 45)], s_mid = in[kDsMid + (lane < 46 ? lane : 45)];
     const float s_high = in[kDsHigh + (lane < 39 ? lane : 38)], s_tail = in[kDsTail + (lane < 48 ? lane : 47)];
-    if (lane < 46) { S.d1[lane] = (double)s_low; S.d2[lane] = (double)s_mid; }
+    if (lane < 46) { S.d1[lane] = (R)s_low; S.d2[lane] = (R)s_mid; }
     if (lane < 39) S.dhi[lane] = s_high;
     if (lane < 48) S.tail[lane] = s_tail;
 
@@ -323,7 +332,10 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaun
         const uint32_t d = S.desc[b];
         const int bits = (int)(d & 31u), sf = (int)(d >> 5);
         float v = 0.0f;
-        if (bits != 0 && sf != 0) {                  // quantization.js:65-78: Float32((q * SF) / range), q any int32
+        if constexpr (F32) {                         // k_decode<float>'s step product, also for a silent BFU (k_decode_fields<float>)
+          const R step = sf != 0 ? S.sf_tab[sf] * S.inv_tab[bits > 0 ? bits - 1 : 0] : (R)0;
+          v = (float)((R)(bits != 0 ? q[m] : 0) * step);
+        } else if (bits != 0 && sf != 0) {           // quantization.js:65-78: Float32((q * SF) / range), q any int32
           const int32_t range = (1 << (bits - 1)) - 1;
           v = f32(((double)q[m] * S.sf_tab[sf]) / (double)range);
         }
@@ -336,17 +348,17 @@ __global__ __launch_bounds__(C1_WAVE, 3) void k_decode_from_state(C1DecStateLaun
     // ---------------- imdctStage (decoder.js:116-330) with the pool's imdctOverlap tails ----------------
     const FrameModes M{F.m0, F.m1, F.m2};
     float *mid = S.u.m.zz.mid;
-    const IMixGeometry IG = imix_geometry<double>(lane, M);
-    imdct_r4<double>(S.cb.coef, S.u.m.zz.z, mid, IG, M.m0 == 0 || M.m1 == 0 || M.m2 == 0, M.m2 == 0, T, RT);
+    const IMixGeometry IG = imix_geometry<R>(lane, M);
+    imdct_r4<R>(S.cb.coef, S.u.m.zz.z, mid, IG, M.m0 == 0 || M.m1 == 0 || M.m2 == 0, M.m2 == 0, T, RT);
     wave_fence();
-    overlap_add_mixed<double>(S, mid, lane, M);
+    overlap_add_mixed<R>(S, mid, lane, M);
     wave_fence();
-    save_imdct_tails<double>(S, mid, lane);
+    save_imdct_tails<R>(S, mid, lane);
     wave_fence();
 
     // ---------------- qmfSynthesisStage (decoder.js:349-389) with the pool's delay lines ----------------
-    double s0[4], s1[4];
-    qmf_synthesis_frame<double>(S, lane, T, s0, s1);
+    R s0[4], s1[4];
+    qmf_synthesis_frame<R>(S, lane, T, s0, s1);
     wave_fence();
     if (L.pcm) {
       float4 *dst = reinterpret_cast<float4 *>(L.pcm + dst_off + 8 * lane);
@@ -392,7 +404,8 @@ void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_
 }
 void c1k_launch_decode_from_states(const C1DecStateLaunch &L, hipStream_t stream) {
   if (L.n <= 0) return;
-  hipLaunchKernelGGL(k_decode_from_state<false>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  if (L.binary32) hipLaunchKernelGGL((k_decode_from_state<float, false>), dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  else hipLaunchKernelGGL((k_decode_from_state<double, false>), dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
 }
 void c1k_launch_encode_rows(const C1EncStateLaunch &L, hipStream_t stream) {
   if (L.n <= 0) return;
@@ -400,7 +413,8 @@ void c1k_launch_encode_rows(const C1EncStateLaunch &L, hipStream_t stream) {
 }
 void c1k_launch_decode_rows(const C1DecStateLaunch &L, hipStream_t stream) {
   if (L.n <= 0) return;
-  hipLaunchKernelGGL(k_decode_from_state<true>, dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  if (L.binary32) hipLaunchKernelGGL((k_decode_from_state<float, true>), dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
+  else hipLaunchKernelGGL((k_decode_from_state<double, true>), dim3(state_grid(L.n)), dim3(C1_WAVE), 0, stream, L);
 }
 void c1k_launch_copy_rows(uint32_t *dst, const uint32_t *dst_rows, const uint32_t *src, const uint32_t *src_rows, int src_broadcast,
                           int64_t n, int dwords, hipStream_t stream) {

@@ -203,6 +203,18 @@ napi_value CtxCreate(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_create_external(env, ctx, FinalizeCtx, nullptr, &ext));
   return ext;
 }
+// ctxSetDecodeModel(ctx, model): c1_ctx_set_decode_model (0 exact, 1 binary32 in the unit-walking kernel, 2 binary32 throughout)
+napi_value CtxSetDecodeModel(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  c1_ctx *ctx;
+  if (!get_external(env, argv[0], &ctx)) return nullptr;
+  int32_t model = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[1], &model));
+  const int rc = c1_ctx_set_decode_model(ctx, model);
+  if (rc) return throw_c1(env, rc);
+  return nullptr;
+}
 
 // ---- batches ------------------------------------------------------------------------------------------
 // encodeBatch(ctx, [Float32Array...], haloFrames, options) -> Uint8Array(frames*channels*212)
@@ -1571,6 +1583,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"getDefaultTables", nullptr, GetDefaultTables, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setTables", nullptr, SetTables, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxCreate", nullptr, CtxCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ctxSetDecodeModel", nullptr, CtxSetDecodeModel, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"allocPinned", nullptr, AllocPinned, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatch", nullptr, EncodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeBatchModes", nullptr, EncodeBatchModes, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -52,6 +52,7 @@ export class BufferPool {
   constructor() {
     this.encoderStream = null // c1_enc_stream, created by the first encode() closure call
     this.decoderStream = null // c1_dec_stream
+    this.decoderPrecision = 'exact' // the precision of the decode() closure that created decoderStream (pipeline/decoder.js)
     this.encoderOptionsKey = null
     this.pendingEncoderState = null // Float32Array(483) set before the stream exists
     this.pendingDecoderState = null // Float32Array(179)

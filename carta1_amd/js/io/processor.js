@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, encodeSignalsMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
+import { native, context, checkPrecision, decodeContext, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, encodeSignalsMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -187,7 +187,11 @@ export async function encodeAeaPcm(channels, options = {}) {
   return image
 }
 
+// options: { devices, precision: 'exact' (default) | 'binary32' } (native.js); the multi-device decode is the exact one only
 export async function decodeAeaPcm(input, options = {}) {
+  const precision = checkPrecision(options)
+  const multi = Array.isArray(options.devices) && options.devices.length
+  if (multi && precision !== 'exact') throw new TypeError("precision: 'binary32' cannot be combined with devices")
   let bytes
   if (input instanceof Uint8Array) bytes = input
   else if (input instanceof ArrayBuffer) bytes = new Uint8Array(input)
@@ -205,7 +209,7 @@ export async function decodeAeaPcm(input, options = {}) {
     body[units.length] = 0xac
   }
   if (body.length === 0) return nch === 1 ? [new Float32Array(0)] : [new Float32Array(0), new Float32Array(0)]
-  const where = Array.isArray(options.devices) && options.devices.length ? options.devices : context()
+  const where = multi ? options.devices : decodeContext(precision)
   return native().decodeBatchAsync(where, body, nch, 0)
 }
 
@@ -328,8 +332,10 @@ export async function encodeAeaPcmMany(items, options = {}) {
   })
 }
 
-// decodeAeaPcm for many AEA images (Uint8Array or ArrayBuffer) at once -> per image an array of Float32Array, one per channel
-export async function decodeAeaPcmMany(images) {
+// decodeAeaPcm for many AEA images (Uint8Array or ArrayBuffer) at once -> per image an array of Float32Array, one per channel.
+// options: { precision: 'exact' (default) | 'binary32' } (native.js)
+export async function decodeAeaPcmMany(images, options = {}) {
+  const precision = checkPrecision(options)
   if (!Array.isArray(images)) throw new TypeError('images must be an array of AEA byte images')
   const parsed = images.map(imageBody)
   const frameOffsets = new Float64Array(parsed.reduce((n, p) => n + p.nch, 0) + 1)
@@ -344,7 +350,7 @@ export async function decodeAeaPcmMany(images) {
     deinterleaveItemUnits(body, nch, units, frameOffsets[k])
     k += nch
   }
-  const pcm = total > 0 ? native().decodeSignals(context(), units, frameOffsets) : new Float32Array(0)
+  const pcm = total > 0 ? native().decodeSignals(decodeContext(precision), units, frameOffsets) : new Float32Array(0)
   k = 0
   return parsed.map(({ nch }) => {
     const out = []
@@ -371,8 +377,9 @@ export function encodeWavPcm(wavBody, options = {}) {
 }
 
 // AEA image -> { channelCount, samples: Int16Array (interleaved) }: decode + the 16-bit conversion of createWavBlob
-// (processor.js:349-447) on the device
-export function decodeAeaToWav16(bytes) {
+// (processor.js:349-447) on the device.  options: { precision: 'exact' (default) | 'binary32' } (native.js)
+export function decodeAeaToWav16(bytes, options = {}) {
+  const precision = checkPrecision(options)
   if (!(bytes instanceof Uint8Array)) throw new TypeError('ATRAC1 decoding requires AEA bytes')
   const { info, units } = AudioProcessor.parseAea(bytes)
   const nch = info.channelCount
@@ -387,12 +394,12 @@ export function decodeAeaToWav16(bytes) {
   } else if (rest) {
     whole = units.subarray(0, units.length - rest)
   }
-  return { channelCount: nch, samples: whole.length ? native().decodeWav16Batch(context(), whole, nch) : new Int16Array(0) }
+  return { channelCount: nch, samples: whole.length ? native().decodeWav16Batch(decodeContext(precision), whole, nch) : new Int16Array(0) }
 }
 
 export class AudioProcessor {
   static encodeAeaPcm(channels, options = {}) { return encodeAeaPcm(channels, options) }
-  static decodeAeaPcm(input) { return decodeAeaPcm(input) }
+  static decodeAeaPcm(input, options = {}) { return decodeAeaPcm(input, options) }
 
   // PCM frames -> a 16-bit PCM WAV file (the reference's createWavBlob, processor.js:349-447, returns a Blob; createWavBytes
   // returns the same bytes as a Uint8Array so this also runs where Blob does not exist).  pcmFrames: mono frames (or one
@@ -508,9 +515,10 @@ export class AudioProcessor {
 
   static async *decodeStream(encodedFrames, options = {}) {
     const { channelCount = 1, onProgress } = options
+    const precision = checkPrecision(options)
     if (channelCount !== 1 && channelCount !== 2) throw new Error(`Unsupported channel count: ${channelCount}`)
     const decoders = []
-    for (let c = 0; c < channelCount; c++) decoders.push(decode(new BufferPool()))
+    for (let c = 0; c < channelCount; c++) decoders.push(decode(new BufferPool(), { precision }))
     let frameIndex = 0
     let pending = []
     for await (const frame of encodedFrames) {

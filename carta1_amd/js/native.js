@@ -8,6 +8,7 @@ import { buildNativeTables } from './core/constants.js'
 const require = createRequire(import.meta.url)
 let addon = null
 let defaultCtx = null
+let binary32Ctx = null
 
 export function native() {
   if (!addon) {
@@ -25,6 +26,30 @@ export function context(device = 0) {
   if (device !== 0) return native().ctxCreate(device)
   if (!defaultCtx) defaultCtx = native().ctxCreate(0)
   return defaultCtx
+}
+
+// The decode option { precision: 'exact' | 'binary32' } of decode(), decodeAeaPcm, decodeAeaPcmMany, decodeAeaToWav16 and
+// AudioProcessor.decodeStream.  'exact' (default): bit-identical to the reference.  'binary32': every decode entry in binary32
+// (c1_ctx_set_decode_model, C1_DECODE_BINARY32): the PCM differs from the reference's by rounding noise, a few 2^-24 of the
+// signal.  Anything else is a TypeError naming the option, raised before any native call.
+export const DECODE_EXACT = 0, DECODE_BINARY32_BULK = 1, DECODE_BINARY32 = 2
+export function checkPrecision(options) {
+  if (options === null || typeof options !== 'object') throw new TypeError('options must be an object { precision }')
+  const precision = options.precision === undefined ? 'exact' : options.precision
+  if (precision !== 'exact' && precision !== 'binary32') throw new TypeError(`precision must be 'exact' or 'binary32', got ${String(precision)}`)
+  return precision
+}
+
+// The context decode calls of the given precision run on.  The shared default context is never switched: binary32 decodes have
+// a default context of their own, created at the first use, whose decode model is C1_DECODE_BINARY32.
+export function decodeContext(precision = 'exact') {
+  if (precision !== 'binary32') return context()
+  if (!binary32Ctx) {
+    const ctx = native().ctxCreate(0)
+    native().ctxSetDecodeModel(ctx, DECODE_BINARY32)
+    binary32Ctx = ctx
+  }
+  return binary32Ctx
 }
 
 export function deviceCount() {

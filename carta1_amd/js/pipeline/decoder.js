@@ -2,18 +2,27 @@
 // overlap-add and QMF synthesis run as one HIP kernel; decoder state lives in the pool's native stream.
 import { BufferPool } from '../core/buffers.js'
 import { SPECS_PER_BFU } from '../core/constants.js'
-import { native, context } from '../native.js'
+import { native, context, checkPrecision, decodeContext } from '../native.js'
 import { throwError } from '../utils.js'
 
 // A sound unit (Uint8Array) is decoded from its bytes; a frameData object from its fields as they stand, without
 // serializeFrame, so that fields no unit can carry (an nBfu outside BFU_AMOUNTS, a band mode of 1, mantissas beyond their word
 // length) decode as the reference decodes them.  Both kinds continue the same native stream.
-export function decode(bufferPool = new BufferPool()) {
+// options: { precision: 'exact' (default) | 'binary32' } (native.js).  The pool's native stream lives on the context of the
+// precision it was created with; a closure of the other precision on the same pool moves it -- the pool's state is read from
+// the stream and a new stream on the other context continues from it -- so the audio goes on without a seam.
+export function decode(bufferPool = new BufferPool(), options = {}) {
+  const precision = checkPrecision(options)
   if (!bufferPool) throwError('imdctStage: bufferPool is required')
   return (frameData) => {
     const addon = native()
+    if (bufferPool.decoderStream && bufferPool.decoderPrecision !== precision) {
+      bufferPool.pendingDecoderState = addon.decStreamGetState(bufferPool.decoderStream, 1)
+      bufferPool.decoderStream = null
+    }
     if (!bufferPool.decoderStream) {
-      bufferPool.decoderStream = addon.decStreamCreate(context(), 1)
+      bufferPool.decoderStream = addon.decStreamCreate(decodeContext(precision), 1)
+      bufferPool.decoderPrecision = precision
       if (bufferPool.pendingDecoderState) { // a state set before the stream existed (BufferPool.setDecoderState)
         addon.decStreamSetState(bufferPool.decoderStream, 1, bufferPool.pendingDecoderState)
         bufferPool.pendingDecoderState = null

@@ -171,10 +171,34 @@ int c1_ctx_quantization_stats(c1_ctx *ctx, uint64_t *units, uint64_t *repacked);
  * the exact recheck (cleared by c1_ctx_speculation_stats(reset)). */
 int c1_ctx_detection_stats(c1_ctx *ctx, uint64_t *units, uint64_t *rechecked);
 
-/* Decoder arithmetic.  0 (default): the reference's -- binary64 operations, binary32 at every typed-array store --
- * decoded PCM bit-identical to the reference.  1: the same computation in binary32 throughout; the PCM then differs
- * from the reference's by rounding noise (measured RMS < 1e-7 on full-scale material; the task statement allows 1e-5
- * "otherwise").  Applies to every decode entry point of the context. */
+/* Decoder arithmetic: one of three models per context.
+ *   C1_DECODE_EXACT (0, default): the reference's -- binary64 operations, binary32 at every typed-array store -- decoded PCM
+ *     and decoder state bit-identical to the reference, on every entry.
+ *   C1_DECODE_BINARY32_BULK (1): the unit-walking kernel alone (c1_decode_device / _batch, c1_decode_wav16_batch, the bulk of
+ *     c1_decode_signals*, a c1_dec_stream while it is pushed units) computes in binary32; the PCM then differs from the
+ *     reference's by rounding noise (at most 11 u of a coefficient's peak response and 3 u of a stream's RMS, u = 2^-24,
+ *     DESIGN.md 6s).  Everything that decodes from frame fields or from a c1_dec_state stays exact: c1_decode_fields_*,
+ *     c1_decode_frames_from_states*, the first frame of every signal of c1_decode_signals* and the states it writes,
+ *     c1_dec_stream_push_fields, a stream's pushes from a c1_dec_stream_set_state or push_fields onwards, and
+ *     c1_dec_stream_get_state.
+ *   C1_DECODE_BINARY32 (2): every decode entry of the context that produces PCM or decoder state computes in binary32, in the
+ *     unit-walking kernel's arithmetic operation for operation: c1_decode_device / _batch, c1_decode_wav16_batch,
+ *     c1_decode_fields_device / _batch, c1_decode_frames_from_states*, c1_decode_signals* (the bulk, the first frames and the
+ *     states written out), c1_dec_stream_push in all its branches, c1_dec_stream_push_fields and c1_dec_stream_get_state /
+ *     _set_state.  Sound units decode to the same bits through any of them and through any split into calls.
+ * A stream reads its context's model at every call.  A c1_dec_state is 179 floats under any model (the binary32 delay lines
+ * are stored as they are, the exact ones hold binary32 values already), so a change of model between two pushes is well
+ * defined: each frame is decoded from the state before it under the model in force.
+ * Under every model these stay in the reference's arithmetic: c1_measure_pcm_*, the single-stage exports (c1_dequantize,
+ * c1_dequantize_frames, c1_imdct_batch, c1_qmf_synthesis_batch, c1_unpack_units) and c1_decode_batch_multi, which takes no
+ * context.
+ * c1_ctx_set_decode_model: C1_ERR_ARG for a NULL context or any other value, which leaves the model unchanged.
+ * c1_ctx_set_decode_precision(ctx, x) is c1_ctx_set_decode_model(ctx, x ? C1_DECODE_BINARY32_BULK : C1_DECODE_EXACT). */
+#define C1_DECODE_EXACT 0
+#define C1_DECODE_BINARY32_BULK 1
+#define C1_DECODE_BINARY32 2
+int c1_ctx_set_decode_model(c1_ctx *ctx, int model);
+int c1_ctx_get_decode_model(c1_ctx *ctx, int *model);
 int c1_ctx_set_decode_precision(c1_ctx *ctx, int binary32);
 
 /* ---- encode: replaces the encode() frame closure body, encoder.js:438-450
@@ -620,7 +644,8 @@ int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
  *   Unit halo.  halo_units (0 or 1): the unit(s) of frame -1 precede `units`, as for c1_decode_device; otherwise the decoder
  *     starts from a fresh pool.
  *   Decoded PCM.  y[c][t], t = 0 .. 512 * frames - 1, is the Float32 PCM c1_decode_device writes for these units, channels,
- *     frames and halo_units, bit for bit: the exact (binary64) decoder whatever c1_ctx_set_decode_precision says.
+ *     frames and halo_units under C1_DECODE_EXACT, bit for bit: the exact (binary64) decoder under every decode model of the
+ *     context (c1_ctx_set_decode_model); the meter has no binary32 form.
  *   Delayed input.  x[c][t] = pcm[c][t - 266] (the codec delay); zero where t - 266 < -512 * halo_frames.
  *   Sums, in binary64 with no fused operation.  For unit u (frame f, channel c) and segment s = 0 .. 15, t = 512 f + 32 s + i,
  *     i ascending over 0 .. 31:   e = (double)y - (double)x
@@ -660,7 +685,8 @@ int c1_measure_pcm_batch(c1_ctx *ctx, const float *const *pcm, int channels, int
  * Bit-identical to c1_encode_batch on a fresh context. */
 int c1_encode_batch_multi(const int *devices, int n_devices, const float *const *pcm, int channels, int64_t frames,
                           int halo_frames, const c1_encode_options *opts, uint8_t *units);
-/* decode twin: every range starts from the unit(s) of the frame before it */
+/* decode twin: every range starts from the unit(s) of the frame before it.  It takes no context and has no decode model: the
+ * exact decoder always (c1_ctx_set_decode_model) */
 int c1_decode_batch_multi(const int *devices, int n_devices, const uint8_t *units, int channels, int64_t frames,
                           int halo_units, float *const *pcm);
 
@@ -815,8 +841,11 @@ typedef struct c1_dec_state {   /* 179 floats = 716 bytes */
  * (decode: units[i*212 ..] from in[i] into pcm[i*512 ..]).  out may be in (in place) or NULL; n == 0 writes nothing.  All
  * pools share opts: detection -- the frame's magnitudes are compared with in[i].transient_mags and written to out[i] -- or
  * fixed block modes, any mix of long and short, under which transient_mags passes through unchanged (encoder.js:130-132);
- * any supported allocation bias.  Number model: the reference's always (binary64 operations, binary32 at every typed-array
- * store): nothing is speculated and c1_ctx_set_decode_precision does not apply.  C1_ERR_ARG for a NULL pointer or n out of range. */
+ * any supported allocation bias.  Number model: encode, the reference's always (binary64 operations, binary32 at every
+ * typed-array store), nothing is speculated; decode, the reference's under the decode models C1_DECODE_EXACT and
+ * C1_DECODE_BINARY32_BULK, and binary32 under C1_DECODE_BINARY32 (c1_ctx_set_decode_model): PCM and out[i] are then what
+ * c1_decode_device computes in binary32 for the same unit after the same history, bit for bit.  C1_ERR_ARG for a NULL pointer
+ * or n out of range. */
 /* device pointers, asynchronous on the context's stream (the caller's-stream contract above); n 0 .. 2^27; pcm 16-byte
  * aligned, units (decode) and states 4-byte aligned.  The state is not checked: for non-finite entries the output is unspecified, and no access leaves the buffers. */
 int c1_encode_frames_from_states_device(c1_ctx *ctx, int64_t n, const float *pcm, const c1_enc_state *in,
@@ -841,9 +870,11 @@ int c1_decode_frames_from_states(c1_ctx *ctx, int64_t n, const uint8_t *units, c
  * How: the concatenation runs once through c1_encode_device / c1_decode_device as one mono stream; then the
  * first two frames of every signal (decode: the first frame) are computed again from in[i] by the from-state kernels, and the
  * pools are rebuilt from the last two frames (decode: the last unit) as c1_*_stream_get_state rebuilds them.
- * c1_ctx_set_decode_precision(1) applies to the bulk of a decode call; the first frame of every signal is still computed in
- * the reference's number model (binary64 operations, binary32 at every typed-array store), because the from-state kernel has
- * no other: that frame is bit-identical to the reference either way. */
+ * Decode models (c1_ctx_set_decode_model).  C1_DECODE_BINARY32_BULK applies to the bulk of a decode call; the first frame
+ * of every signal and the pools written to out are still computed in the reference's number model (binary64 operations,
+ * binary32 at every typed-array store): that frame is bit-identical to the reference.  Under C1_DECODE_BINARY32 the bulk, the
+ * first frames and the pools are all binary32: every signal is, bit for bit, its own c1_decode_device call under that model
+ * (from in[i]: the continuation of the binary32 stream in[i] came from). */
 /* device pointers -- pcm, units, in, out -- but frame_offsets, a HOST pointer that is read before the call returns.
  * Asynchronous on the context's stream (the caller's-stream contract above).  n 0 .. 2^20, frame_offsets[n] 0 .. 2^27; pcm
  * 16-byte aligned, units and states 4-byte aligned.  The states are not checked, as in c1_encode_frames_from_states_device.
@@ -907,7 +938,13 @@ int c1_encode_signals_measured(c1_ctx *ctx, int64_t n, const int64_t *frame_offs
  * entry is C1_ERR_ARG and leaves the stream as it was.  How: the two frames after an encoder restore, and the frame after a
  * decoder restore, run through the from-state kernels; from then on the stream's own PCM / unit history is real again
  * (all state after a frame is a function of that frame and the 138 samples before it; the decoder's, of that
- * frame's unit alone). */
+ * frame's unit alone).
+ * Decode models (c1_ctx_set_decode_model): a decoder stream reads its context's model at every call.  Under C1_DECODE_BINARY32
+ * pushes of units and of fields, in any interleaving and after a restore, all compute in binary32 and give the bits of one
+ * c1_decode_device call over the whole stream; under the other two models everything but the plain unit push is exact.
+ * get_state returns the pool the last frame left under the model that decoded it.  When the model went to or from
+ * C1_DECODE_BINARY32 between two pushes, the next push continues from that pool as after set_state: every frame is the
+ * from-state frame (c1_decode_frames_from_states) under the model in force, from the pool the frame before it left. */
 int c1_enc_stream_get_state(c1_enc_stream *s, c1_enc_state *out);
 int c1_enc_stream_set_state(c1_enc_stream *s, const c1_enc_state *in);
 int c1_dec_stream_get_state(c1_dec_stream *s, c1_dec_state *out);
@@ -975,7 +1012,8 @@ int c1_mdct_batch(c1_ctx *ctx, const float *bands, int64_t frames, int halo_fram
 
 /* The decoder's pipeline stages (codec/pipeline/decoder.js:52-389) and deserializeFrame, for `frames` (0 .. 2^20) consecutive
  * frames of one channel.  Host pointers, synchronous, like the two calls above; the reference's number model (binary64
- * operations, binary32 at every typed-array store) always: c1_ctx_set_decode_precision does not apply to them.
+ * operations, binary32 at every typed-array store) under every decode model: c1_ctx_set_decode_model and
+ * c1_ctx_set_decode_precision do not reach the single-stage exports, which have no binary32 form.
  * "Frame fields", int32 arrays per batch: nbfu[frames] (nBfu); block_modes[frames*3] (the three band modes); sfi[frames*52]
  * and wl[frames*52] (scale-factor and word-length index per BFU); quantized[frames*512] (BFU after BFU, SPECS_PER_BFU[b]
  * values each: slot order, where a long band's coefficients also sit). */
@@ -1083,8 +1121,13 @@ int c1_allocate_bits(c1_ctx *ctx, const double *data, int64_t data_len, const in
  * (the interleave of c1_unpack_units over stereo units).  halo_frames 0 or 1: one frame of fields per channel precedes each
  * pointer, the stream's previous frame, whose fields rebuild imdctOverlap and qmfDelays; without one the state is a fresh
  * BufferPool's zeros.  pcm[c] = frames * 512 samples.
- * Number model: the reference's always (binary64 operations, binary32 at every typed-array store); c1_ctx_set_decode_precision
- * does not apply.  Dequantization is Float32((q * SCALE_FACTORS[sfi]) / ((1 << (bits - 1)) - 1)) for any int32 q, with the
+ * Number model: the reference's (binary64 operations, binary32 at every typed-array store) under the decode models
+ * C1_DECODE_EXACT and C1_DECODE_BINARY32_BULK.  Under C1_DECODE_BINARY32 (c1_ctx_set_decode_model) the binary32 unit decoder's,
+ * operation for operation: dequantization is Float32(q * Float32(Float32(SCALE_FACTORS[sfi]) * Float32(1 / range))), the
+ * product also for sfi 0 (a zero with q's sign) and +0 for word length 0, and the later stages run in binary32; the fields
+ * c1_unpack_units makes of sound units then decode to the bits c1_decode_device gives for the units under that model, and
+ * fields no unit can carry stay within its error against the exact decode.  c1_dec_stream_push_fields follows
+ * the same rule.  Exact dequantization is Float32((q * SCALE_FACTORS[sfi]) / ((1 << (bits - 1)) - 1)) for any int32 q, with the
  * semantics of c1_dequantize_frames: entries at or above nBfu are never read, nor are the mantissas of BFUs with word length 0,
  * and a band is long only when its mode is exactly 0.
  * Domain: nbfu 0..52; below nbfu, wl 0..15 and sfi 0..63; block modes and mantissas any int32. */
