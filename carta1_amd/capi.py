@@ -214,6 +214,12 @@ SIGNATURES = {
     'c1_encode_signals_measured': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                              C.POINTER(EncodeOptions), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_signals_measured_modes_device': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                                          C.POINTER(EncodeOptions), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'c1_encode_signals_measured_modes': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                                   C.POINTER(EncodeOptions), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'c1_enc_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'c1_enc_stream_set_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'c1_dec_stream_get_state': (C.c_int, [C.c_void_p, C.c_void_p]),

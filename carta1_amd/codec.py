@@ -1105,6 +1105,60 @@ class Context:
             None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
             vp(units_ptr), vp(out_states_ptr), vp(taken_ptr), vp(shifts_ptr), vp(distortion_ptr), vp(energy_ptr), vp(weights_ptr)))
 
+    def encode_signals_measured_modes(self, signals, candidates, options=None, states=None, return_states=False, in_place=False,
+                                      scale_factor_offsets=None, return_distortion=False, return_shifts=False):
+        """encode_signals() with the measured block-mode search of encode_measured_modes() (c1_encode_signals_measured_modes):
+        signal i's rows are what EncoderStream.push_measured_modes reports for it in one push on a mono stream restored to
+        states[i] (or fresh).  candidates, scale_factor_offsets (None: the plain measured allocation), the return_* flags and
+        their ValueErrors are encode_measured_modes()'s.  Returns per-signal lists in encode_measured_modes()'s result order --
+        (units, choice, modes, taken[, shifts][, distortion, energy]) -- and last, with return_states or in_place, the (n, 483)
+        pools after every signal's last frame."""
+        pcm, off = signals_layout([pad_signal(x) for x in signals])
+        n = off.size - 1
+        total = int(off[-1])
+        st = None if states is None else _state_rows(states, capi.ENC_STATE_FLOATS, n)
+        if in_place and st is None:
+            raise ValueError('in_place needs states')
+        cand = mode_candidates(candidates)
+        count = len(cand)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
+        out = st if in_place else (np.zeros((n, capi.ENC_STATE_FLOATS), dtype=np.float32) if return_states else None)
+        units = np.zeros((total, 212), dtype=np.uint8)
+        choice = np.zeros(total, dtype=np.uint8)
+        modes = np.zeros(total, dtype=np.uint8)
+        taken = np.zeros(total, dtype=np.uint8)
+        shifts = np.zeros((total, 52), dtype=np.int8) if return_shifts else None
+        dist = np.zeros((total, count, 2), dtype=np.float64) if return_distortion else None
+        energy = np.zeros((total, count), dtype=np.float64) if return_distortion else None
+        opts = (options or EncoderOptions()).to_c()
+        data = lambda a: None if a is None else a.ctypes.data
+        capi.check(capi.load().c1_encode_signals_measured_modes(
+            self._h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), pcm.ctypes.data, data(st), C.byref(opts), cand.ctypes.data, count,
+            data(offs), 0 if offs is None else len(offs), units.ctypes.data, data(out), choice.ctypes.data, modes.ctypes.data,
+            taken.ctypes.data, data(shifts), data(dist), data(energy)))
+        res = (split_rows(units, off), split_rows(choice, off), split_rows(modes, off), split_rows(taken, off))
+        res = res + (split_rows(shifts, off),) if return_shifts else res
+        res = res + (split_rows(dist, off), split_rows(energy, off)) if return_distortion else res
+        return res + (out,) if (return_states or in_place) else res
+
+    def encode_signals_measured_modes_device(self, frame_offsets, pcm_ptr, candidates, units_ptr=None, states_ptr=None,
+                                             out_states_ptr=None, options=None, scale_factor_offsets=None, choice_ptr=None,
+                                             modes_ptr=None, taken_ptr=None, shifts_ptr=None, distortion_ptr=None, energy_ptr=None):
+        """c1_encode_signals_measured_modes_device: raw device pointers as for encode_signals_device; frame_offsets, the
+        candidates and the offsets are host values (as for encode_measured_modes_device, the library's own checks decide; None
+        for no offsets).  Every output may be None, not all; choice, modes and taken are uint8 [frames], shifts int8 [frames,
+        52], distortion float64 [frames, n, 2] and energy float64 [frames, n].  Asynchronous on the context's stream."""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        opts = (options or EncoderOptions()).to_c()
+        vp = lambda p: C.c_void_p(p) if p else None
+        cand = mode_candidates(candidates, check=False)
+        offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets, check=False)
+        capi.check(capi.load().c1_encode_signals_measured_modes_device(
+            self._h, off.size - 1, off.ctypes.data_as(C.POINTER(C.c_int64)), vp(pcm_ptr), vp(states_ptr), C.byref(opts),
+            cand.ctypes.data if len(cand) else None, len(cand), offs.ctypes.data if offs is not None and len(offs) else None,
+            0 if offs is None else len(offs), vp(units_ptr), vp(out_states_ptr), vp(choice_ptr), vp(modes_ptr), vp(taken_ptr),
+            vp(shifts_ptr), vp(distortion_ptr), vp(energy_ptr)))
+
     def decode_signals_device(self, frame_offsets, units_ptr, pcm_ptr, states_ptr=None, out_states_ptr=None):
         off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
         capi.check(capi.load().c1_decode_signals_device(
@@ -1835,11 +1889,14 @@ def aea_image_units(data):
     return units, nch
 
 
-def encode_aea_pcm_many(items, options=None, ctx=None, measured_allocation=False, scale_factor_offsets=None, masking=None):
+def encode_aea_pcm_many(items, options=None, ctx=None, measured_allocation=False, scale_factor_offsets=None, masking=None,
+                        measured_mode_candidates=None):
     """encode_aea_pcm for many items in one device call: items is a list of [L] or [L, R]; options.title may be one string
     or one per item.  Every result is byte for byte what encode_aea_pcm returns for that item alone.
     measured_allocation: the units of every item are Context.encode_measured's for that item alone (with scale_factor_offsets
-    and masking as there, which need it), through Context.encode_signals_measured."""
+    and masking as there, which need it), through Context.encode_signals_measured.
+    measured_mode_candidates (needs measured_allocation; with scale_factor_offsets or without, never with masking): the units
+    of every item are Context.encode_measured_modes' for that item alone, through Context.encode_signals_measured_modes."""
     options = dict(options or {})
     title = options.pop('title', 'encoded by carta1')
     titles = [title] * len(items) if isinstance(title, str) else list(title)
@@ -1847,8 +1904,19 @@ def encode_aea_pcm_many(items, options=None, ctx=None, measured_allocation=False
         raise ValueError('title must be one string or one per item')
     if not measured_allocation and (scale_factor_offsets is not None or masking is not None):
         raise ValueError('scale_factor_offsets and masking need measured_allocation')
+    if measured_mode_candidates is not None:
+        if not measured_allocation:
+            raise ValueError('measured_mode_candidates needs measured_allocation')
+        if masking is not None:
+            raise ValueError('measured_mode_candidates and masking cannot be combined: the mode search has no masking weights')
+        cand = mode_candidates(measured_mode_candidates)
+        if scale_factor_offsets is not None:
+            check_scale_factor_offsets(scale_factor_offsets)
     signals, counts = items_to_signals(items)
-    if measured_allocation:
+    if measured_mode_candidates is not None:
+        units = _ctx(ctx).encode_signals_measured_modes(signals, cand, options=EncoderOptions(options),
+                                                        scale_factor_offsets=scale_factor_offsets)[0]
+    elif measured_allocation:
         units = _ctx(ctx).encode_signals_measured(signals, options=EncoderOptions(options), scale_factor_offsets=scale_factor_offsets,
                                                   masking=masking)[0]
     else:

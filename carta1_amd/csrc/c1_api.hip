@@ -5344,6 +5344,211 @@ int encode_signals_measured_impl(c1_ctx *ctx, int64_t n, const int64_t *off, con
   return C1_OK;
 }
 
+// per-row staging of a mode search over signals, carved from c1_ctx::d_sig: a BestModesCall's outputs over W rows
+struct RowStageModes {
+  uint8_t *choice, *modes_out, *taken;
+  int8_t *shifts;
+  double *distortion, *energy;
+};
+
+// encode_rows_pass with the mode search of c1_encode_measured_modes_device (bm: candidates, offsets and the call's outputs over
+// the units of the concatenation): encode_from_states_modes over row lists.  Per chunk of W rows the from-state row kernel under
+// all-long options into the workspace's planes and under all-short options into the search's own (a plane no candidate needs is
+// not made), the pools advanced once, by the last of the two; per candidate the composed side record and the allocation chain
+// into trial record k; launch_measured_modes into the rows' staging, packing, and one launch that moves unit and outputs to
+// units[src[r]].  base: the call's options with neither threshold nor fixed modes.  units (and row_units) may be null
+int encode_rows_pass_modes(c1_ctx *ctx, const float *pcm, const uint32_t *src, const float *in, const uint32_t *in_rows, bool bcast,
+                           float *out, const uint32_t *out_rows, int64_t rows, int64_t W, const c1_encode_options *base,
+                           const BestModesCall *bm, const RowStageModes *st, uint8_t *units, uint8_t *row_units) {
+  int rc;
+  bool bm_long = false, bm_short = false;                      // some candidate codes a band long / short
+  for (int k = 0; k < bm->n; k++) {
+    if ((bm->cand[k] & 0x3f) != 0x3a) bm_long = true;
+    if ((bm->cand[k] & 0x3f) != 0) bm_short = true;
+  }
+  BestModesCall sm = *bm;                                      // the same definition, the outputs at the rows' staging
+  sm.choice = bm->choice ? st->choice : nullptr;
+  sm.modes_out = bm->modes_out ? st->modes_out : nullptr;
+  sm.taken = bm->taken ? st->taken : nullptr;
+  sm.shifts = bm->shifts ? st->shifts : nullptr;
+  sm.distortion = bm->distortion ? st->distortion : nullptr;
+  sm.energy = bm->energy ? st->energy : nullptr;
+  const int64_t trial_stride = ctx->trial_units * kAllocBytes;
+  for (int64_t r0 = 0; r0 < rows; r0 += W) {
+    const int64_t m = std::min(W, rows - r0);
+    for (int pass = 0; pass < 2; pass++) {                     // 0: all long, 1: all short
+      if (!(pass ? bm_short : bm_long)) continue;
+      c1_encode_options one = *base;
+      one.fixed_block_modes[0] = one.fixed_block_modes[1] = pass ? 2 : 0;
+      one.fixed_block_modes[2] = pass ? 3 : 0;
+      if ((rc = upload_opts(ctx, &one))) return rc;
+      const bool last = pass == 1 || !bm_short;                // the last pass leaves the pools
+      C1EncStateLaunch K;
+      memset(&K, 0, sizeof K);
+      K.pcm = pcm;
+      K.src_rows = src + r0;
+      K.in = (in_rows || bcast) ? in : in + r0 * kEncStateFloats;
+      K.in_rows = in_rows ? in_rows + r0 : nullptr;
+      K.in_broadcast = bcast ? 1 : 0;
+      K.out = !last ? nullptr : ((!out || out_rows) ? out : out + r0 * kEncStateFloats);
+      K.out_rows = (last && out_rows) ? out_rows + r0 : nullptr;
+      K.n = m;
+      K.tables = ctx->d_tables;
+      K.opts = ctx->d_opts;
+      K.coefs = pass ? ctx->d_bm_coefs : ctx->d_coefs[0];
+      K.side = pass ? ctx->d_bm_side : ctx->d_side[0];
+      K.detect = -1;
+      ScopedTiming t(ctx, K_SIGNAL_STARTS);
+      c1k_launch_encode_rows(K, ctx->stream);
+    }
+    C1EncodeLaunch L;
+    memset(&L, 0, sizeof L);
+    L.channels = 1;
+    L.frames = m;
+    L.tables = ctx->d_tables;
+    L.opts = ctx->d_opts;
+    L.coefs = ctx->d_coefs[0];
+    L.side = ctx->d_side[0];
+    L.alloc = ctx->d_alloc[0];
+    L.cand = ctx->d_cand[0];
+    L.work_count = ctx->d_work[0];
+    L.work_list = ctx->d_work[0] + 4;
+    L.sel_list = ctx->d_work[0] + 4 + (size_t)ctx->ws_units * 7;
+    L.units = row_units;
+    for (int k = 0; k < bm->n; k++) {                          // one chain after the other: they share the side plane and the scratch
+      { ScopedTiming t(ctx, K_ANALYSIS); c1k_launch_compose_side(L.side, ctx->d_bm_side, m, bm->cand[k], ctx->d_bm_cand_side, ctx->stream); }
+      ScopedTiming t(ctx, K_ALLOCATE);
+      C1EncodeLaunch A = L;
+      A.side = ctx->d_bm_cand_side;
+      A.alloc = ctx->d_trial + (size_t)k * trial_stride;
+      c1k_launch_allocate(A, ctx->stream);
+    }
+    launch_measured_modes(ctx, L, ctx->d_trial, trial_stride, &sm, 0, ctx->stream);
+    if (row_units) { ScopedTiming t(ctx, K_PACK); c1k_launch_pack(L, false, ctx->stream); }
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    C1ScatterRowsModesLaunch X;
+    memset(&X, 0, sizeof X);
+    X.dst_rows = src + r0;
+    X.n = m;
+    X.n_cand = bm->n;
+    if (row_units) { X.units_src = reinterpret_cast<const uint32_t *>(row_units); X.units_dst = reinterpret_cast<uint32_t *>(units); }
+    if (bm->choice) { X.choice_src = st->choice; X.choice_dst = bm->choice; }
+    if (bm->modes_out) { X.modes_src = st->modes_out; X.modes_dst = bm->modes_out; }
+    if (bm->taken) { X.taken_src = st->taken; X.taken_dst = bm->taken; }
+    if (bm->shifts) { X.shifts_src = reinterpret_cast<const uint32_t *>(st->shifts); X.shifts_dst = reinterpret_cast<uint32_t *>(bm->shifts); }
+    if (bm->distortion) { X.distortion_src = reinterpret_cast<const uint32_t *>(st->distortion); X.distortion_dst = reinterpret_cast<uint32_t *>(bm->distortion); }
+    if (bm->energy) { X.energy_src = reinterpret_cast<const uint32_t *>(st->energy); X.energy_dst = reinterpret_cast<uint32_t *>(bm->energy); }
+    c1k_launch_scatter_signal_rows_modes(X, ctx->stream);
+  }
+  return C1_OK;
+}
+
+// encode_signals_impl with the measured block-mode search: device pointers but frame_offsets; arguments checked by
+// the callers.  bm: the call's candidates, offsets (set) and outputs, over the units of the concatenation.  units may be null.
+// Both settings of C1_SIGNAL_STARTS take the two-pass route
+int encode_signals_measured_modes_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const float *pcm, const float *in,
+                                       const c1_encode_options *opts, const BestModesCall *bm, uint8_t *units, float *out) {
+  int rc;
+  TimingScope scope(ctx);
+  const int64_t total = off[n];
+  c1_encode_options base;
+  modes_call_opts(*opts, &base);
+  // 1. the whole concatenation as one mono stream, as c1_encode_measured_modes_device runs it: every row but those of the first
+  //    two frames of a signal is final
+  const float *chan[1] = {pcm};
+  if ((rc = encode_device_impl(ctx, chan, 1, total, 0, &base, units, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, bm))) return rc;
+  int64_t nA = 0, nB = 0, nC = 0, nZ = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t len = off[i + 1] - off[i];
+    nA += len >= 1; nB += len >= 2; nC += len >= 3; nZ += len == 0;
+  }
+  const bool copy_empty = out && out != in && nZ > 0;
+  if (nA == 0 && !copy_empty) return C1_OK;
+  if (!out) nC = 0;
+  // index lists, as encode_signals_impl's: A = signals of >= 1 frame (frame 0), B = of >= 2 (frame 1), C = of >= 3 (the last
+  // two frames), Z = empty ones
+  const size_t words = (size_t)(2 * nA + 3 * nB + 3 * nC + nZ);
+  uint32_t *h;
+  if ((rc = rows_image(ctx, words, &h))) return rc;
+  uint32_t *a_src = h, *a_sig = a_src + nA, *b_src = a_sig + nA, *b_sig = b_src + nB, *b_row = b_sig + nB, *c_src0 = b_row + nB,
+           *c_src1 = c_src0 + nC, *c_sig = c_src1 + nC, *z_sig = c_sig + nC;
+  {
+    int64_t a = 0, b = 0, c = 0, z = 0;
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t f0 = off[i], len = off[i + 1] - f0;
+      if (len == 0) { z_sig[z++] = (uint32_t)i; continue; }
+      if (len >= 2) { b_src[b] = (uint32_t)(f0 + 1); b_sig[b] = (uint32_t)i; b_row[b] = (uint32_t)a; b++; }
+      if (len >= 3 && out) { c_src0[c] = (uint32_t)(f0 + len - 2); c_src1[c] = (uint32_t)(f0 + len - 1); c_sig[c] = (uint32_t)i; c++; }
+      a_src[a] = (uint32_t)f0; a_sig[a] = (uint32_t)i; a++;
+    }
+  }
+  // a chunk of W rows: the workspace, the second planes, the candidate side plane and a trial record per unit and candidate
+  int64_t W = 0;
+  if (nA > 0) {
+    if ((rc = join_tail(ctx))) return rc;
+    W = std::min(nA, chunk_for_call(ctx, nA, 1, false, bm->n, true));
+    if ((rc = ensure_workspace(ctx, W))) return rc;
+    if ((rc = ensure_trial_allocs(ctx, W, bm->n))) return rc;
+    if ((rc = ensure_best_modes_planes(ctx, W))) return rc;
+  }
+  SigCarve cv;
+  const size_t o_zero = cv.take(sizeof(c1_enc_state)), o_lists = cv.take(words * sizeof(uint32_t)),
+               o_tmp = cv.take(out ? 0 : (size_t)nA * sizeof(c1_enc_state)), o_tmp2 = cv.take((size_t)nC * sizeof(c1_enc_state)),
+               o_units = cv.take((size_t)W * C1_UNIT_BYTES), o_choice = cv.take((size_t)W), o_modes = cv.take((size_t)W),
+               o_taken = cv.take((size_t)W), o_shifts = cv.take((size_t)W * 52),
+               o_dist = cv.take((size_t)W * bm->n * 2 * sizeof(double)), o_energy = cv.take((size_t)W * bm->n * sizeof(double));
+  if ((rc = ensure_sig(ctx, cv.bytes))) return rc;
+  uint8_t *base_p = static_cast<uint8_t *>(ctx->d_sig);
+  float *zero = reinterpret_cast<float *>(base_p + o_zero), *tmp = reinterpret_cast<float *>(base_p + o_tmp), *tmp2 = reinterpret_cast<float *>(base_p + o_tmp2);
+  uint32_t *d = reinterpret_cast<uint32_t *>(base_p + o_lists);
+  const uint32_t *da_src = d, *da_sig = da_src + nA, *db_src = da_sig + nA, *db_sig = db_src + nB, *db_row = db_sig + nB, *dc_src0 = db_row + nB,
+                 *dc_src1 = dc_src0 + nC, *dc_sig = dc_src1 + nC, *dz_sig = dc_sig + nC;
+  const RowStageModes st = {base_p + o_choice, base_p + o_modes, base_p + o_taken, reinterpret_cast<int8_t *>(base_p + o_shifts),
+                            reinterpret_cast<double *>(base_p + o_dist), reinterpret_cast<double *>(base_p + o_energy)};
+  uint8_t *row_units = units ? base_p + o_units : nullptr;
+  HIP_TRY(hipMemsetAsync(zero, 0, sizeof(c1_enc_state), ctx->stream));
+  if ((rc = upload_rows(ctx, d, words))) return rc;
+  // the pools in flight live in `out` at their signal's index, or in scratch at their row of list A when out is NULL
+  float *S = out ? out : tmp;
+  // 2. frame 0 of every signal from in[i] (a fresh pool when in is NULL)
+  if ((rc = encode_rows_pass_modes(ctx, pcm, da_src, in ? in : zero, in ? da_sig : nullptr, !in, (out || nB) ? S : nullptr, out ? da_sig : nullptr,
+                                   nA, W, &base, bm, &st, units, row_units))) return rc;
+  // 3. frame 1 from the pool step 2 left, in place
+  if ((rc = encode_rows_pass_modes(ctx, pcm, db_src, S, out ? db_sig : db_row, false, S, out ? db_sig : db_row, nB, W, &base, bm, &st, units,
+                                   row_units))) return rc;
+  if (out) {
+    // 4. signals of three frames and more: the pool after the last frame is a function of the last two frames (state only, from
+    //    zeros: c1_enc_stream_get_state does the same); the modes are given, so transient_mags keeps what steps 2 and 3 passed through
+    C1EncStateLaunch K;
+    memset(&K, 0, sizeof K);
+    K.pcm = pcm;
+    K.src_rows = dc_src0;
+    K.in = zero;
+    K.in_broadcast = 1;
+    K.out = tmp2;
+    K.n = nC;
+    K.tables = ctx->d_tables;
+    K.opts = ctx->d_opts;
+    K.state_only = 1;
+    K.detect = 0;                                          // the zero pool's magnitudes pass through: every float of tmp2 is written
+    ScopedTiming t(ctx, K_SIGNAL_STARTS);
+    c1k_launch_encode_rows(K, ctx->stream);
+    K.src_rows = dc_src1;
+    K.in = tmp2;
+    K.in_broadcast = 0;
+    K.out = out;
+    K.out_rows = dc_sig;
+    K.keep_mags = 1;
+    c1k_launch_encode_rows(K, ctx->stream);
+    // empty signals: the pool passes through
+    if (copy_empty)
+      c1k_launch_copy_rows(reinterpret_cast<uint32_t *>(out), dz_sig, reinterpret_cast<const uint32_t *>(in ? in : zero), in ? dz_sig : nullptr,
+                           in ? 0 : 1, nZ, kEncStateFloats, ctx->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
 int decode_signals_impl(c1_ctx *ctx, int64_t n, const int64_t *off, const uint8_t *units, const float *in, float *pcm, float *out) {
   int rc;
   TimingScope scope(ctx);
@@ -5590,6 +5795,106 @@ int c1_encode_signals_measured(c1_ctx *ctx, int64_t n, const int64_t *frame_offs
   if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (shifts && !d_shifts && T) memset(shifts, 0, T * 52);     // c1_encode_measured_*: no index moves
+  return C1_OK;
+}
+
+namespace {
+// what the arguments of c1_encode_signals_measured_modes* decide alone, as c1_enc_stream_push_measured_modes judges them
+int check_signals_measured_modes_args(const char *what, const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand,
+                                      const int8_t *sf_offsets, int n_offsets) {
+  int rc;
+  if ((rc = check_mode_candidates(what, cand_modes, n_cand))) return rc;
+  if (!sf_offsets && n_offsets != 0) return fail(C1_ERR_ARG, "%s: n_offsets = %d, but sf_offsets is NULL", what, n_offsets);
+  if (sf_offsets && (rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  return check_measured_opts(what, opts, false);
+}
+}  // namespace
+
+int c1_encode_signals_measured_modes_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                                            const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                            int n_offsets, uint8_t *units, c1_enc_state *out, uint8_t *choice, uint8_t *modes_out,
+                                            uint8_t *taken, int8_t *shifts, double *distortion, double *energy) {
+  const char *const what = "c1_encode_signals_measured_modes_device";
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_signals_measured_modes_args(what, opts, cand_modes, n_cand, sf_offsets, n_offsets))) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets(what, n, frame_offsets, kMaxSignalFrames, &total))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy)
+    return fail(C1_ERR_ARG, "%s: units, choice, modes_out, taken, shifts, distortion and energy are all NULL", what);
+  if (total > 0 && !pcm) return fail(C1_ERR_ARG, "%s: pcm is NULL", what);
+  if ((uintptr_t)pcm & 15) return fail(C1_ERR_ARG, "%s: pcm must be 16-byte aligned on the device", what);
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)units | (uintptr_t)shifts) & 3) return fail(C1_ERR_ARG, "%s: units, states and shifts must be 4-byte aligned on the device", what);
+  if (((uintptr_t)distortion | (uintptr_t)energy) & 7) return fail(C1_ERR_ARG, "%s: distortion and energy must be 8-byte aligned on the device", what);
+  static const int8_t kOwnIndex[1] = {0};                      // no offsets: the search over the plain measured allocation
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's arrays may change while the call runs
+  int8_t offs[C1_MAX_SF_OFFSETS];
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  if (sf_offsets) memcpy(offs, sf_offsets, (size_t)n_offsets);
+  BestModesCall bm = {n_cand, cand, choice, modes_out, distortion, energy};
+  bm.sf_offsets = sf_offsets ? offs : kOwnIndex;
+  bm.n_offsets = sf_offsets ? n_offsets : 1;
+  bm.taken = taken;
+  bm.shifts = shifts;                                          // a single offset 0 moves no index: zeros
+  return encode_signals_measured_modes_impl(ctx, n, frame_offsets, pcm, reinterpret_cast<const float *>(in), opts, &bm, units,
+                                            reinterpret_cast<float *>(out));
+}
+
+int c1_encode_signals_measured_modes(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                                     const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                     int n_offsets, uint8_t *units, c1_enc_state *out, uint8_t *choice, uint8_t *modes_out, uint8_t *taken,
+                                     int8_t *shifts, double *distortion, double *energy) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_encode_signals_measured_modes";
+  int rc;
+  if ((rc = check_signals_measured_modes_args(what, opts, cand_modes, n_cand, sf_offsets, n_offsets))) return rc;
+  int64_t total = 0;
+  if ((rc = check_frame_offsets(what, n, frame_offsets, kMaxSignalFramesHost, &total))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy)
+    return fail(C1_ERR_ARG, "%s: units, choice, modes_out, taken, shifts, distortion and energy are all NULL", what);
+  if (total > 0 && !pcm) return fail(C1_ERR_ARG, "%s: pcm is NULL", what);
+  if (in && (rc = check_states_finite(what, "signal", in, n, kEncStateFloats, kEncStateFields, 5))) return rc;
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (n == 0) return C1_OK;
+  // from here on only the device can fail
+  DeviceScratch ds;
+  float *dp, *dst = nullptr; uint8_t *du = nullptr, *d_choice = nullptr, *d_modes = nullptr, *d_taken = nullptr; int8_t *d_shifts = nullptr;
+  double *d_dist = nullptr, *d_energy = nullptr;
+  const size_t T = (size_t)total, N = (size_t)n, C = (size_t)n_cand;
+  if ((rc = ds.alloc(&dp, T * 512))) return rc;
+  if (units && (rc = ds.alloc(&du, T * C1_UNIT_BYTES))) return rc;
+  if ((in || out) && (rc = ds.alloc(&dst, N * kEncStateFloats))) return rc;
+  if (choice && (rc = ds.alloc(&d_choice, T))) return rc;
+  if (modes_out && (rc = ds.alloc(&d_modes, T))) return rc;
+  if (taken && (rc = ds.alloc(&d_taken, T))) return rc;
+  if (shifts && (rc = ds.alloc(&d_shifts, T * 52))) return rc;
+  if (distortion && (rc = ds.alloc(&d_dist, T * C * 2))) return rc;
+  if (energy && (rc = ds.alloc(&d_energy, T * C))) return rc;
+  if (T) HIP_TRY(hipMemcpyAsync(dp, pcm, T * 512 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, N * sizeof(c1_enc_state), hipMemcpyHostToDevice, ctx->stream));
+  static const int8_t kOwnIndex[1] = {0};                      // no offsets: the search over the plain measured allocation
+  BestModesCall bm = {n_cand, cand_modes, d_choice, d_modes, d_dist, d_energy};
+  bm.sf_offsets = sf_offsets ? sf_offsets : kOwnIndex;
+  bm.n_offsets = sf_offsets ? n_offsets : 1;
+  bm.taken = d_taken;
+  bm.shifts = d_shifts;
+  if ((rc = encode_signals_measured_modes_impl(ctx, n, frame_offsets, dp, in ? dst : nullptr, opts, &bm, du, out ? dst : nullptr))) return rc;
+  if (units && T) HIP_TRY(hipMemcpyAsync(units, du, T * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (choice && T) HIP_TRY(hipMemcpyAsync(choice, d_choice, T, hipMemcpyDeviceToHost, ctx->stream));
+  if (modes_out && T) HIP_TRY(hipMemcpyAsync(modes_out, d_modes, T, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken && T) HIP_TRY(hipMemcpyAsync(taken, d_taken, T, hipMemcpyDeviceToHost, ctx->stream));
+  if (shifts && T) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, T * 52, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion && T) HIP_TRY(hipMemcpyAsync(distortion, d_dist, T * C * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy && T) HIP_TRY(hipMemcpyAsync(energy, d_energy, T * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, dst, N * sizeof(c1_enc_state), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return C1_OK;
 }
 

@@ -258,6 +258,21 @@ struct C1ScatterRowsLaunch {
   const uint32_t *energy_src; uint32_t *energy_dst;
   const uint32_t *weights_src; uint32_t *weights_dst;
 };
+// The same for the rows of a measured mode search (k_scatter_signal_rows_modes, c1_k_signal_rows_modes.hip): per row 53 dwords of
+// a sound unit, one byte each of choice, modes_out and taken, 13 dwords of shifts, 4 * n_cand of distortion and 2 * n_cand of
+// energy (n_cand 1 .. C1_MAX_MODE_CANDIDATES; the kernel clamps it)
+struct C1ScatterRowsModesLaunch {
+  const uint32_t *dst_rows;
+  int64_t n;
+  int n_cand;
+  const uint32_t *units_src; uint32_t *units_dst;
+  const uint8_t *choice_src; uint8_t *choice_dst;
+  const uint8_t *modes_src; uint8_t *modes_dst;
+  const uint8_t *taken_src; uint8_t *taken_dst;
+  const uint32_t *shifts_src; uint32_t *shifts_dst;
+  const uint32_t *distortion_src; uint32_t *distortion_dst;
+  const uint32_t *energy_src; uint32_t *energy_dst;
+};
 
 // Run length of the frame-walking kernels: consecutive frames of one channel a wave walks, carrying the filter state
 // (one extra warm-up frame per run).  Measured on MI355X (1 M stereo frames, A/B in one session): 64-frame runs beat
@@ -480,6 +495,8 @@ void c1k_launch_copy_rows(uint32_t *dst, const uint32_t *dst_rows, const uint32_
 // the first one or two frames of n signals in one pass, and the rows of a signals call to their places (c1_k_signal_starts.hip)
 void c1k_launch_signal_starts(const C1SignalStartsLaunch &L, hipStream_t stream);
 void c1k_launch_scatter_signal_rows(const C1ScatterRowsLaunch &L, hipStream_t stream);
+// the rows of a measured mode search over n signals to their places (c1_k_signal_rows_modes.hip)
+void c1k_launch_scatter_signal_rows_modes(const C1ScatterRowsModesLaunch &L, hipStream_t stream);
 // performFFT's magnitudes of `rows` stored band rows (512 floats each) into the transient_mags of states[0 .. rows)
 void c1k_launch_state_mags(const C1DevTables *tables, const float *bands, int64_t rows, float *states, hipStream_t stream);
 // kind_mask: bit k = fill the 512-frame segments with (segment & 3) == k (15 = all)

@@ -792,6 +792,36 @@ napi_value EncodeSignalsMeasured(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encodeSignalsMeasuredModes(ctx, Float32Array pcm, Float64Array frameOffsets, options, Uint8Array candidates, Int8Array offsets |
+// null) -> Uint8Array(frames * 212): encodeSignals with the measured block-mode search of encodeMeasuredModes (offsets null: the
+// plain measured allocation), every signal from a fresh pool: c1_encode_signals_measured_modes
+napi_value EncodeSignalsMeasuredModes(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_ctx *ctx;
+  void *d, *cand = nullptr, *offsets = nullptr;
+  size_t samples, n_cand = 0, n_offsets = 0;
+  std::vector<int64_t> off;
+  c1_encode_options o;
+  if (!get_external(env, argv[0], &ctx) || !get_typed(env, argv[1], napi_float32_array, &d, &samples) ||
+      !get_frame_offsets(env, argv[2], &off) || !get_options(env, argv[3], &o) ||
+      !get_typed(env, argv[4], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  napi_valuetype t;
+  NAPI_OK(napi_typeof(env, argv[5], &t));
+  if (t != napi_null && t != napi_undefined && !get_typed(env, argv[5], napi_int8_array, &offsets, &n_offsets)) return nullptr;
+  if (n_cand < 1 || n_cand > C1_MAX_MODE_CANDIDATES) { napi_throw_range_error(env, nullptr, "candidates must hold 1 to 8 mode bytes"); return nullptr; }
+  if (samples % 512 || (uint64_t)off.back() != samples / 512) { napi_throw_type_error(env, nullptr, "pcm must hold frameOffsets[n] frames of 512 samples"); return nullptr; }
+  if (n_offsets > 64) n_offsets = 64;                           // the library's own check names the limit
+  uint8_t *units;
+  napi_value out = make_u8(env, (samples / 512) * C1_UNIT_BYTES, &units);
+  if (!out) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  const int rc = c1_encode_signals_measured_modes(ctx, (int64_t)off.size() - 1, off.data(), static_cast<const float *>(d), nullptr, &o,
+                                                  static_cast<const uint8_t *>(cand), (int)n_cand, static_cast<const int8_t *>(offsets),
+                                                  offsets ? (int)n_offsets : 0, units, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 // decodeSignals(ctx, Uint8Array units, Float64Array frameOffsets) -> Float32Array(frames * 512)
 napi_value DecodeSignals(napi_env env, napi_callback_info info) {
   napi_value argv[3];
@@ -1603,6 +1633,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"decodeBatchAsync", nullptr, DecodeBatchAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeSignals", nullptr, EncodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeSignalsMeasured", nullptr, EncodeSignalsMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeSignalsMeasuredModes", nullptr, EncodeSignalsMeasuredModes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeSignals", nullptr, DecodeSignals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamCreate", nullptr, EncStreamCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -217,6 +217,16 @@ export function modeCandidateBytes(candidates) {
   })
 }
 
+// c1_encode_signals_measured_modes on the default context: encodeMeasuredModes for n independent mono signals of any lengths in one
+// call, every signal from a fresh pool.  pcm and frameOffsets as for encodeSignalsMeasured; candidates and scaleFactorOffsets
+// (null: the plain measured allocation) as for encodeMeasuredModes.  Returns the units, Uint8Array(frames * 212): signal i's are
+// what encodeMeasuredModes gives for it alone.
+export function encodeSignalsMeasuredModes(pcm, frameOffsets, nativeOptions, candidates, scaleFactorOffsets = null, ctx = context()) {
+  const bytes = modeCandidateBytes(candidates)
+  const offsets = scaleFactorOffsets === null || scaleFactorOffsets === undefined ? null : checkScaleFactorOffsets(scaleFactorOffsets)
+  return native().encodeSignalsMeasuredModes(ctx, pcm, frameOffsets, nativeOptions, bytes, offsets)
+}
+
 // c1_encode_measured_modes_batch on the default context: encodeMeasured with the block modes of every sound unit chosen among the
 // candidates by the final error of the measured allocation under each -- per (unit, candidate) the figures of encodeMeasured under
 // that constant byte, the candidate of least T_final = taken ? T(n*) : T_ref wins, the first on a tie.  nativeOptions:

@@ -928,6 +928,42 @@ int c1_encode_signals_measured(c1_ctx *ctx, int64_t n, const int64_t *frame_offs
                                const double *mask_floor, const double *mask_spread, uint8_t *units, c1_enc_state *out,
                                uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights);
 
+/* c1_encode_signals* with the measured block-mode search: layout, pools, in / out (NULL, or in place) and empty
+ * signals as in c1_encode_signals*, frame_offsets with n + 1 entries, a stereo file two signals.  cand_modes, n_cand (1 to 8
+ * distinct bytes of the domain), sf_offsets and n_offsets are c1_enc_stream_push_measured_modes': sf_offsets NULL with n_offsets 0
+ * is the search over the plain measured allocation, and shifts is then zeros; n_offsets != 0 without offsets is C1_ERR_ARG.  The
+ * per-unit outputs have c1_encode_measured_modes_*'s shapes, indexed by frame of the concatenation: choice, modes_out and taken
+ * one entry per unit, shifts 52, distortion 2 * n_cand (unit-major), energy n_cand; each may be NULL, and so may units, as long as
+ * one output is asked for.  There are no masking tables: each candidate's thresholds would come from a different spectrum, and
+ * nothing has shown their ratios comparable across modes.
+ * Definition, by composition: the rows of signal i -- units and all six outputs, doubles as bit patterns -- are what
+ * c1_enc_stream_push_measured_modes reports for signal i's frames in one push on a mono stream created with opts and restored to
+ * in[i] with c1_enc_stream_set_state (or fresh), under the same candidates and offsets, and out[i] is that stream's
+ * c1_enc_stream_get_state: what a stream holds after c1_enc_stream_push_modes of modes_out, transient_mags passing from in[i] to
+ * out[i].  Of opts only what the measured calls read under given modes is read: neither the threshold nor the fixed modes.
+ * Nothing depends on the neighbouring signals, on chunking, on the speculation mode, on C1_SIGNAL_STARTS or on which measuring
+ * kernel a launch takes (C1_MEASURED_WIDE).
+ * How: the concatenation runs once as c1_encode_measured_modes_device runs it; the first two frames of every signal are computed
+ * again from in[i] -- the from-state kernel under all-long and under all-short options, the allocation chain per candidate, the
+ * search, packing -- frame 1 from the pool frame 0 left, and one launch per chunk of rows moves their units and outputs to their
+ * places.  Both settings of C1_SIGNAL_STARTS take this two-pass route.
+ * Device form: device pointers but frame_offsets, cand_modes and sf_offsets, which are HOST pointers read before the call
+ * returns.  Asynchronous on the context's stream under the contracts of c1_encode_signals_device and
+ * c1_encode_measured_modes_device.  Limits, the tighter of the calls composed: n 0 .. 2^20, frame_offsets[n] 0 .. 2^27; pcm
+ * 16-byte aligned; units, states and shifts 4-byte, distortion and energy 8-byte aligned.  States are not checked. */
+int c1_encode_signals_measured_modes_device(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets /* host */, const float *pcm,
+                                            const c1_enc_state *in, const c1_encode_options *opts, const uint8_t *cand_modes /* host */,
+                                            int n_cand, const int8_t *sf_offsets /* host */, int n_offsets, uint8_t *units,
+                                            c1_enc_state *out, uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts,
+                                            double *distortion, double *energy);
+/* host pointers, synchronous; frame_offsets[n] 0 .. 2^22.  What the arguments alone decide is decided first and needs neither a
+ * context nor a device: the candidates, the offsets, the options, frame_offsets, a non-finite state entry (naming its signal and
+ * field), all outputs NULL.  A rejected call writes nothing. */
+int c1_encode_signals_measured_modes(c1_ctx *ctx, int64_t n, const int64_t *frame_offsets, const float *pcm, const c1_enc_state *in,
+                                     const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                     int n_offsets, uint8_t *units, c1_enc_state *out, uint8_t *choice, uint8_t *modes_out,
+                                     uint8_t *taken, int8_t *shifts, double *distortion, double *energy);
+
 /* Snapshot and restore of a stream: host pointers, `channels` entries.  get_state returns what the reference's pool would hold
  * after the same calls -- pushes, option changes and earlier restores; every field zero on a fresh stream.  transient_mags is
  * the spectrum of the last frame detection ran on: the last pushed frame while detection is on, the kept frame after a switch
