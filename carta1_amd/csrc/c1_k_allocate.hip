@@ -33,10 +33,18 @@ namespace {
 // rank(a) > rank(b)  <=>  a > (b | kLow): one integer compare, no field extraction.  Rank 0 never occurs
 // in a live entry, so unused slots (kSentinel: rank 0) and parked entries (below) act as sentinels: no bounds checks in the sift.
 //
-// Heaps live in LDS as heap[slot][lane] (64 dwords per slot: conflict-free, the two children of a node one
+// Heaps live in LDS as heap[row][lane] (64 dwords per row: conflict-free, the two children of a node one
 // ds_read2st64 apart).  An entry that leaves the heap is parked, rank cleared, in the slot the shrinking
 // heap frees, so when the loop ends slots [0, initial size) hold every BFU with its final word length.
-constexpr int kHeapSlotsPerLane = 52 + 1;   // + one sentinel slot behind the last (13 568 bytes per wave: 12 waves per CU; 54 rows leave 11)
+// Slots 0..2 (the root and its children) live in registers from the construction to the word-length gather and have
+// no row: row r holds slot r + 3, and the last row is the sentinel behind slot 51.  The children of the slot in row q
+// are rows 2q + 4 and 2q + 5, its grandchildren rows 4q + 12 .. 4q + 15.
+// 50 rows are 12 800 bytes, and a CU hands out its LDS in 128 blocks of 1 280 bytes: 10 blocks per single-wave
+// workgroup, 12 workgroups per CU.  (With a row per slot, 53 rows = 13 568 bytes took 11 blocks: 11 waves per CU,
+// not the 12 this comment claimed before.)
+constexpr int kHeapRows = 52 - 3 + 1;
+constexpr int kHeapLdsBytes = kHeapRows * 64 * 4;
+static_assert((kHeapLdsBytes + 1279) / 1280 * 12 <= 128, "heaps: 12 single-wave workgroups per CU = at most 10 LDS blocks of 1 280 bytes each");
 constexpr uint32_t kLow = 0x1FFFFFu;
 constexpr uint32_t kSentinel = 52u;           // rank 0, word length 0, "BFU 52": the gather behind the heap run sends it to the spare slot
 constexpr int kCandBytes = kCandidateBytes;  // per unit: 8 totals (double) + 8 x 32-byte results + 8 lower bounds
@@ -46,26 +54,41 @@ __device__ __forceinline__ uint32_t heap_entry(uint32_t rank, int size, int s, i
   return (rank << 21) | ((uint32_t)size << 16) | ((uint32_t)s << 10) | ((uint32_t)wl << 6) | (uint32_t)b;
 }
 
-// siftDown (bitallocation.js:314-341) for every lane of the wave at once.  `el`,`er` are the already
-// loaded children of `i`; lanes finish at different depths, the loop runs while any lane still moves.
-__device__ __forceinline__ void heap_sift_down(uint32_t *hp, int sentinel, int i, uint32_t v, uint32_t el,
-                                               uint32_t er, bool active) {
+// siftDown (bitallocation.js:314-341) for every lane of the wave at once, from a slot `i` >= 3 (one that has a row).
+// `el`,`er` are the already loaded children of `i`; lanes finish at different depths, the loop runs while any lane still moves.
+__device__ __forceinline__ void heap_sift_down(uint32_t *hp, int i, uint32_t v, uint32_t el, uint32_t er, bool active) {
   const uint32_t vmax = v | kLow;
   for (;;) {
     const uint32_t m = max(el | kLow, vmax);
     const bool take_r = er > m;                    // pr > max(pl, pv)
     const bool take_l = !take_r && el > vmax;      // pl > pv
     const bool moved = active && (take_r || take_l);
-    if (active) hp[i * 64] = moved ? (take_r ? er : el) : v;   // a lane that stops here drops v into place
+    if (active) hp[(i - 3) * 64] = moved ? (take_r ? er : el) : v;   // a lane that stops here drops v into place
     active = moved;
     if (__builtin_amdgcn_ballot_w64(active) == 0) break;
     i = moved ? 2 * i + 1 + (take_r ? 1 : 0) : i;
     // children 2i+1, 2i+2; a node without children reads (slot 51, sentinel) and its left value is masked
     const int l = 2 * i + 1;
-    const uint32_t *src = hp + min(l, sentinel - 1) * 64;
-    el = l < sentinel ? src[0] : 0u;
+    const uint32_t *src = hp + (min(l, 51) - 3) * 64;
+    el = l < 52 ? src[0] : 0u;
     er = src[64];
   }
+}
+
+// the same from slot `k` = 1 or 2, which lives in a register and holds `v`: returns what the slot holds afterwards.
+// Its children are slots 3,4 or 5,6 = rows 2k - 2, 2k - 1.
+__device__ __forceinline__ uint32_t heap_sift_below_root(uint32_t *hp, int k, uint32_t v, bool active) {
+  const uint32_t *src = hp + (2 * k - 2) * 64;
+  const uint32_t el = src[0], er = src[64];
+  const uint32_t vmax = v | kLow;
+  const bool take_r = er > max(el | kLow, vmax);
+  const bool take_l = !take_r && el > vmax;
+  const bool moved = active && (take_r || take_l);
+  if (__builtin_amdgcn_ballot_w64(moved) != 0) {
+    const int i = 2 * k + 1 + (take_r ? 1 : 0);                       // 3..6: its children are slots 7..14
+    heap_sift_down(hp, i, v, hp[(2 * i + 1 - 3) * 64], hp[(2 * i + 2 - 3) * 64], moved);
+  }
+  return moved ? (take_r ? er : el) : v;
 }
 
 // kSpecs as compile-time constants: in the 52-way unrolled loops below a size is then part of an immediate, where the
@@ -95,10 +118,11 @@ __device__ __forceinline__ void reopen(uint32_t (&sf)[13]) {
 // chooses between two instances so that neither carries the other's code: ranks by the integer form, where a
 // successful step is ONE addition to the root's entry (rank_step0 / rank_step, verified on the host for every
 // (sfi, wl)), or ranks looked up in the table of the Float32 priorities.
-// During the spending loop the three top slots of the heap live in registers (r0 = root, r1/r2 = its
-// children): most steps end at the root (equal priorities do not move, :325-331), so they touch no memory.
+// The three top slots of the heap live in registers (r0 = root, r1/r2 = its children) and are handed back in them:
+// most steps end at the root (equal priorities do not move, :325-331), so they touch no memory.
 template <bool AFFINE>
-__device__ __forceinline__ void heap_phase(uint32_t *hp, int n, const uint32_t (&sf)[13], const C1DevEncOpts *O, bool live) {
+__device__ __forceinline__ void heap_phase(uint32_t *hp, int n, const uint32_t (&sf)[13], const C1DevEncOpts *O, bool live,
+                                           uint32_t &r0, uint32_t &r1, uint32_t &r2) {
   const __attribute__((address_space(4))) uint16_t *rank_t = (const __attribute__((address_space(4))) uint16_t *)O->rank;
   // (an LDS copy of this table is slower: 512 more bytes per wave cost a wave per CU, measured 1.50 -> 1.63 ms)
   // entry of (s, wl = 0) in the integer form: ((A s + C + off) << 21) | (s << 10) = (((A << 11) | 1) s + ((C + off) << 11)) << 10,
@@ -106,36 +130,74 @@ __device__ __forceinline__ void heap_phase(uint32_t *hp, int n, const uint32_t (
   const uint32_t mul0 = ((uint32_t)O->rank_a << 11) | 1u, add0 = (uint32_t)(O->rank_c + O->rank_off) << 11;
   const uint32_t step0 = O->rank_step0, step = O->rank_step;
   int remaining = 212 * 8 - 40 - 10 * n;                   // bitallocation.js:97-100
-  int hs = 0;
   // distributeBitsRDO (:203-281): initial heap = BFUs below n with a non-zero scale factor
   // branch-free: every BFU writes its entry at the cursor, only live ones advance it (the next one overwrites the
   // slot otherwise; what the last dead one leaves behind is cleared with the sentinels)
   // (in blocks of 13 BFUs that the scheduler cannot interleave: see totals_tabled)
+  // The cursor is lane-varying, so slots 0..2 cannot go to registers as they are written: while BFUs 0..49 are placed
+  // they borrow the last three rows (47..49), which slots 50, 51 and the sentinel need only afterwards.  `cur` is the
+  // heap size + 47; the row of the cursor is cur mod 50, one subtraction and one unsigned minimum.
+  uint32_t cur = 47;
 #pragma unroll
   for (int b0 = 0; b0 < 52; b0 += 13) if (own_block()) {
 #pragma unroll
-  for (int b = b0; b < b0 + 13; b++) {
+  for (int b = b0; b < b0 + 13 && b < 50; b++) {
     if (b < n) {
       const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
       const uint32_t fixed = ((uint32_t)kSpecsHost[b] << 16) | (uint32_t)b;
-      if constexpr (AFFINE) hp[hs * 64] = ((__umul24(mul0, (uint32_t)s) + add0) << 10) | fixed;
-      else hp[hs * 64] = ((uint32_t)rank_t[s * 16] << 21) | ((uint32_t)s << 10) | fixed;
-      hs += (s != 0 && live) ? 1 : 0;
+      uint32_t *at = hp + min(cur, cur - (uint32_t)kHeapRows) * 64;
+      if constexpr (AFFINE) *at = ((__umul24(mul0, (uint32_t)s) + add0) << 10) | fixed;
+      else *at = ((uint32_t)rank_t[s * 16] << 21) | ((uint32_t)s << 10) | fixed;
+      cur += (s != 0 && live) ? 1 : 0;
     }
   }
   }
-  for (int k = hs; k < kHeapSlotsPerLane; k++) hp[k * 64] = kSentinel;   // rank 0: below every live entry
-  for (int i = (hs >> 1) - 1; i >= 0; i--) {               // heapify (:238-241); per-lane trip counts
+  int hs = (int)cur - 47;
+  r0 = hp[47 * 64]; r1 = hp[48 * 64]; r2 = hp[49 * 64];
+  // BFUs 50 and 51: the cursor is at most 51, that is row 48
+#pragma unroll
+  for (int b = 50; b < 52; b++) {
+    if (b < n) {
+      const int s = (sf[b >> 2] >> ((b & 3) * 8)) & 63;
+      const uint32_t fixed = ((uint32_t)kSpecsHost[b] << 16) | (uint32_t)b;
+      uint32_t e;
+      if constexpr (AFFINE) e = ((__umul24(mul0, (uint32_t)s) + add0) << 10) | fixed;
+      else e = ((uint32_t)rank_t[s * 16] << 21) | ((uint32_t)s << 10) | fixed;
+      r0 = hs == 0 ? e : r0; r1 = hs == 1 ? e : r1; r2 = hs == 2 ? e : r2;
+      if (hs >= 3) hp[(hs - 3) * 64] = e;
+      hs += (s != 0 && live) ? 1 : 0;
+    }
+  }
+  // rank 0 behind the heap: below every live entry
+  r0 = hs > 0 ? r0 : kSentinel; r1 = hs > 1 ? r1 : kSentinel; r2 = hs > 2 ? r2 : kSentinel;
+  for (int k = max(hs, 3) - 3; k < kHeapRows; k++) hp[k * 64] = kSentinel;
+  // heapify (:238-241), per-lane trip counts: the slots that have a row, then slots 2, 1 and the root
+  const int half = hs >> 1;
+  for (int i = half - 1; i >= 3; i--) {
     const int l = 2 * i + 1;
-    heap_sift_down(hp, 52, i, hp[i * 64], hp[l * 64], hp[(l + 1) * 64], true);
+    heap_sift_down(hp, i, hp[(i - 3) * 64], hp[(l - 3) * 64], hp[(l - 2) * 64], true);
+  }
+  if (__builtin_amdgcn_ballot_w64(half >= 2) != 0) {
+    r2 = heap_sift_below_root(hp, 2, r2, half >= 3);
+    r1 = heap_sift_below_root(hp, 1, r1, half >= 2);
+  }
+  if (__builtin_amdgcn_ballot_w64(half >= 1) != 0) {
+    const uint32_t v = r0, vmax = v | kLow;
+    const bool take_r = r2 > max(r1 | kLow, vmax);
+    const bool take_l = !take_r && r1 > vmax;
+    const bool moved = half >= 1 && (take_r || take_l);
+    r0 = moved ? (take_r ? r2 : r1) : v;
+    const uint32_t below = heap_sift_below_root(hp, take_r ? 2 : 1, v, moved);
+    r1 = (moved && !take_r) ? below : r1; r2 = (moved && take_r) ? below : r2;
   }
   // greedy spending loop (:244-278): the root either takes its next priority or leaves the heap (does not
   // fit :251-258, or reached the last word length :271-277); then one sift.
-  uint32_t r0 = hp[0], r1 = hp[64], r2 = hp[128];
-  // the smallest BFU has 4 coefficients, so with fewer than 4 bits left no entry can take its next step: the
-  // remaining iterations of the reference only pop entries that do not fit and change nothing (:251-258)
-  bool run = remaining >= 4 && hs > 0;
-  while (__builtin_amdgcn_ballot_w64(run) != 0) {
+  // The smallest BFU has 4 coefficients, so with fewer than 4 bits left no entry can take its next step: the
+  // remaining iterations of the reference only pop entries that do not fit and change nothing (:251-258).
+  // A lane whose heap is empty gives its bits up, so "4 bits left" alone says whether a lane still runs.
+  remaining = hs > 0 ? remaining : 0;
+  while (__builtin_amdgcn_ballot_w64(remaining >= 4) != 0) {
+    const bool run = remaining >= 4;
     const uint32_t top = r0;
     const bool wl0 = (top & (15u << 6)) == 0;
     const int size = (top >> 16) & 31;
@@ -154,81 +216,84 @@ __device__ __forceinline__ void heap_phase(uint32_t *hp, int n, const uint32_t (
       v = upd | ((uint32_t)rank_t[s * 16 + (nxt & 15)] << 21);
       last_wl = nxt >= 15;
     }
+    remaining -= fits ? cost : 0;                          // (a lane that no longer runs has less than any cost left, or a sentinel of size 0 on top)
     const bool leaves = run && (!fits || last_wl);
-    if (__builtin_amdgcn_ballot_w64(leaves) != 0) {
-      // the last element replaces the root; the leaver is parked, rank 0, in the slot that frees
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(leaves) != 0, 0)) {
+      // Out of line, behind its vote: the last element replaces the root; the leaver is parked, rank 0, in the slot that
+      // frees.  A heap of one parks its root where it is (nothing below it has a rank, so the sift leaves it there) and
+      // the lane stops.
       const int li = hs - 1;
-      const uint32_t deep = hp[(li > 3 ? li : 3) * 64];
-      const uint32_t last = li == 0 ? r0 : (li == 1 ? r1 : (li == 2 ? r2 : deep));
+      const uint32_t deep = hp[(max(li, 3) - 3) * 64];
       if (leaves) {
-        v = last;
+        v = li == 0 ? upd : (li == 1 ? r1 : (li == 2 ? r2 : deep));
         hs = li;
-        if (li > 2) hp[li * 64] = upd;
-        r0 = li == 0 ? upd : r0; r1 = li == 1 ? upd : r1; r2 = li == 2 ? upd : r2;
+        if (li > 2) hp[(li - 3) * 64] = upd;
+        r1 = li == 1 ? upd : r1; r2 = li == 2 ? upd : r2;
+        remaining = li == 0 ? 0 : remaining;
       }
     }
-    if (run) remaining -= fits ? cost : 0;
-    const bool sift = run && hs > 0;
-    // level 0: root against r1, r2
+    // The sift moves a hole, not the entry: at every level the winning child (one compare, one select) moves up if it
+    // beats v (one compare) and the hole follows it; v itself is written once, where the descent stops.
     const uint32_t vmax = v | kLow;
-    const bool tr0 = r2 > max(r1 | kLow, vmax);
-    const bool tl0 = !tr0 && r1 > vmax;
-    const bool mv0 = sift && (tr0 || tl0);
-    if (sift) r0 = mv0 ? (tr0 ? r2 : r1) : v;
-    {
-      // level 1: the chosen child's children are slots 3,4 or 5,6.  (No "does any lane still move?" test in front of
-      // levels 1 and 2: among 64 heaps one nearly always does, and the test costs more than the level it would skip.)
-      const int i1 = tr0 ? 2 : 1;
-      const uint32_t *src = hp + (2 * i1 + 1) * 64;
-      const uint32_t el = src[0], er = src[64];
-      // both pairs of grandchildren (slots 4 i1 + 3 .. 4 i1 + 6 <= 14: always inside the lane's slots) are requested with the
-      // children: one LDS round trip decides two levels -- the loop is a chain of dependent round trips, not of instructions
-      const uint32_t g0 = src[(2 * i1 + 2) * 64], g1 = src[(2 * i1 + 3) * 64], g2 = src[(2 * i1 + 4) * 64], g3 = src[(2 * i1 + 5) * 64];
-      const bool tr1 = er > max(el | kLow, vmax);
-      const bool tl1 = !tr1 && el > vmax;
-      const bool mv1 = mv0 && (tr1 || tl1);
-      const uint32_t val = mv1 ? (tr1 ? er : el) : v;
-      if (mv0) { if (tr0) r2 = val; else r1 = val; }
-      // levels 2..5 unrolled (a heap of 52 has six): node i2 in slots 3..6 against its children (the grandchildren above),
-      // then ONE more round trip for the children (slots 15..30) and grandchildren (31..62) of the node in slots 7..14 it
-      // moves to.  Two round trips per step where the loop of heap_sift_down made up to five (one per level and one more
-      // to find that the last level has no children); a lane that stops early just stops writing.
-      {
-        const int i2 = 2 * i1 + 1 + (tr1 ? 1 : 0);
-        const uint32_t c0 = tr1 ? g2 : g0, c1 = tr1 ? g3 : g1;
-        const bool tr2 = c1 > max(c0 | kLow, vmax);
-        const bool tl2 = !tr2 && c0 > vmax;
-        const bool mv2 = mv1 && (tr2 || tl2);
-        if (mv1) hp[i2 * 64] = mv2 ? (tr2 ? c1 : c0) : v;
-        if (__builtin_amdgcn_ballot_w64(mv2) != 0) {
-          const int i3 = 2 * i2 + 1 + (tr2 ? 1 : 0);                  // 7..14
-          const uint32_t *s3 = hp + (2 * i3 + 1) * 64;                // children: slots 15..30
-          const uint32_t d0 = s3[0], d1 = s3[64];
-          // grandchildren: the four slots from 4 i3 + 3, one base and immediate offsets.  Only nodes 12..14 have grandchildren
-          // past slot 51; of those only slots 51 (a real one) and 52 (the sentinel row, whose rank 0 never wins) matter, as the
-          // children of slot 25.  Such a lane reads slots 49..52 and takes the upper pair; a node from 26 on has no
-          // children, which its number says.
-          const bool far = i3 >= 12;
-          const uint32_t *s4 = hp + min(4 * i3 + 3, 49) * 64;
-          const uint32_t h0 = s4[0], h1 = s4[64], h2 = s4[128], h3 = s4[192];
-          const bool tr3 = d1 > max(d0 | kLow, vmax);
-          const bool tl3 = !tr3 && d0 > vmax;
-          const bool mv3 = mv2 && (tr3 || tl3);
-          if (mv2) hp[i3 * 64] = mv3 ? (tr3 ? d1 : d0) : v;
-          const int i4 = 2 * i3 + 1 + (tr3 ? 1 : 0);                  // 15..30
-          const bool upper = tr3 || far;
-          const uint32_t e0 = upper ? h2 : h0, e1 = upper ? h3 : h1;
-          const bool tr4 = e1 > max(e0 | kLow, vmax);
-          const bool tl4 = !tr4 && e0 > vmax;
-          const bool mv4 = mv3 && i4 < 26 && (tr4 || tl4);
-          if (mv3) hp[i4 * 64] = mv4 ? (tr4 ? e1 : e0) : v;
-          if (mv4) hp[(2 * i4 + 1 + (tr4 ? 1 : 0)) * 64] = v;          // slots 31..51: no children
-        }
-      }
+    // level 0: root against r1, r2
+    const bool t0 = r2 > (r1 | kLow);                      // pr > pl
+    const uint32_t w0 = t0 ? r2 : r1;
+    const bool mv0 = run && w0 > vmax;                     // max(pl, pr) > pv
+    if (run) r0 = mv0 ? w0 : v;
+    // level 1: the chosen child's children are slots 3,4 or 5,6 = rows 0,1 or 2,3.  (No "does any lane still move?" test
+    // in front of levels 1 and 2: among 64 heaps one nearly always does, and the test costs more than the level it would skip.)
+    const uint32_t *s1 = hp + (t0 ? 2 : 0) * 64;
+    const uint32_t el = s1[0], er = s1[64];
+    // both pairs of grandchildren (slots 7..10 or 11..14 = rows 4..7 or 8..11) are requested with the children: one LDS
+    // round trip decides two levels -- the loop is a chain of dependent round trips, not of instructions
+    const uint32_t *s2 = hp + (t0 ? 8 : 4) * 64;
+    const uint32_t g0 = s2[0], g1 = s2[64], g2 = s2[128], g3 = s2[192];
+    const bool t1 = er > (el | kLow);
+    const uint32_t w1 = t1 ? er : el;
+    const bool mv1 = mv0 && w1 > vmax;
+    const uint32_t val = mv1 ? w1 : v;
+    r1 = (mv0 && !t0) ? val : r1; r2 = (mv0 && t0) ? val : r2;
+    // levels 2..5 unrolled (a heap of 52 has six): the hole in rows 0..3 against its children (the grandchildren above),
+    // then ONE more round trip for the children (rows 12..27) and grandchildren (rows 28..) of the row in 4..11 it moves
+    // to.  Two round trips per step where the loop of heap_sift_down made up to five (one per level and one more to find
+    // that the last level has no children); a lane that stops early just stops writing.
+    const uint32_t cl = t1 ? g2 : g0, cr = t1 ? g3 : g1;
+    const bool t2 = cr > (cl | kLow);
+    const uint32_t w2 = t2 ? cr : cl;
+    const bool mv2 = mv1 && w2 > vmax;
+    const int q2 = (t0 ? 2 : 0) + (t1 ? 1 : 0);
+    uint32_t *hole = hp + q2 * 64;
+    if (mv2) *hole = w2;
+    if (__builtin_amdgcn_ballot_w64(mv2) != 0) {
+      const int q3 = 2 * q2 + 4 + (t2 ? 1 : 0);                   // rows 4..11 (slots 7..14)
+      const uint32_t *s3 = hp + (2 * q3 + 4) * 64;                // children: rows 12..27 (slots 15..30)
+      const uint32_t d0 = s3[0], d1 = s3[64];
+      // grandchildren: the four rows from 4 q3 + 12, one base and immediate offsets.  Only rows 9..11 have grandchildren
+      // past slot 51; of those only slot 51 (a real one) and the sentinel row behind it (whose rank 0 never wins) matter, as
+      // the children of slot 25 (row 22).  Such a lane reads rows 46..49 and takes the upper pair; a slot from 26 on (row 23)
+      // has no children, which its number says.
+      const bool far = q3 >= 9;
+      const uint32_t *s4 = hp + min(4 * q3 + 12, kHeapRows - 4) * 64;
+      const uint32_t h0 = s4[0], h1 = s4[64], h2 = s4[128], h3 = s4[192];
+      const bool t3 = d1 > (d0 | kLow);
+      const uint32_t w3 = t3 ? d1 : d0;
+      const bool mv3 = mv2 && w3 > vmax;
+      uint32_t *p3 = hp + q3 * 64;
+      hole = mv2 ? p3 : hole;
+      if (mv3) *p3 = w3;
+      const int q4 = 2 * q3 + 4 + (t3 ? 1 : 0);                   // rows 12..27
+      const bool upper = t3 || far;
+      const uint32_t e0 = upper ? h2 : h0, e1 = upper ? h3 : h1;
+      const bool t4 = e1 > (e0 | kLow);
+      const uint32_t w4 = t4 ? e1 : e0;
+      const bool mv4 = mv3 && q4 < 23 && w4 > vmax;
+      uint32_t *p4 = hp + q4 * 64;
+      hole = mv3 ? p4 : hole;
+      if (mv4) *p4 = w4;
+      hole = mv4 ? hp + (2 * q4 + 4 + (t4 ? 1 : 0)) * 64 : hole;   // rows 28..48 (slots 31..51): no children
     }
-    run = run && remaining >= 4 && hs > 0;
+    if (mv1) *hole = v;                                    // (a hole in slots 0..2 took v as it was decided, above)
   }
-  hp[0] = r0; hp[64] = r1; hp[128] = r2;
 }
 
 // calculateTotalDistortion (:157-190), sequential double sum, index ascending, from the host's tables of its terms
@@ -315,32 +380,37 @@ template <bool BOUND>
 __device__ __forceinline__ void run_candidate(uint32_t *hp, int n, uint32_t (&sf)[13], const C1DevEncOpts *O,
                                               bool live, uint64_t &res0, uint64_t &res1, uint64_t &res2,
                                               uint64_t &res3, double &total, double (&lbs)[7]) {
-  if (O->rank_affine != 0) heap_phase<true>(hp, n, sf, O, live);
-  else heap_phase<false>(hp, n, sf, O, live);
-  // Every BFU that ever entered the heap now sits in one of the first slots (as many as the heap started with) with its final
-  // word length; the slots behind hold the sentinel, which names slot 52.  The word lengths are put in BFU order through the lane's own column of the heap: the
-  // top byte of slot b takes BFU b's word length (a byte store: the rank bits up there are done with, and the low bits
-  // that name an unread entry's BFU and word length stay as they are), then the 52 top bytes are read back in order and
-  // packed with constant shifts.  6 vector instructions per BFU; selecting one of four 64-bit words by a lane-varying
-  // index cost 25 (1 300 of the 8 300 a wave of k_alloc_first issued).
+  uint32_t top[3];
+  if (O->rank_affine != 0) heap_phase<true>(hp, n, sf, O, live, top[0], top[1], top[2]);
+  else heap_phase<false>(hp, n, sf, O, live, top[0], top[1], top[2]);
+  // Every BFU that ever entered the heap now sits in one of the first slots (as many as the heap started with: three registers,
+  // then the rows) with its final word length; the slots behind hold the sentinel, which names BFU 52.  The word lengths are put
+  // in BFU order through the lane's own column of the heap: the upper half of every entry is done with (rank, size), so
+  // BFU b's word length goes to byte 2 + (b & 1) of row b >> 1 (a byte store: the low half, which names an unread
+  // entry's BFU and word length, stays as it is; the sentinel's byte is in row 26 and is never read), then the 52 bytes are
+  // read back in order and packed with constant shifts.  6 vector instructions per BFU; selecting one of four 64-bit
+  // words by a lane-varying index cost 25 (1 300 of the 8 300 a wave of k_alloc_first issued).
   {
     uint8_t *hb = reinterpret_cast<uint8_t *>(hp);
+    auto put = [hb](uint32_t e) { hb[((e & 62u) << 7) + (e & 1u) + 2] = (uint8_t)((e >> 6) & 15u); };
 #pragma unroll
-    for (int k = 0; k < 52; k++) hb[k * 256 + 3] = 0;
+    for (int k = 0; k < 26; k++) *reinterpret_cast<uint16_t *>(hb + k * 256 + 2) = 0;
 #pragma unroll
-    for (int k0 = 0; k0 < 52; k0 += 8) {
+    for (int j = 0; j < 3; j++) put(top[j]);
+#pragma unroll
+    for (int k0 = 0; k0 < kHeapRows - 1; k0 += 8) {
       uint32_t e[8];
 #pragma unroll
-      for (int j = 0; j < 8; j++) if (k0 + j < 52) e[j] = hp[(k0 + j) * 64];
+      for (int j = 0; j < 8; j++) if (k0 + j < kHeapRows - 1) e[j] = hp[(k0 + j) * 64];
 #pragma unroll
-      for (int j = 0; j < 8; j++) if (k0 + j < 52) hb[(e[j] & 63u) * 256 + 3] = (uint8_t)((e[j] >> 6) & 15u);
+      for (int j = 0; j < 8; j++) if (k0 + j < kHeapRows - 1) put(e[j]);
     }
     uint32_t d[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       d[i] = 0;
 #pragma unroll
-      for (int j = 0; j < 8; j++) if (8 * i + j < 52) d[i] |= (hp[(8 * i + j) * 64] >> 24) << (4 * j);
+      for (int j = 0; j < 8; j++) if (8 * i + j < 52) d[i] |= (uint32_t)hb[((8 * i + j) >> 1) * 256 + 2 + (j & 1)] << (4 * j);
     }
     res0 = (uint64_t)d[0] | ((uint64_t)d[1] << 32); res1 = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
     res2 = (uint64_t)d[4] | ((uint64_t)d[5] << 32); res3 = (uint64_t)d[6] | ((uint64_t)d[7] << 32);
@@ -369,7 +439,7 @@ __device__ __forceinline__ void store_candidate(uint8_t *cand, int64_t unit, int
 __device__ __forceinline__ bool getenv_no_tonal(const C1DevEncOpts *O) { return O->alloc_no_tonal != 0; }   // C1_ALLOC_NO_TONAL=1 (experiments)
 
 __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_first(C1EncodeLaunch L) {
-  __shared__ uint32_t heap[kHeapSlotsPerLane * 64];
+  __shared__ uint32_t heap[kHeapRows * 64];
   const C1DevEncOpts *O = L.opts;
   const __attribute__((address_space(4))) double *biased = (const __attribute__((address_space(4))) double *)O->biased;
   const int lane = threadIdx.x;
@@ -596,7 +666,7 @@ __global__ __launch_bounds__(256) void k_alloc_bound(C1EncodeLaunch L) {
 template <bool FIRST_ROUND>
 __global__ __launch_bounds__(C1_WAVE, 3) void k_alloc_rest(C1EncodeLaunch L, const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_count,
                                                            uint32_t *__restrict__ list2) {
-  __shared__ uint32_t heap[kHeapSlotsPerLane * 64];
+  __shared__ uint32_t heap[kHeapRows * 64];
   const C1DevEncOpts *O = L.opts;
   const int lane = threadIdx.x;
   const uint32_t count = *list_count;
