@@ -384,7 +384,7 @@ class Context:
         return (units, taken, dist, energy) if return_distortion else (units, taken)
 
     def encode_measured_modes(self, channels, candidates, options=None, halo_frames=0, scale_factor_offsets=None,
-                              return_distortion=False, return_shifts=False):
+                              return_distortion=False, return_shifts=False, masking=None, return_weights=False):
         """encode_measured() with the block modes of every sound unit chosen among `candidates` by the final error of the measured
         allocation under each (c1_encode_measured_modes_batch; opt-in like encode_measured()).  candidates: as for
         encode_best_modes(); scale_factor_offsets: as for encode_measured(), None for the plain measured allocation (offsets
@@ -393,7 +393,12 @@ class Context:
         Returns (units, choice uint8 [units], modes uint8 [units], taken uint8 [units]), then with return_shifts shifts int8
         [units, 52] (the winner's), then with return_distortion distortion float64 [units, n, 2] (T_ref, T(n*)) and energy
         float64 [units, n]; units are what encode_measured(modes=modes, ...) gives.  The dearest encode of the library: one
-        greedy allocation per unit and candidate."""
+        greedy allocation per unit and candidate.
+        masking (c1_encode_measured_modes_masked_batch): True for the packaged tables or a (floor, spread or None) pair, as for
+        encode_measured().  Every candidate's errors are then divided by ONE masking threshold per unit and BFU, computed from the
+        unit's all-long spectrum whatever the candidates (the weights encode_measured(modes=zeros, masking=...) reports), so the
+        weighted T_final of the candidates are comparable; distortion and energy are the weighted ones.  None: the call above,
+        untouched.  return_weights (needs masking): weights float64 [units, 52] ends the result."""
         opts = (options or EncoderOptions()).to_c()
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         n = len(chans[0])
@@ -402,6 +407,9 @@ class Context:
         frames = max(n // 512 - halo_frames, 0)
         cand = mode_candidates(candidates)
         count = len(cand)
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
         offs = check_scale_factor_offsets((0,) if scale_factor_offsets is None else scale_factor_offsets)
         total = frames * len(chans)
         units = np.zeros((total, 212), dtype=np.uint8)
@@ -412,6 +420,17 @@ class Context:
         dist = np.zeros((total, count, 2), dtype=np.float64) if return_distortion else None
         energy = np.zeros((total, count), dtype=np.float64) if return_distortion else None
         ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
+        if mask is not None:
+            weights = np.zeros((total, 52), dtype=np.float64) if return_weights else None
+            capi.check(capi.load().c1_encode_measured_modes_masked_batch(
+                self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts), cand.ctypes.data, count, offs.ctypes.data,
+                len(offs), mask[0].ctypes.data, None if mask[1] is None else mask[1].ctypes.data, units.ctypes.data, choice.ctypes.data,
+                modes.ctypes.data, taken.ctypes.data, None if shifts is None else shifts.ctypes.data,
+                None if dist is None else dist.ctypes.data, None if energy is None else energy.ctypes.data,
+                None if weights is None else weights.ctypes.data))
+            out = (units, choice, modes, taken) + ((shifts,) if return_shifts else ())
+            out = out + (dist, energy) if return_distortion else out
+            return out + (weights,) if return_weights else out
         capi.check(capi.load().c1_encode_measured_modes_batch(
             self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, C.byref(opts), cand.ctypes.data, count, offs.ctypes.data,
             len(offs), units.ctypes.data, choice.ctypes.data, modes.ctypes.data, taken.ctypes.data,
@@ -543,15 +562,26 @@ class Context:
 
     def encode_measured_modes_device(self, pcm_ptrs, frames, candidates, units_ptr=None, choice_ptr=None, modes_ptr=None, taken_ptr=None,
                                      shifts_ptr=None, distortion_ptr=None, energy_ptr=None, options=None, halo_frames=0,
-                                     scale_factor_offsets=None):
+                                     scale_factor_offsets=None, masking=None, weights_ptr=None):
         """c1_encode_measured_modes_device: candidates as for encode_best_modes_device and scale_factor_offsets as for
         encode_measured_device (host values; checked by the library: C1_ERR_ARG), None for offsets (0,); outputs on the device,
         each may be None (units_ptr None: measure only), not all; choice, modes and taken are uint8 [units], shifts int8 [units,
-        52], distortion float64 [units, n, 2] and energy float64 [units, n]."""
+        52], distortion float64 [units, n, 2] and energy float64 [units, n].  masking (host values, as for encode_measured_modes):
+        c1_encode_measured_modes_masked_device, and weights_ptr = float64 [units, 52] on the device, or None."""
         opts = (options or EncoderOptions()).to_c()
         cand = mode_candidates(candidates, check=False)
         offs = check_scale_factor_offsets((0,) if scale_factor_offsets is None else scale_factor_offsets, check=False)
         vp = lambda p: C.c_void_p(p) if p else None
+        if masking is not None:
+            mask = check_masking(masking, check=False)                             # the library's own check decides
+            capi.check(capi.load().c1_encode_measured_modes_masked_device(
+                self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, C.byref(opts), cand.ctypes.data if len(cand) else None,
+                len(cand), offs.ctypes.data if len(offs) else None, len(offs), mask[0].ctypes.data,
+                None if mask[1] is None else mask[1].ctypes.data, vp(units_ptr), vp(choice_ptr), vp(modes_ptr), vp(taken_ptr), vp(shifts_ptr),
+                vp(distortion_ptr), vp(energy_ptr), vp(weights_ptr)))
+            return
+        if weights_ptr:
+            raise ValueError('weights_ptr needs masking')
         capi.check(capi.load().c1_encode_measured_modes_device(
             self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, C.byref(opts), cand.ctypes.data if len(cand) else None,
             len(cand), offs.ctypes.data if len(offs) else None, len(offs), vp(units_ptr), vp(choice_ptr), vp(modes_ptr), vp(taken_ptr),
@@ -1284,14 +1314,17 @@ class EncoderStream:
         out = out + (dist, energy) if return_distortion else out
         return out + (weights,) if return_weights else out
 
-    def push_measured_modes(self, channels, candidates, scale_factor_offsets=None, return_distortion=False, return_shifts=False):
+    def push_measured_modes(self, channels, candidates, scale_factor_offsets=None, return_distortion=False, return_shifts=False,
+                            masking=None, return_weights=False):
         """push_measured() with the block modes of every pushed unit chosen among `candidates` by the final error of the measured
         allocation under each: Context.encode_measured_modes on a live stream (c1_enc_stream_push_measured_modes).  Per (unit,
         candidate) the figures are push_measured(modes=constant byte, ...)'s on a twin stream; the units are
         push_measured(modes=modes, ...)'s, and the stream afterwards is what it is after push(modes=modes), so the kinds of push
         may be mixed.  For a stream pushed from its start the rows are Context.encode_measured_modes' over the whole signal.
         candidates, scale_factor_offsets, the return_* flags, their ValueErrors and the result -- (units, choice, modes,
-        taken[, shifts][, distortion, energy]) -- are Context.encode_measured_modes'."""
+        taken[, shifts][, distortion, energy]) -- are Context.encode_measured_modes'.  masking and return_weights are that call's
+        too (c1_enc_stream_push_measured_modes_masked): one masking threshold per unit weighs every candidate, and weights ends
+        the result; None takes the call above, untouched."""
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         if len(chans) != self.channels:
             raise ValueError('expected %d channels' % self.channels)
@@ -1301,6 +1334,9 @@ class EncoderStream:
         frames = n // 512
         cand = mode_candidates(candidates)
         count = len(cand)
+        if return_weights and masking is None:
+            raise ValueError('return_weights needs masking')
+        mask = None if masking is None else check_masking(masking)
         offs = None if scale_factor_offsets is None else check_scale_factor_offsets(scale_factor_offsets)
         total = frames * self.channels
         units = np.zeros((total, 212), dtype=np.uint8)
@@ -1311,6 +1347,15 @@ class EncoderStream:
         dist = np.zeros((total, count, 2), dtype=np.float64) if return_distortion else None
         energy = np.zeros((total, count), dtype=np.float64) if return_distortion else None
         data = lambda a: None if a is None else a.ctypes.data
+        if mask is not None:
+            weights = np.zeros((total, 52), dtype=np.float64) if return_weights else None
+            capi.check(capi.load().c1_enc_stream_push_measured_modes_masked(
+                self._h, capi.ptr_array([c.ctypes.data for c in chans]), frames, cand.ctypes.data, count, data(offs),
+                0 if offs is None else len(offs), mask[0].ctypes.data, data(mask[1]), units.ctypes.data, choice.ctypes.data,
+                modes.ctypes.data, taken.ctypes.data, data(shifts), data(dist), data(energy), data(weights)))
+            out = (units, choice, modes, taken) + ((shifts,) if return_shifts else ())
+            out = out + (dist, energy) if return_distortion else out
+            return out + (weights,) if return_weights else out
         capi.check(capi.load().c1_enc_stream_push_measured_modes(
             self._h, capi.ptr_array([c.ctypes.data for c in chans]), frames, cand.ctypes.data, count, data(offs),
             0 if offs is None else len(offs), units.ctypes.data, choice.ctypes.data, modes.ctypes.data, taken.ctypes.data, data(shifts),

@@ -806,6 +806,11 @@ struct BestModesCall {
   int n_offsets = 0;
   uint8_t *taken = nullptr;
   int8_t *shifts = nullptr;
+  // c1_encode_measured_modes_masked_device: the uploaded tables (c1_ctx::d_mask; null for the calls above) and its output.  The
+  // front end then always makes the all-long analysis: the weights come from it
+  const double *mask = nullptr;
+  bool has_spread = false;
+  double *weights = nullptr;
 };
 
 // One call of c1_encode_best_bias_device: the palette's size and the call's outputs (device memory, each may be null)
@@ -930,6 +935,16 @@ void launch_measured_modes(c1_ctx *ctx, const C1EncodeLaunch &L, const uint8_t *
   ScopedTiming t(ctx, K_MEASURE, stream);
   const int64_t units = L.frames * L.channels;
   const bool wide = ctx->measured_wide < 0 ? units <= kMeasuredModesWideUnits : ctx->measured_wide != 0;
+  if (bm->mask) {
+    // the same over e' = P_b * e, P_b from the unit's all-long plane and the tables (c1_encode_measured_modes_masked_device)
+    (wide ? c1k_launch_measured_modes_masked_wide : c1k_launch_measured_modes_masked)(
+        L, ctx->d_bm_coefs, ctx->d_bm_side, trial, trial_stride, bm->cand, bm->n, bm->sf_offsets, bm->n_offsets, bm->mask, bm->has_spread,
+        L.units != nullptr, bm->choice ? bm->choice + at : nullptr, bm->modes_out ? bm->modes_out + at : nullptr,
+        bm->taken ? bm->taken + at : nullptr, bm->shifts ? bm->shifts + at * 52 : nullptr,
+        bm->distortion ? bm->distortion + at * bm->n * 2 : nullptr, bm->energy ? bm->energy + at * bm->n : nullptr,
+        bm->weights ? bm->weights + at * 52 : nullptr, stream);
+    return;
+  }
   (wide ? c1k_launch_measured_modes_wide : c1k_launch_measured_modes)(
       L, ctx->d_bm_coefs, ctx->d_bm_side, trial, trial_stride, bm->cand, bm->n, bm->sf_offsets, bm->n_offsets, L.units != nullptr,
       bm->choice ? bm->choice + at : nullptr, bm->modes_out ? bm->modes_out + at : nullptr, bm->taken ? bm->taken + at : nullptr,
@@ -1009,6 +1024,7 @@ int encode_device_impl(c1_ctx *ctx, const float *const *pcm, int channels, int64
     if ((bm->cand[k] & 0x3f) != 0x3a) bm_long = true;
     if ((bm->cand[k] & 0x3f) != 0) bm_short = true;
   }
+  if (bm && bm->mask) bm_long = true;                          // the weights come from the all-long analysis, whatever the candidates
   if (taps && (!coefs_tap || !side_tap || !alloc_tap)) return fail(C1_ERR_ARG, "coefs, side and alloc taps must be given together");
   if (taps && frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "stage taps are not chunked: at most %lld frames per call", (long long)kMaxChunkFrames);
   // Two-stage software pipeline over chunks: the analysis of chunk i+1 (fp64-VALU bound) runs on one
@@ -3423,6 +3439,117 @@ int c1_encode_measured_modes_batch(c1_ctx *ctx, const float *const *pcm, int cha
   return C1_OK;
 }
 
+// ---- the mode search under one masking threshold per unit (c1_encode_measured_modes_masked_*) ---------------------------------
+// c1_encode_measured_modes_device's chain with the tables of c1_encode_measured_masked_device: validated and uploaded as there, and
+// the search's kernel weighs every candidate's errors with P_b from the unit's all-long spectrum
+int c1_encode_measured_modes_masked_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                           const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                           int n_offsets, const double *mask_floor, const double *mask_spread, uint8_t *units,
+                                           uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion,
+                                           double *energy, double *weights) {
+  const char *const what = "c1_encode_measured_modes_masked_device";
+  CTX_GUARD(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  if ((rc = check_channels(channels))) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measured_opts(what, opts, false))) return rc;
+  if ((rc = check_mode_candidates(what, cand_modes, n_cand))) return rc;
+  if ((rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if ((rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy && !weights)
+    return fail(C1_ERR_ARG, "%s: units, choice, modes_out, taken, shifts, distortion, energy and weights are all NULL", what);
+  c1_encode_options base = *opts;                              // the modes are the candidates': neither threshold nor fixed modes are read
+  base.transient_threshold = 1.0;
+  base.fixed_block_modes[0] = base.fixed_block_modes[1] = base.fixed_block_modes[2] = -1;
+  if (frames > 0) {
+    // the tail of an earlier speculative encode may still run beside the context's stream: it reads none of this
+    if ((rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+  }
+  BestModesCall mc = {n_cand, nullptr, choice, modes_out, distortion, energy};
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's arrays may change once the call has returned
+  int8_t offs[C1_MAX_SF_OFFSETS];
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  memcpy(offs, sf_offsets, (size_t)n_offsets);
+  mc.cand = cand;
+  mc.sf_offsets = offs;
+  mc.n_offsets = n_offsets;
+  mc.taken = taken;
+  mc.shifts = shifts;
+  mc.mask = ctx->d_mask;
+  mc.has_spread = mask_spread != nullptr;
+  mc.weights = weights;
+  return encode_device_impl(ctx, pcm, channels, frames, halo_frames, &base, units, nullptr, nullptr, nullptr, nullptr, false,
+                            nullptr, nullptr, nullptr, &mc);
+}
+
+int c1_encode_measured_modes_masked_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                          const c1_encode_options *opts, const uint8_t *cand_modes, int n_cand, const int8_t *sf_offsets,
+                                          int n_offsets, const double *mask_floor, const double *mask_spread, uint8_t *units,
+                                          uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion,
+                                          double *energy, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_encode_measured_modes_masked_batch";
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measured_opts(what, opts, false))) return rc;
+  if ((rc = check_mode_candidates(what, cand_modes, n_cand))) return rc;
+  if ((rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if ((rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  if (!units && !choice && !modes_out && !taken && !shifts && !distortion && !energy && !weights)
+    return fail(C1_ERR_ARG, "%s: units, choice, modes_out, taken, shifts, distortion, energy and weights are all NULL", what);
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), choice_off = up256(unit_off + n_units * C1_UNIT_BYTES), modes_off = up256(choice_off + n_units),
+               taken_off = up256(modes_off + n_units), shift_off = up256(taken_off + n_units), dist_off = up256(shift_off + n_units * 52),
+               energy_off = up256(dist_off + n_units * n_cand * 2 * sizeof(double)),
+               weight_off = up256(energy_off + n_units * n_cand * sizeof(double));
+  if ((rc = ensure_io(ctx, weight_off + n_units * 52 * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off, *d_choice = (uint8_t *)ctx->d_io + choice_off, *d_modes = (uint8_t *)ctx->d_io + modes_off,
+          *d_taken = (uint8_t *)ctx->d_io + taken_off;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>((char *)ctx->d_io + shift_off);
+  double *d_dist = reinterpret_cast<double *>((char *)ctx->d_io + dist_off), *d_energy = reinterpret_cast<double *>((char *)ctx->d_io + energy_off),
+         *d_weights = reinterpret_cast<double *>((char *)ctx->d_io + weight_off);
+  if ((rc = c1_encode_measured_modes_masked_device(ctx, dptr, channels, frames, halo_frames, opts, cand_modes, n_cand, sf_offsets, n_offsets,
+                                                   mask_floor, mask_spread, units ? d_units : nullptr, choice ? d_choice : nullptr,
+                                                   modes_out ? d_modes : nullptr, taken ? d_taken : nullptr, shifts ? d_shifts : nullptr,
+                                                   distortion ? d_dist : nullptr, energy ? d_energy : nullptr,
+                                                   weights ? d_weights : nullptr))) return rc;
+  if (units) HIP_TRY(hipMemcpyAsync(units, d_units, n_units * C1_UNIT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (choice) HIP_TRY(hipMemcpyAsync(choice, d_choice, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (modes_out) HIP_TRY(hipMemcpyAsync(modes_out, d_modes, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (taken) HIP_TRY(hipMemcpyAsync(taken, d_taken, n_units, hipMemcpyDeviceToHost, ctx->stream));
+  if (shifts) HIP_TRY(hipMemcpyAsync(shifts, d_shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
+  if (distortion) HIP_TRY(hipMemcpyAsync(distortion, d_dist, n_units * n_cand * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (energy) HIP_TRY(hipMemcpyAsync(energy, d_energy, n_units * n_cand * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, d_weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 int c1_decode_device(c1_ctx *ctx, const uint8_t *units, int channels, int64_t frames, int halo_units,
                      float *const *pcm) {
   CTX_GUARD(ctx);
@@ -4032,6 +4159,7 @@ void bm_outputs_at(const BestModesCall &bm, int64_t at, BestModesCall *part) {
   if (part->shifts) part->shifts += at * 52;
   if (part->distortion) part->distortion += at * bm.n * 2;
   if (part->energy) part->energy += at * bm.n;
+  if (part->weights) part->weights += at * 52;
 }
 
 // the options of a call whose modes are the candidates': neither threshold nor fixed modes are read
@@ -4055,6 +4183,7 @@ int encode_from_states_modes(c1_ctx *ctx, int64_t n, const float *pcm, int64_t p
     if ((bm->cand[k] & 0x3f) != 0x3a) bm_long = true;
     if ((bm->cand[k] & 0x3f) != 0) bm_short = true;
   }
+  if (bm->mask) bm_long = true;                                // the weights come from the all-long analysis, whatever the candidates
   if ((rc = join_tail(ctx))) return rc;
   if ((rc = ensure_workspace(ctx, n))) return rc;
   if ((rc = ensure_trial_allocs(ctx, n, bm->n))) return rc;
@@ -4358,6 +4487,60 @@ int c1_enc_stream_push_measured_modes(c1_enc_stream *s, const float *const *pcm,
   return enc_stream_push_impl(s, pcm, frames, nullptr, units, nullptr, 0, nullptr, nullptr, nullptr, &bm, &host);
 }
 
+int c1_enc_stream_push_measured_modes_masked(c1_enc_stream *s, const float *const *pcm, int64_t frames, const uint8_t *cand_modes, int n_cand,
+                                             const int8_t *sf_offsets, int n_offsets, const double *mask_floor, const double *mask_spread,
+                                             uint8_t *units, uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts,
+                                             double *distortion, double *energy, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a stream nor a device
+  const char *const what = "c1_enc_stream_push_measured_modes_masked";
+  int rc;
+  if (frames < 0) return fail(C1_ERR_ARG, "%s: frames must be >= 0", what);
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "%s: at most %lld frames per call", what, (long long)kMaxModesBatchFrames);
+  if ((rc = check_mode_candidates(what, cand_modes, n_cand))) return rc;
+  if (!sf_offsets && n_offsets != 0) return fail(C1_ERR_ARG, "%s: n_offsets = %d, but sf_offsets is NULL", what, n_offsets);
+  if (sf_offsets && (rc = check_sf_offsets(what, sf_offsets, n_offsets))) return rc;
+  if ((rc = check_masking(what, mask_floor, mask_spread))) return rc;
+  if (frames > 0 && (!pcm || !units)) return fail(C1_ERR_ARG, "%s: pcm or units is NULL", what);
+  if (!s) return fail(C1_ERR_ARG, "%s: stream is NULL", what);
+  c1_ctx *ctx = s->ctx;
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if ((rc = check_measured_opts(what, &s->opts, false))) return rc;
+  if (frames == 0) return C1_OK;
+  for (int c = 0; c < s->channels; c++)
+    if (!pcm[c]) return fail(C1_ERR_ARG, "%s: pcm[%d] is NULL", what, c);
+  // from here on only the device can fail.  The outputs' staging: c1_enc_stream_push_measured's block, asked for twice the units:
+  // that holds a search's outputs and the weights, laid out over this push's units
+  constexpr size_t kBytes = 52 * sizeof(double) + C1_MAX_MODE_CANDIDATES * 3 * sizeof(double) + 52 + 3;
+  static_assert(2 * kMeasBlockBytes >= kBytes, "two staging blocks hold a weighted mode search's outputs");
+  const int64_t n_units = frames * s->channels;
+  if ((rc = enc_stream_meas_block(s, 2 * n_units))) return rc;
+  const size_t cap = (size_t)n_units;
+  double *d_weights = static_cast<double *>(s->d_meas), *d_dist = d_weights + cap * 52, *d_energy = d_dist + cap * C1_MAX_MODE_CANDIDATES * 2;
+  int8_t *d_shifts = reinterpret_cast<int8_t *>(d_energy + cap * C1_MAX_MODE_CANDIDATES);
+  uint8_t *d_choice = reinterpret_cast<uint8_t *>(d_shifts + cap * 52), *d_modes = d_choice + cap, *d_taken = d_modes + cap;
+  static const int8_t kOwnIndex[1] = {0};                      // no offsets: the search over the plain measured allocation
+  uint8_t cand[C1_MAX_MODE_CANDIDATES];                        // the caller's arrays may change while the call runs
+  int8_t offs[C1_MAX_SF_OFFSETS];
+  memcpy(cand, cand_modes, (size_t)n_cand);
+  if (sf_offsets) memcpy(offs, sf_offsets, (size_t)n_offsets);
+  if ((rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+  BestModesCall bm = {n_cand, cand, choice ? d_choice : nullptr, modes_out ? d_modes : nullptr, distortion ? d_dist : nullptr,
+                      energy ? d_energy : nullptr};
+  bm.sf_offsets = sf_offsets ? offs : kOwnIndex;
+  bm.n_offsets = sf_offsets ? n_offsets : 1;
+  bm.taken = taken ? d_taken : nullptr;
+  bm.shifts = shifts ? d_shifts : nullptr;                     // a single offset 0 moves no index: zeros
+  bm.mask = ctx->d_mask;
+  bm.has_spread = mask_spread != nullptr;
+  bm.weights = weights ? d_weights : nullptr;
+  BestModesCall host = {n_cand, cand, choice, modes_out, distortion, energy};
+  host.taken = taken;
+  host.shifts = shifts;
+  host.weights = weights;
+  return enc_stream_push_impl(s, pcm, frames, nullptr, units, nullptr, 0, nullptr, nullptr, nullptr, &bm, &host);
+}
+
 namespace {
 // modes null: the stream's options decide.  Else the frames behave as if the options had been switched to fixed block modes
 // for them, frame by frame and channel by channel, and back afterwards: the detector does not run, and on a stream under
@@ -4514,6 +4697,7 @@ int enc_stream_push_impl(c1_enc_stream *s, const float *const *pcm, int64_t fram
     if (bm_host->shifts) HIP_TRY(hipMemcpyAsync(bm_host->shifts, bm->shifts, n_units * 52, hipMemcpyDeviceToHost, ctx->stream));
     if (bm_host->distortion) HIP_TRY(hipMemcpyAsync(bm_host->distortion, bm->distortion, n_units * bm->n * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (bm_host->energy) HIP_TRY(hipMemcpyAsync(bm_host->energy, bm->energy, n_units * bm->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (bm_host->weights) HIP_TRY(hipMemcpyAsync(bm_host->weights, bm->weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   s->pushed += frames;

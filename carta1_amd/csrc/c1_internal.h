@@ -425,6 +425,20 @@ void c1k_launch_measured_modes_wide(const C1EncodeLaunch &L, const float *coefs_
 // units, two candidates at offset 0 and eight at five offsets), at every one of which it was the faster kernel (10 times at up to
 // 256 units with eight candidates, 1.4 to 2.4 times at 8 192); C1_MEASURED_WIDE overrides
 constexpr int64_t kMeasuredModesWideUnits = 8192;
+// c1k_launch_measured_modes / _wide with every candidate's errors weighed by one threshold per unit and BFU
+// (c1_k_measured_modes_masked.hip, c1_k_measured_modes_masked_wide.hip; the definition is include/carta1_hip.h's): mask as for
+// c1k_launch_measured_masked (floor[52], then the transposed matrix, device memory), P_b from the unit's all-long plane in L.coefs,
+// which therefore always holds the all-long analysis, whatever the candidates.  weights (units * 52) may be null as every output
+void c1k_launch_measured_modes_masked(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short, const uint8_t *trial,
+                                      int64_t trial_stride, const uint8_t *cand, int n_cand, const int8_t *sf_offsets, int n_offsets,
+                                      const double *mask, bool has_spread, bool finalize, uint8_t *choice, uint8_t *modes_out,
+                                      uint8_t *taken, int8_t *shifts, double *distortion, double *energy, double *weights,
+                                      hipStream_t stream);
+void c1k_launch_measured_modes_masked_wide(const C1EncodeLaunch &L, const float *coefs_short, const uint8_t *side_short,
+                                           const uint8_t *trial, int64_t trial_stride, const uint8_t *cand, int n_cand,
+                                           const int8_t *sf_offsets, int n_offsets, const double *mask, bool has_spread, bool finalize,
+                                           uint8_t *choice, uint8_t *modes_out, uint8_t *taken, int8_t *shifts, double *distortion,
+                                           double *energy, double *weights, hipStream_t stream);
 // the word lengths allocated by the measured coding error (c1_k_measured.hip; the definition is include/carta1_hip.h's).  L.coefs,
 // L.side: the analysis' planes; L.alloc: the record c1k_launch_allocate left for every unit.  Per unit the table e(b, w), the
 // greedy allocation for each of the eight amounts, T_ref over the record and T(n*) over the best greedy one; taken = T(n*) <

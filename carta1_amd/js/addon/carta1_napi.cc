@@ -610,6 +610,68 @@ napi_value EncodeMeasuredMasked(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// encodeMeasuredModesMasked(ctx, [Float32Array...], haloFrames, options, Uint8Array candidates, Int8Array offsets, Float64Array floor,
+// Float64Array spread | null) -> encodeMeasuredModes' object (distortion and energy weighted) and weights:
+// Float64Array(frames*channels*52), the one reciprocal masking threshold per unit and BFU that weighs every candidate:
+// c1_encode_measured_modes_masked_batch
+napi_value EncodeMeasuredModesMasked(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  c1_ctx *ctx;
+  std::vector<float *> ch;
+  size_t samples = 0, n_cand = 0, n_offsets = 0, n_floor = 0, n_spread = 0;
+  int32_t halo = 0;
+  c1_encode_options o;
+  void *cand = nullptr, *offsets = nullptr, *floor = nullptr, *spread = nullptr;
+  if (!get_external(env, argv[0], &ctx) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &halo));
+  if (!get_options(env, argv[3], &o) || !get_typed(env, argv[4], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  if (!get_typed(env, argv[5], napi_int8_array, &offsets, &n_offsets)) return nullptr;
+  napi_valuetype st;
+  NAPI_OK(napi_typeof(env, argv[7], &st));
+  const bool have_spread = st != napi_null && st != napi_undefined;
+  if (!get_typed(env, argv[6], napi_float64_array, &floor, &n_floor)) return nullptr;
+  if (have_spread && !get_typed(env, argv[7], napi_float64_array, &spread, &n_spread)) return nullptr;
+  if (n_floor != 52 || (have_spread && n_spread != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (n_cand < 1 || n_cand > C1_MAX_MODE_CANDIDATES) { napi_throw_range_error(env, nullptr, "candidates must hold 1 to 8 mode bytes"); return nullptr; }
+  if (samples % 512 || (int64_t)(samples / 512) < halo) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  if (n_offsets > 64) n_offsets = 64;                           // the library's own check names the limit
+  const int64_t frames = (int64_t)(samples / 512) - halo;
+  const size_t n_units = (size_t)frames * ch.size();
+  uint8_t *units, *choice, *modes, *taken;
+  napi_value out_units = make_u8(env, n_units * C1_UNIT_BYTES, &units), out_choice = make_u8(env, n_units, &choice),
+             out_modes = make_u8(env, n_units, &modes), out_taken = make_u8(env, n_units, &taken);
+  if (!out_units || !out_choice || !out_modes || !out_taken) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  napi_value ab_s, ab_d, ab_e, ab_w, out_shifts, out_dist, out_energy, out_weights;
+  void *shifts, *dist, *energy, *weights;
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52, &shifts, &ab_s));
+  NAPI_OK(napi_create_typedarray(env, napi_int8_array, n_units * 52, ab_s, 0, &out_shifts));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * 2 * sizeof(double), &dist, &ab_d));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand * 2, ab_d, 0, &out_dist));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * n_cand * sizeof(double), &energy, &ab_e));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * n_cand, ab_e, 0, &out_energy));
+  NAPI_OK(napi_create_arraybuffer(env, n_units * 52 * sizeof(double), &weights, &ab_w));
+  NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * 52, ab_w, 0, &out_weights));
+  const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
+  const int rc = c1_encode_measured_modes_masked_batch(ctx, p, (int)ch.size(), frames, halo, &o, static_cast<const uint8_t *>(cand), (int)n_cand,
+                                                       static_cast<const int8_t *>(offsets), (int)n_offsets, static_cast<const double *>(floor),
+                                                       have_spread ? static_cast<const double *>(spread) : nullptr, units, choice, modes, taken,
+                                                       static_cast<int8_t *>(shifts), static_cast<double *>(dist), static_cast<double *>(energy),
+                                                       static_cast<double *>(weights));
+  if (rc) return throw_c1(env, rc);
+  napi_value obj;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_set_named_property(env, obj, "units", out_units));
+  NAPI_OK(napi_set_named_property(env, obj, "choice", out_choice));
+  NAPI_OK(napi_set_named_property(env, obj, "modes", out_modes));
+  NAPI_OK(napi_set_named_property(env, obj, "taken", out_taken));
+  NAPI_OK(napi_set_named_property(env, obj, "shifts", out_shifts));
+  NAPI_OK(napi_set_named_property(env, obj, "distortion", out_dist));
+  NAPI_OK(napi_set_named_property(env, obj, "energy", out_energy));
+  NAPI_OK(napi_set_named_property(env, obj, "weights", out_weights));
+  return obj;
+}
+
 // measureUnits(ctx, [Float32Array...], haloFrames, Uint8Array units, Float64Array floor | null, Float64Array spread | null)
 // -> { noise, signal: Float64Array(frames*channels*52), totals: Float64Array(frames*channels*2), weights: Float64Array(frames*
 // channels*52), with tables only }: the coding error of given sound units against their PCM, c1_measure_units_batch
@@ -1157,6 +1219,39 @@ napi_value EncStreamPushMeasuredModes(napi_env env, napi_callback_info info) {
   if (rc) return throw_c1(env, rc);
   return out;
 }
+// encStreamPushMeasuredModesMasked(stream, [Float32Array...], Uint8Array candidates, Int8Array offsets | null, Float64Array floor,
+// Float64Array spread | null) -> Uint8Array units: encStreamPushMeasuredModes with every candidate weighed by one masking
+// threshold per unit, as encodeMeasuredModesMasked chooses: c1_enc_stream_push_measured_modes_masked
+napi_value EncStreamPushMeasuredModesMasked(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  c1_enc_stream *s;
+  std::vector<float *> ch;
+  size_t samples = 0, n_cand = 0, n_off = 0, n_floor = 0, n_spread = 0;
+  void *cand = nullptr, *off = nullptr, *floor = nullptr, *spread = nullptr;
+  if (!get_external(env, argv[0], &s) || !get_channels(env, argv[1], &ch, &samples)) return nullptr;
+  if (!get_typed(env, argv[2], napi_uint8_array, &cand, &n_cand)) return nullptr;
+  napi_valuetype t;
+  NAPI_OK(napi_typeof(env, argv[3], &t));
+  if (t != napi_null && t != napi_undefined && !get_typed(env, argv[3], napi_int8_array, &off, &n_off)) return nullptr;
+  if (!get_typed(env, argv[4], napi_float64_array, &floor, &n_floor)) return nullptr;
+  NAPI_OK(napi_typeof(env, argv[5], &t));
+  if (t != napi_null && t != napi_undefined && !get_typed(env, argv[5], napi_float64_array, &spread, &n_spread)) return nullptr;
+  if (n_floor != 52 || (spread && n_spread != 52 * 52)) { napi_throw_type_error(env, nullptr, "masking: floor holds 52 values, spread 52 * 52"); return nullptr; }
+  if (samples % 512) { napi_throw_type_error(env, nullptr, "PCM length must be a multiple of 512"); return nullptr; }
+  if (n_cand > 64) n_cand = 64;                                 // the library's own checks name the limits
+  if (n_off > 64) n_off = 64;
+  const int64_t frames = (int64_t)(samples / 512);
+  uint8_t *units;
+  napi_value out = make_u8(env, (size_t)frames * ch.size() * C1_UNIT_BYTES, &units);
+  const float *p[2] = {ch[0], ch.size() > 1 ? ch[1] : nullptr};
+  const int rc = c1_enc_stream_push_measured_modes_masked(s, p, frames, static_cast<const uint8_t *>(cand), (int)n_cand,
+                                                          static_cast<const int8_t *>(off), off ? (int)n_off : 0,
+                                                          static_cast<const double *>(floor), static_cast<const double *>(spread), units,
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return throw_c1(env, rc);
+  return out;
+}
 // encStreamSetOptions(stream, packedOptions): the options of the next push on (c1_enc_stream_set_options)
 napi_value EncStreamSetOptions(napi_env env, napi_callback_info info) {
   napi_value argv[2];
@@ -1623,6 +1718,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeMeasured", nullptr, EncodeMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredSf", nullptr, EncodeMeasuredSf, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredModes", nullptr, EncodeMeasuredModes, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encodeMeasuredModesMasked", nullptr, EncodeMeasuredModesMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measureUnits", nullptr, MeasureUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measurePcm", nullptr, MeasurePcm, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -1639,6 +1735,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encStreamPush", nullptr, EncStreamPush, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPushMeasured", nullptr, EncStreamPushMeasured, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamPushMeasuredModes", nullptr, EncStreamPushMeasuredModes, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"encStreamPushMeasuredModesMasked", nullptr, EncStreamPushMeasuredModesMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetOptions", nullptr, EncStreamSetOptions, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamGetState", nullptr, StreamGetState<c1_enc_stream, c1_enc_state, c1_enc_stream_get_state>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encStreamSetState", nullptr, StreamSetState<c1_enc_stream, c1_enc_state, c1_enc_stream_set_state>, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -8,7 +8,7 @@ import { SAMPLES_PER_FRAME, AEA_HEADER_SIZE, SOUND_UNIT_SIZE, SAMPLE_RATE } from
 import { encode } from '../pipeline/encoder.js'
 import { decode } from '../pipeline/decoder.js'
 import { serializeFrame, deserializeFrame, AeaFile } from './serialization.js'
-import { native, context, checkPrecision, decodeContext, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, encodeSignalsMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
+import { native, context, checkPrecision, decodeContext, encodeBatchModes, encodeBatchBiases, encodeBestBias, encodeBestModes, encodeMeasured, encodeMeasuredModes, encodeMeasuredModesMasked, encodeSignalsMeasured, checkScaleFactorOffsets, checkMasking } from '../native.js'
 import { biasedTable } from '../coding/bitallocation.js'
 
 function padChannels(channels) {
@@ -61,7 +61,11 @@ export async function encodeAeaPcm(channels, options = {}) {
   // leaves the least error (c1_encode_measured_modes_batch).  scaleFactorOffsets combines with it; mutually exclusive with
   // blockModes, blockModeCandidates and masking (TypeError naming both).  The dearest encode of all: one greedy allocation per
   // unit and candidate
-  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, measuredModeCandidates, scaleFactorOffsets, masking, ...encoderValues } = options
+  // options.modeSearchMasking (with measuredAllocation: true and measuredModeCandidates only, else TypeError naming what is missing):
+  // true or { floor, spread } as for masking.  The search then weighs every candidate's errors with ONE masking threshold per unit
+  // and BFU, from the unit's all-long spectrum (c1_encode_measured_modes_masked_batch).  `masking` keeps meaning "thresholds from
+  // the unit's own modes" and stays mutually exclusive with measuredModeCandidates
+  const { title = 'encoded by carta1', devices, blockModes, allocationBiases, allocationBiasCandidates, blockModeCandidates, measuredAllocation, measuredModeCandidates, modeSearchMasking, scaleFactorOffsets, masking, ...encoderValues } = options
   const encoderOptions = new EncoderOptions(encoderValues)
   const { frames, padded } = padChannels(channels)
   const haveCandidates = allocationBiasCandidates !== undefined && allocationBiasCandidates !== null
@@ -99,6 +103,12 @@ export async function encodeAeaPcm(channels, options = {}) {
     if (!(Array.isArray(measuredModeCandidates) || measuredModeCandidates instanceof Uint8Array) || n < 1 || n > 8) {
       throw new RangeError(`measuredModeCandidates must hold 1 to 8 mode bytes, got ${n}`)
     }
+  }
+  const haveSearchMasking = modeSearchMasking !== undefined && modeSearchMasking !== null && modeSearchMasking !== false
+  if (haveSearchMasking) {
+    if (!measuredAllocation) throw new TypeError('modeSearchMasking needs measuredAllocation: true and measuredModeCandidates: it weighs the measured block-mode search')
+    if (!haveMeasuredModes) throw new TypeError('modeSearchMasking needs measuredModeCandidates: it weighs the measured block-mode search; masking weighs the allocation under given modes')
+    checkMasking(modeSearchMasking)
   }
   if (measuredAllocation) {
     for (const [name, value] of [['allocationBiases', allocationBiases], ['allocationBiasCandidates', allocationBiasCandidates], ['blockModeCandidates', blockModeCandidates]]) {
@@ -167,7 +177,9 @@ export async function encodeAeaPcm(channels, options = {}) {
   const unitCount = frames * channels.length
   const image = new Uint8Array(AEA_HEADER_SIZE + unitCount * SOUND_UNIT_SIZE)
   image.set(AeaFile.createHeader(title, unitCount, channels.length), 0) // frameCount counts units: processor.js:320-325
-  if (frames > 0 && haveMeasuredModes) {
+  if (frames > 0 && haveMeasuredModes && haveSearchMasking) {
+    image.set(encodeMeasuredModesMasked(padded, encoderOptions.toNative(), measuredModeCandidates, haveOffsets ? scaleFactorOffsets : null, modeSearchMasking).units, AEA_HEADER_SIZE)
+  } else if (frames > 0 && haveMeasuredModes) {
     image.set(encodeMeasuredModes(padded, encoderOptions.toNative(), measuredModeCandidates, haveOffsets ? scaleFactorOffsets : null).units, AEA_HEADER_SIZE)
   } else if (frames > 0 && measuredAllocation) {
     image.set(encodeMeasured(padded, encoderOptions.toNative(), blockModes || null, haveOffsets ? scaleFactorOffsets : null, haveMasking ? masking : null).units, AEA_HEADER_SIZE)

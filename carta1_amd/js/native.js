@@ -249,6 +249,20 @@ export function encodeMeasuredModes(channels, nativeOptions, candidates, scaleFa
   return native().encodeMeasuredModes(ctx, channels, haloFrames, nativeOptions, bytes, offsets)
 }
 
+// c1_encode_measured_modes_masked_batch on the default context: encodeMeasuredModes with every candidate's errors divided by ONE
+// masking threshold per unit and BFU, computed from the unit's all-long spectrum whatever the candidates (the weights
+// encodeMeasured reports under all-long modes and the same tables), so that the candidates' weighted T_final are comparable.
+// candidates and scaleFactorOffsets as for encodeMeasuredModes; masking: true (MASKING_DEFAULT) or { floor, spread } as for
+// encodeMeasured, required.  Returns encodeMeasuredModes' object with the weighted distortion and energy, and weights:
+// Float64Array(frames * channels * 52).
+export function encodeMeasuredModesMasked(channels, nativeOptions, candidates, scaleFactorOffsets, masking, haloFrames = 0, ctx = context()) {
+  const bytes = modeCandidateBytes(candidates)
+  const offsets = scaleFactorOffsets === null || scaleFactorOffsets === undefined ? Int8Array.of(0) : checkScaleFactorOffsets(scaleFactorOffsets)
+  if (masking === null || masking === undefined) throw new TypeError('encodeMeasuredModesMasked needs masking: true or { floor, spread }')
+  const tables = checkMasking(masking)
+  return native().encodeMeasuredModesMasked(ctx, channels, haloFrames, nativeOptions, bytes, offsets, tables.floor, tables.spread)
+}
+
 // c1_measure_units_batch on the default context: the coding error of sound units that already exist -- any encoder's -- against
 // their PCM, scored from the bytes with the yardstick of encodeMeasured.  channels: one or two Float32Arrays of (haloFrames +
 // frames) * 512 samples; units: Uint8Array of frames * channels * 212 bytes (frame-major, channels interleaved), every unit's

@@ -18,10 +18,12 @@ import { throwError } from '../utils.js'
 // allocation's final error under each (c1_enc_stream_push_measured_modes); the fields' blockModes are then the unit's, whatever
 // options.fixedBlockModes says.  Neither keeps any state, so frames with and without them may alternate on one pool.  Without the
 // object, or with measuredAllocation falsy, the closure is the reference's, byte for byte; scaleFactorOffsets, masking or
-// measuredModeCandidates without measuredAllocation: true is encodeAeaPcm's TypeError.
+// measuredModeCandidates without measuredAllocation: true is encodeAeaPcm's TypeError.  modeSearchMasking (true | { floor, spread };
+// with measuredAllocation: true and measuredModeCandidates only, else encodeAeaPcm's TypeError naming what is missing) weighs that
+// search with one masking threshold per unit, from the all-long spectrum (c1_enc_stream_push_measured_modes_masked).
 function measuredArguments(measured) {
   if (measured === undefined || measured === null) return null
-  const { measuredAllocation, measuredModeCandidates, scaleFactorOffsets, masking } = measured
+  const { measuredAllocation, measuredModeCandidates, modeSearchMasking, scaleFactorOffsets, masking } = measured
   if (measuredAllocation !== undefined && measuredAllocation !== null && typeof measuredAllocation !== 'boolean') {
     throw new TypeError(`measuredAllocation must be a boolean, got ${measuredAllocation}`)
   }
@@ -37,11 +39,16 @@ function measuredArguments(measured) {
     }
     candidates = modeCandidateBytes(measuredModeCandidates)
   }
+  const haveSearchMasking = modeSearchMasking !== undefined && modeSearchMasking !== null && modeSearchMasking !== false
+  if (haveSearchMasking) {
+    if (!measuredAllocation) throw new TypeError('modeSearchMasking needs measuredAllocation: true and measuredModeCandidates: it weighs the measured block-mode search')
+    if (!haveCandidates) throw new TypeError('modeSearchMasking needs measuredModeCandidates: it weighs the measured block-mode search; masking weighs the allocation under given modes')
+  }
   const haveOffsets = scaleFactorOffsets !== undefined && scaleFactorOffsets !== null
   if (haveOffsets && !measuredAllocation) throw new TypeError('scaleFactorOffsets needs measuredAllocation: true; no other path chooses scale factors')
   if (haveMasking && !measuredAllocation) throw new TypeError('masking needs measuredAllocation: true; no other path weighs its errors')
   if (!measuredAllocation) return null
-  return { candidates, offsets: haveOffsets ? checkScaleFactorOffsets(scaleFactorOffsets) : null, tables: haveMasking ? checkMasking(masking) : { floor: null, spread: null } }
+  return { candidates, offsets: haveOffsets ? checkScaleFactorOffsets(scaleFactorOffsets) : null, tables: haveMasking ? checkMasking(masking) : { floor: null, spread: null }, searchTables: haveSearchMasking ? checkMasking(modeSearchMasking) : null }
 }
 
 export function encode(options = new EncoderOptions(), bufferPool = new BufferPool(), measured = undefined) {
@@ -69,11 +76,13 @@ export function encode(options = new EncoderOptions(), bufferPool = new BufferPo
       bufferPool.encoderOptionsKey = key
     }
     const searched = how !== null && how.candidates !== null
-    const unit = searched
-      ? addon.encStreamPushMeasuredModes(bufferPool.encoderStream, [pcmSamples], how.candidates, how.offsets)
-      : how
-        ? addon.encStreamPushMeasured(bufferPool.encoderStream, [pcmSamples], how.offsets, how.tables.floor, how.tables.spread)
-        : addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
+    const unit = searched && how.searchTables
+      ? addon.encStreamPushMeasuredModesMasked(bufferPool.encoderStream, [pcmSamples], how.candidates, how.offsets, how.searchTables.floor, how.searchTables.spread)
+      : searched
+        ? addon.encStreamPushMeasuredModes(bufferPool.encoderStream, [pcmSamples], how.candidates, how.offsets)
+        : how
+          ? addon.encStreamPushMeasured(bufferPool.encoderStream, [pcmSamples], how.offsets, how.tables.floor, how.tables.spread)
+          : addon.encStreamPush(bufferPool.encoderStream, [pcmSamples])
     const fields = deserializeFrame(unit)
     // same array, as encoder.js:131-132; modes the candidates chose are the unit's own
     if (options.fixedBlockModes && !searched) fields.blockModes = options.fixedBlockModes

@@ -510,7 +510,8 @@ int c1_encode_measured_sf_batch(c1_ctx *ctx, const float *const *pcm, int channe
  * in the workgroup kernel against 2.98 ms a wave per unit, and the whole call 1.54 ms against 2.72 ms for that loop (DESIGN.md
  * 6q).
  * Not done: masking weights in this search (each candidate's thresholds come from another spectrum, and nothing has shown
- * their ratios comparable across modes), pruning of candidates.  The streaming form is c1_enc_stream_push_measured_modes. */
+ * their ratios comparable across modes), pruning of candidates.  The streaming form is c1_enc_stream_push_measured_modes.
+ * c1_encode_measured_modes_masked_* (below) weighs every candidate with one threshold per unit, from the all-long spectrum. */
 int c1_encode_measured_modes_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
                                     const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
                                     const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
@@ -583,6 +584,81 @@ int c1_encode_measured_masked_batch(c1_ctx *ctx, const float *const *pcm, int ch
                                     uint8_t *units /* host, or NULL */, uint8_t *taken /* host, or NULL */,
                                     int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                     double *energy /* host, or NULL */, double *weights /* host, or NULL */);
+
+/* ---- the measured block-mode search under one masking threshold per unit ------------------------------------------------------
+ * c1_encode_measured_masked_* spends a unit's bits by noise-to-mask under the block modes it is given; c1_encode_measured_modes_*
+ * chooses the block modes by an unweighted error.  A unit's own-mode thresholds move with the modes (by up to 19.7 dB in one BFU
+ * between byte 58 and byte 0 on the test material), so per-candidate thresholds are not comparable.  A masking threshold is a
+ * property of the signal, not of the transform chosen to code it: this call computes it once per unit, from the all-long
+ * spectrum, and weighs every candidate's error with it.  OPT-IN like every measured call; the figures are noise-to-mask under the
+ * model of c1_encode_measured_masked_*, and nobody has listened to the result.
+ * New entry points:
+ *   c1_encode_measured_modes_masked_device / _batch.  They take c1_encode_measured_modes_*'s arguments, then mask_floor,
+ *     mask_spread | NULL, and one more optional output, weights (double[units * 52]).
+ *   c1_enc_stream_push_measured_modes_masked, the same extension of c1_enc_stream_push_measured_modes.
+ * Tables are validated and uploaded exactly as in c1_encode_measured_masked_*.  They go through check_masking and
+ * upload_masking, with the same messages and the same stream-order contract.  mask_floor is required.
+ * Weights.  P_b(u) is, bit for bit, the weights row that c1_encode_measured_masked_* reports for unit u under constant modes 0
+ * and these tables.  In detail:
+ *   E_c = sum_j x_c[j]^2 over the all-long coefficients, j ascending, W = 1.
+ *   M_b = sum_c spread[52 b + c] * E_c, c ascending, each product rounded and then added to a sum that starts at +0.0.
+ *   thr_b = M_b > floor[b] ? M_b : floor[b].
+ *   P_b = 1.0 / thr_b.
+ * P_b(u) does not depend on the candidates or on the offsets.
+ * Per candidate k.
+ *   e'_k(b, w) = P_b * e_k(b, w), where e_k is the error table c1_encode_measured_sf_* builds for u under the constant byte
+ *     cand_modes[k].
+ *   e_k includes its W_b for short bands.
+ *   The multiply is applied to the finished entry, before the strictly-smaller compare over the offsets, as in
+ *     c1_encode_measured_masked_*.
+ * From there everything is c1_encode_measured_modes_*'s on e':
+ *   T_ref(u,k) = sum_b e'_0(b, wl_ref_k[b]) from trial record k.
+ *   Gains, greedy, totals, the first amount of least T, the NaN rule, taken(u,k) = T* < T_ref, T_final.
+ *   choice[u] is the smallest k of least T_final.  A NaN never wins; all NaN gives 0.
+ *   modes_out, and the winner's record, taken, shifts and packing.
+ * Outputs.
+ *   distortion and energy have c1_encode_measured_modes_*'s shapes and hold the weighted values.
+ *   weights holds P_b for all 52 BFUs of every unit.
+ *   The units are ordinary sound units.  The bytes do not reveal the weights.
+ *   All outputs NULL is C1_ERR_ARG.  units NULL is measure-only, as in c1_encode_measured_modes_*.
+ * Stream.
+ *   After the push the stream is bit for bit what it is after c1_enc_stream_push_modes(modes_out).
+ *   Rows of a stream pushed from its start are the whole-buffer call's.
+ *   A rejected call leaves the stream and every output as they were.
+ *   What the arguments alone decide is decided before the stream or the context is looked at.
+ * Consequences.  With mask_floor all 1.0 and mask_spread NULL or all zero, weights is exactly 1.0 and the other seven outputs are
+ * bit for bit c1_encode_measured_modes_*'s.  With cand_modes = {0}, units, taken, shifts, distortion, energy and weights are bit
+ * for bit c1_encode_measured_masked_*'s under constant modes 0, and in any candidate set that holds byte 0 that column of
+ * distortion and energy is.  weights is the same bits under every candidate set and every offset set: with tables given the
+ * front end always makes the all-long analysis, also for sets that never code long.  Scaling both tables by 4.0 leaves units,
+ * choice, modes_out, taken and shifts unchanged and multiplies distortion, energy and weights by exactly 0.25.  Limits,
+ * chunking, asynchrony, the choice between the wave-per-unit and the workgroup-per-unit kernel (C1_MEASURED_WIDE), invariance
+ * under the speculation mode, the run length, C1_CHUNK_FRAMES, C1_PIPELINE, C1_OVERLAP and the halo, repeatability and "measure"
+ * in c1_ctx_kernel_ms are c1_encode_measured_modes_*'s.
+ * Not done: a c1_encode_signals_* form, meters under shared weights, tonality, temporal masking, anything stereo-aware. */
+int c1_encode_measured_modes_masked_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                           const c1_encode_options *opts, const uint8_t *cand_modes /* HOST, n_cand bytes */, int n_cand,
+                                           const int8_t *sf_offsets /* HOST, n_offsets values */, int n_offsets,
+                                           const double *mask_floor /* HOST, 52 */, const double *mask_spread /* HOST, 52*52, or NULL */,
+                                           uint8_t *units /* device, frames*channels*212, or NULL: measure only */,
+                                           uint8_t *choice /* device, frames*channels, or NULL */,
+                                           uint8_t *modes_out /* device, frames*channels, or NULL: cand_modes[choice[u]] */,
+                                           uint8_t *taken /* device, frames*channels, or NULL */,
+                                           int8_t *shifts /* device, frames*channels*52, or NULL */,
+                                           double *distortion /* device, frames*channels*n_cand*2: weighted T_ref, T(n*), or NULL */,
+                                           double *energy /* device, frames*channels*n_cand (unit-major), or NULL */,
+                                           double *weights /* device, frames*channels*52: P_b, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The options, the candidates, the offsets, the tables and the outputs are
+ * validated before the context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and
+ * without a device the call then returns C1_ERR_NO_DEVICE.  frames 0 .. 2^22 per channel. */
+int c1_encode_measured_modes_masked_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                          const c1_encode_options *opts, const uint8_t *cand_modes /* host */, int n_cand,
+                                          const int8_t *sf_offsets /* host */, int n_offsets,
+                                          const double *mask_floor /* host, 52 */, const double *mask_spread /* host, 52*52, or NULL */,
+                                          uint8_t *units /* host, or NULL */, uint8_t *choice /* host, or NULL */,
+                                          uint8_t *modes_out /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                          int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                          double *energy /* host, or NULL */, double *weights /* host, or NULL */);
 
 /* ---- the coding error of given sound units against their PCM -----------------------------------------------------------------
  * The calls above report the measured error of the units they are about to pack.  This call takes sound units that already
@@ -807,6 +883,19 @@ int c1_enc_stream_push_measured_modes(c1_enc_stream *s, const float *const *pcm 
                                       uint8_t *modes_out /* host, or NULL */, uint8_t *taken /* host, or NULL */,
                                       int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
                                       double *energy /* host, or NULL */);
+/* c1_enc_stream_push_measured_modes under one masking threshold per unit: the streaming form of
+ * c1_encode_measured_modes_masked_* (above), whose definition holds word for word.  mask_floor is required; the tables are
+ * validated and uploaded as in c1_encode_measured_masked_device, with the same messages and the same stream-order contract.
+ * weights (frames*channels*52) may be NULL like every output but units.  Everything else -- the stream afterwards, the first
+ * two frames after c1_enc_stream_set_state, the order of validation, a rejected call -- is c1_enc_stream_push_measured_modes'. */
+int c1_enc_stream_push_measured_modes_masked(c1_enc_stream *s, const float *const *pcm /* host */, int64_t frames,
+                                             const uint8_t *cand_modes /* host, n_cand bytes */, int n_cand,
+                                             const int8_t *sf_offsets /* host, n_offsets values, or NULL */, int n_offsets,
+                                             const double *mask_floor /* host, 52 */, const double *mask_spread /* host, 52*52, or NULL */,
+                                             uint8_t *units /* host, frames*channels*212 */, uint8_t *choice /* host, or NULL */,
+                                             uint8_t *modes_out /* host, or NULL */, uint8_t *taken /* host, or NULL */,
+                                             int8_t *shifts /* host, or NULL */, double *distortion /* host, or NULL */,
+                                             double *energy /* host, or NULL */, double *weights /* host, or NULL */);
 int c1_dec_stream_create(c1_ctx *ctx, int channels, c1_dec_stream **out);
 int c1_dec_stream_push(c1_dec_stream *s, const uint8_t *units /* host */, int64_t frames,
                        float *const *pcm /* host */);
