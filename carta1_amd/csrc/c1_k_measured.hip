@@ -6,8 +6,10 @@
 namespace {
 
 // the domain of a mode byte is what blockSelectorStage writes (encoder.js:143): 0 or 2 in the low and mid fields, 0 or 3 in
-// the high one.  Every mode byte is brought into it before anything selects with its fields
-__device__ __forceinline__ int mode_in_domain(int b) { return (b & 0x02) | (b & 0x08) | ((b & 0x30) == 0x30 ? 0x30 : 0); }
+// the high one.  Every mode byte is brought into it before anything selects with its fields.  The byte read here is the
+// analysis' own, and under fixedBlockModes such as [1,1,1] or [2,2,1] its fields are the option's: a field that is not zero
+// means short blocks (quantization.js:117 and the MDCT test blockMode === 0), as the packing kernels read it
+__device__ __forceinline__ int mode_in_domain(int b) { return ((b & 0x03) ? 0x02 : 0) | ((b & 0x0c) ? 0x08 : 0) | ((b & 0x30) ? 0x30 : 0); }
 
 // =====================================================================================================
 // k_measured_alloc : e(b, w) for every BFU b and word length w, the greedy allocation for every amount, the fallback
