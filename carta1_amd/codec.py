@@ -439,7 +439,7 @@ class Context:
         out = (units, choice, modes, taken) + ((shifts,) if return_shifts else ())
         return out + (dist, energy) if return_distortion else out
 
-    def measure_units(self, channels, units, masking=None, halo_frames=0, return_weights=False):
+    def measure_units(self, channels, units, masking=None, halo_frames=0, return_weights=False, threshold_from='own'):
         """The coding error of sound units that already exist against their PCM (c1_measure_units_batch): any encoder's units,
         scored from the bytes with the yardstick of encode_measured().  channels: the PCM as for encode() (halo_frames frames of
         real history first); units: uint8 [frames * channels, 212], unit index = frame * channels + channel, every unit's block
@@ -447,7 +447,11 @@ class Context:
         52], signal float64 [units, 52], totals float64 [units, 2]): per BFU the W-weighted squared error of the dequantized
         unit against the exact coefficients under the unit's own block modes and the W-weighted energy of those, and their sums
         over the BFUs.  masking: None, or as for encode_measured() -- totals are then the sums weighted by every BFU's reciprocal
-        masking threshold, which return_weights (needs masking) appends as weights float64 [units, 52]."""
+        masking threshold, which return_weights (needs masking) appends as weights float64 [units, 52].  threshold_from: 'own'
+        forms those thresholds from the unit's spectrum under its own block modes; 'long' (needs masking) from the frame's
+        all-long spectrum, the one threshold per unit of encode_measured_modes(masking=...) under which units coded in different
+        modes compare (c1_measure_units_shared_batch); noise and signal are the same either way."""
+        shared = check_threshold_from(threshold_from, masking)
         chans = [np.ascontiguousarray(c, dtype=np.float32) for c in channels]
         n = len(chans[0])
         if any(len(c) != n for c in chans) or n % 512:
@@ -462,7 +466,8 @@ class Context:
         totals = np.zeros((frames * len(chans), 2), dtype=np.float64)
         weights = np.zeros((frames * len(chans), 52), dtype=np.float64) if return_weights else None
         ptrs = capi.ptr_array([c.ctypes.data + halo_frames * 512 * 4 for c in chans])
-        capi.check(capi.load().c1_measure_units_batch(
+        call = capi.load().c1_measure_units_shared_batch if shared else capi.load().c1_measure_units_batch
+        capi.check(call(
             self._h, ptrs, len(chans), n // 512 - halo_frames, halo_frames, u.ctypes.data,
             None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
             noise.ctypes.data, signal.ctypes.data, totals.ctypes.data, None if weights is None else weights.ctypes.data))
@@ -622,14 +627,17 @@ class Context:
                                                          vp(distortion_ptr), vp(energy_ptr)))
 
     def measure_units_device(self, pcm_ptrs, frames, units_ptr, noise_ptr=None, signal_ptr=None, totals_ptr=None, weights_ptr=None,
-                             masking=None, halo_frames=0):
+                             masking=None, halo_frames=0, threshold_from='own'):
         """c1_measure_units_device: units_ptr = frames * channels sound units on the device (4-byte aligned; the block modes are
         not checked: a unit outside the domain is measured under the byte brought into it, never with an access outside the
         buffers); outputs on the device, each may be None, not all: noise, signal and weights float64 [units, 52], totals
-        float64 [units, 2].  masking (host values, as for measure_units); weights_ptr needs it (the library's own check)."""
+        float64 [units, 2].  masking (host values, as for measure_units); weights_ptr needs it (the library's own check).
+        threshold_from as for measure_units: 'long' (needs masking) takes c1_measure_units_shared_device."""
+        shared = check_threshold_from(threshold_from, masking)
         vp = lambda p: C.c_void_p(p) if p else None
         mask = None if masking is None else check_masking(masking, check=False)   # the library's own check decides
-        capi.check(capi.load().c1_measure_units_device(
+        call = capi.load().c1_measure_units_shared_device if shared else capi.load().c1_measure_units_device
+        capi.check(call(
             self._h, capi.ptr_array(pcm_ptrs), len(pcm_ptrs), frames, halo_frames, vp(units_ptr),
             None if mask is None else mask[0].ctypes.data, None if mask is None or mask[1] is None else mask[1].ctypes.data,
             vp(noise_ptr), vp(signal_ptr), vp(totals_ptr), vp(weights_ptr)))
@@ -1585,6 +1593,16 @@ def check_masking(masking, check=True):
 
 
 # ---- the coding error of given sound units (c1_measure_units_*) --------------------------------------------------------------
+def check_threshold_from(threshold_from, masking):
+    """threshold_from of Context.measure_units -> True for 'long' (c1_measure_units_shared_*), False for 'own'.  ValueError for
+    anything else and for 'long' without masking: the all-long threshold is made of the tables."""
+    if threshold_from not in ('own', 'long'):
+        raise ValueError("threshold_from must be 'own' or 'long', got %r" % (threshold_from,))
+    if threshold_from == 'long' and masking is None:
+        raise ValueError("threshold_from='long' needs masking")
+    return threshold_from == 'long'
+
+
 def check_measured_units(units, frames, channels):
     """the units of Context.measure_units -> contiguous uint8 [frames * channels, 212].  ValueError for another size and for the
     first unit whose block modes (deserializeFrame's: 2, 2 and 3 minus the fields of the first six bits) are outside the

@@ -3149,6 +3149,134 @@ int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
   return C1_OK;
 }
 
+// ---- the same under the all-long threshold (c1_measure_units_shared_*) -------------------------------------------------------
+// what the arguments of both calls decide alone: c1_measure_units_*' rules, and the floor is required
+static int check_measure_shared_args(const char *what, const double *mask_floor, const double *mask_spread, const double *noise,
+                                     const double *signal, const double *totals, const double *weights) {
+  if (!noise && !signal && !totals && !weights) return fail(C1_ERR_ARG, "%s: noise, signal, totals and weights are all NULL", what);
+  if (mask_spread && !mask_floor) return fail(C1_ERR_ARG, "%s: mask_spread needs mask_floor", what);
+  if (!mask_floor) return fail(C1_ERR_ARG, "%s: mask_floor is NULL: the all-long threshold needs the tables", what);
+  return check_masking(what, mask_floor, mask_spread);
+}
+
+int c1_measure_units_shared_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                   const uint8_t *units, const double *mask_floor, const double *mask_spread, double *noise,
+                                   double *signal, double *totals, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_measure_units_shared_device";
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxChunkFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxChunkFrames);
+  if ((rc = check_measure_shared_args(what, mask_floor, mask_spread, noise, signal, totals, weights))) return rc;
+  if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+  for (int c = 0; c < channels; c++) {
+    if (!pcm[c] && frames > 0) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if ((uintptr_t)pcm[c] & 15) return fail(C1_ERR_ARG, "pcm[%d] must be 16-byte aligned on the device", c);
+  }
+  if (!units && frames > 0) return fail(C1_ERR_ARG, "%s: units is NULL", what);
+  if ((uintptr_t)units & 3) return fail(C1_ERR_ARG, "%s: units must be 4-byte aligned on the device", what);
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (ctx->profiling && ctx->timing_depth == 0) reset_timings(ctx);
+  if (frames == 0) return C1_OK;
+  // the tail of an earlier speculative encode was joined above: this call works on the context's stream alone
+  if ((rc = upload_masking(ctx, mask_floor, mask_spread))) return rc;
+  const int64_t chunk = chunk_for_call(ctx, frames, channels, true, 0, true);
+  if ((rc = ensure_workspace(ctx, std::min(frames, chunk) * channels))) return rc;
+  if ((rc = ensure_detect_workspace(ctx, std::min(frames, chunk) * channels))) return rc;
+  if ((rc = ensure_best_modes_planes(ctx, std::min(frames, chunk) * channels))) return rc;
+  // Per chunk, on workspace half 0: c1_measure_units_device's front end into the chunk's plane under the units' modes, then, from
+  // the same band samples, the all-long analysis into the mode search's second plane (encode_device_impl's idiom), then the meter.
+  // A frame's coefficients do not depend on the modes of the frames before it, so a chunk needs the PCM history alone
+  for (int64_t f0 = 0, n = 0; f0 < frames; f0 += n) {
+    n = std::min(chunk, frames - f0);
+    C1EncodeLaunch L;
+    memset(&L, 0, sizeof L);
+    for (int c = 0; c < channels; c++) L.pcm[c] = pcm[c] + f0 * 512;
+    L.channels = channels;
+    L.frames = n;
+    L.halo_frames = (int)std::min<int64_t>(2, f0 + halo_frames);
+    L.tables = ctx->d_tables;
+    L.opts = ctx->d_opts;
+    L.coefs = ctx->d_coefs[0];
+    L.side = ctx->d_side[0];
+    C1EncodeLaunch L0 = L;                                     // the all-long analysis: its side records are not read
+    L0.coefs = ctx->d_bm_coefs;
+    L0.side = ctx->d_bm_side;
+    const uint8_t *chunk_units = units + f0 * channels * C1_UNIT_BYTES;
+    uint8_t *mode_bytes = ctx->d_alloc[0];
+    const int64_t at = f0 * channels;
+    {
+      ScopedTiming t(ctx, K_ANALYSIS);
+      c1k_launch_unit_mode_bytes(chunk_units, n * channels, mode_bytes, ctx->stream);
+      c1k_launch_modes_front(L, mode_bytes, ctx->d_bands[0], ctx->d_modes[0], ctx->d_lists[0], ctx->stream);
+      c1k_launch_mdct_bands(L, ctx->d_bands[0], ctx->d_modes[0], ctx->d_lists[0], ctx->stream);
+      c1k_launch_const_mode_lists(0, n * channels, ctx->d_modes[0], ctx->d_lists[0], ctx->stream);
+      c1k_launch_mdct_bands(L0, ctx->d_bands[0], ctx->d_modes[0], ctx->d_lists[0], ctx->stream);
+    }
+    ScopedTiming t(ctx, K_METER);
+    c1k_launch_measure_units_shared(ctx->d_tables, L.coefs, L0.coefs, chunk_units, n * channels, ctx->d_mask, mask_spread != nullptr,
+                                    noise ? noise + at * 52 : nullptr, signal ? signal + at * 52 : nullptr,
+                                    totals ? totals + at * 2 : nullptr, weights ? weights + at * 52 : nullptr, ctx->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return C1_OK;
+}
+
+int c1_measure_units_shared_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                  const uint8_t *units, const double *mask_floor, const double *mask_spread, double *noise,
+                                  double *signal, double *totals, double *weights) {
+  // everything the arguments alone decide comes first and needs neither a context nor a device
+  const char *const what = "c1_measure_units_shared_batch";
+  int rc = check_channels(channels);
+  if (rc) return rc;
+  if (frames < 0 || halo_frames < 0 || halo_frames > 2) return fail(C1_ERR_ARG, "bad frames / halo_frames");
+  if (frames > kMaxModesBatchFrames) return fail(C1_ERR_ARG, "at most %lld frames per call", (long long)kMaxModesBatchFrames);
+  if ((rc = check_measure_shared_args(what, mask_floor, mask_spread, noise, signal, totals, weights))) return rc;
+  if (frames > 0) {
+    if (!pcm) return fail(C1_ERR_ARG, "pcm is NULL");
+    for (int c = 0; c < channels; c++) if (!pcm[c]) return fail(C1_ERR_ARG, "pcm[%d] is NULL", c);
+    if (!units) return fail(C1_ERR_ARG, "%s: units is NULL", what);
+    if ((rc = check_unit_modes(what, units, frames, channels))) return rc;
+  }
+  if (!ctx) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(C1_ERR_NO_DEVICE, "%s: no HIP device available; this library has no CPU path", what); }
+    return fail(C1_ERR_ARG, "context is NULL");
+  }
+  CTX_GUARD(ctx);
+  if ((rc = ctx_bind(ctx))) return rc;
+  if (frames == 0) return C1_OK;
+  // one copy in, the device call, one copy out per output
+  const size_t n_units = (size_t)frames * channels;
+  const size_t ch_bytes = (size_t)(frames + halo_frames) * 512 * sizeof(float);
+  auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t unit_off = up256(ch_bytes * channels), noise_off = up256(unit_off + n_units * C1_UNIT_BYTES),
+               signal_off = up256(noise_off + n_units * 52 * sizeof(double)), totals_off = up256(signal_off + n_units * 52 * sizeof(double)),
+               weight_off = up256(totals_off + n_units * 2 * sizeof(double));
+  if ((rc = ensure_io(ctx, weight_off + n_units * 52 * sizeof(double)))) return rc;
+  const float *dptr[C1_MAX_CHANNELS] = {nullptr, nullptr};
+  for (int c = 0; c < channels; c++) {
+    float *d = reinterpret_cast<float *>((char *)ctx->d_io + ch_bytes * c);
+    HIP_TRY(hipMemcpyAsync(d, pcm[c] - (size_t)halo_frames * 512, ch_bytes, hipMemcpyHostToDevice, ctx->stream));
+    dptr[c] = d + (size_t)halo_frames * 512;
+  }
+  uint8_t *d_units = (uint8_t *)ctx->d_io + unit_off;
+  double *d_noise = reinterpret_cast<double *>((char *)ctx->d_io + noise_off), *d_signal = reinterpret_cast<double *>((char *)ctx->d_io + signal_off),
+         *d_totals = reinterpret_cast<double *>((char *)ctx->d_io + totals_off), *d_weights = reinterpret_cast<double *>((char *)ctx->d_io + weight_off);
+  HIP_TRY(hipMemcpyAsync(d_units, units, n_units * C1_UNIT_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = c1_measure_units_shared_device(ctx, dptr, channels, frames, halo_frames, d_units, mask_floor, mask_spread,
+                                           noise ? d_noise : nullptr, signal ? d_signal : nullptr, totals ? d_totals : nullptr,
+                                           weights ? d_weights : nullptr))) return rc;
+  if (noise) HIP_TRY(hipMemcpyAsync(noise, d_noise, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (signal) HIP_TRY(hipMemcpyAsync(signal, d_signal, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (totals) HIP_TRY(hipMemcpyAsync(totals, d_totals, n_units * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, d_weights, n_units * 52 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return C1_OK;
+}
+
 // ---- the decoded PCM error of given sound units (c1_measure_pcm_*) ----------------------------------------------------------
 // what the arguments of both calls decide alone, before a context is looked at
 static int check_measure_pcm_args(const char *what, const float *const *pcm, int channels, int64_t frames, int halo_frames,

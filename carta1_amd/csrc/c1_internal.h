@@ -478,6 +478,11 @@ void c1k_launch_unit_mode_bytes(const uint8_t *units, int64_t n, uint8_t *modes,
 // c1k_launch_measured_masked, or null: P_b = 1.0.  noise, signal, weights (n * 52) and totals (n * 2) may each be null
 void c1k_launch_measure_units(const C1DevTables *tables, const float *coefs, const uint8_t *units, int64_t n, const double *mask,
                               bool has_spread, double *noise, double *signal, double *totals, double *weights, hipStream_t stream);
+// the same under the all-long threshold (c1_k_measure_units_shared.hip): coefs_long holds the n * 512 coefficients of the exact
+// analysis under mode byte 0, from which the weights come as c1k_launch_measured_modes_masked forms them; mask is not null
+void c1k_launch_measure_units_shared(const C1DevTables *tables, const float *coefs, const float *coefs_long, const uint8_t *units,
+                                     int64_t n, const double *mask, bool has_spread, double *noise, double *signal, double *totals,
+                                     double *weights, hipStream_t stream);
 // the error of the decoded PCM of given sound units against the delayed input (c1_k_measure_pcm.hip; the definition is
 // include/carta1_hip.h's): k_decode<double>'s walk over the units, the comparison in place of the PCM stores
 void c1k_launch_measure_pcm(const C1MeasurePcmLaunch &L, hipStream_t stream);

@@ -674,8 +674,9 @@ napi_value EncodeMeasuredModesMasked(napi_env env, napi_callback_info info) {
 
 // measureUnits(ctx, [Float32Array...], haloFrames, Uint8Array units, Float64Array floor | null, Float64Array spread | null)
 // -> { noise, signal: Float64Array(frames*channels*52), totals: Float64Array(frames*channels*2), weights: Float64Array(frames*
-// channels*52), with tables only }: the coding error of given sound units against their PCM, c1_measure_units_batch
-napi_value MeasureUnits(napi_env env, napi_callback_info info) {
+// channels*52), with tables only }: the coding error of given sound units against their PCM, c1_measure_units_batch; shared: under
+// the all-long threshold, c1_measure_units_shared_batch (the library requires the floor)
+static napi_value measure_units_call(napi_env env, napi_callback_info info, bool shared) {
   napi_value argv[6];
   if (!get_args(env, info, 6, argv)) return nullptr;
   c1_ctx *ctx;
@@ -708,16 +709,19 @@ napi_value MeasureUnits(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_units * width[k], ab, 0, &arrays[k]));
   }
   const float *p[2] = {ch[0] + (size_t)halo * 512, ch.size() > 1 ? ch[1] + (size_t)halo * 512 : nullptr};
-  const int rc = c1_measure_units_batch(ctx, p, (int)ch.size(), frames, halo, static_cast<const uint8_t *>(units),
-                                        have_floor ? static_cast<const double *>(floor) : nullptr,
-                                        have_spread ? static_cast<const double *>(spread) : nullptr, static_cast<double *>(data[0]),
-                                        static_cast<double *>(data[1]), static_cast<double *>(data[2]), static_cast<double *>(data[3]));
+  const int rc = (shared ? c1_measure_units_shared_batch : c1_measure_units_batch)(
+      ctx, p, (int)ch.size(), frames, halo, static_cast<const uint8_t *>(units), have_floor ? static_cast<const double *>(floor) : nullptr,
+      have_spread ? static_cast<const double *>(spread) : nullptr, static_cast<double *>(data[0]), static_cast<double *>(data[1]),
+      static_cast<double *>(data[2]), static_cast<double *>(data[3]));
   if (rc) return throw_c1(env, rc);
   napi_value obj;
   NAPI_OK(napi_create_object(env, &obj));
   for (int k = 0; k < n_out; k++) NAPI_OK(napi_set_named_property(env, obj, names[k], arrays[k]));
   return obj;
 }
+napi_value MeasureUnits(napi_env env, napi_callback_info info) { return measure_units_call(env, info, false); }
+// measureUnitsShared: the same arguments and result, the weights from the frame's all-long spectrum
+napi_value MeasureUnitsShared(napi_env env, napi_callback_info info) { return measure_units_call(env, info, true); }
 
 // measurePcm(ctx, [Float32Array...], haloFrames, Uint8Array units, haloUnits) -> { noise, signal: Float64Array(frames*channels*16),
 // totals: Float64Array(frames*channels*2) }: the error of the decoded PCM of given sound units against their PCM, per 32 samples,
@@ -1721,6 +1725,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"encodeMeasuredModesMasked", nullptr, EncodeMeasuredModesMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeMeasuredMasked", nullptr, EncodeMeasuredMasked, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measureUnits", nullptr, MeasureUnits, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"measureUnitsShared", nullptr, MeasureUnitsShared, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"measurePcm", nullptr, MeasurePcm, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"decodeBatch", nullptr, DecodeBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"encodeWavBatch", nullptr, EncodeWavBatch, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -271,6 +271,9 @@ export function encodeMeasuredModesMasked(channels, nativeOptions, candidates, s
 // W-weighted squared error of the dequantized unit against the exact coefficients under the unit's own block modes and the
 // W-weighted energy of those, totals: Float64Array(frames * channels * 2), their sums over the BFUs -- weighted by every BFU's
 // reciprocal masking threshold when masking is given, and the result then gains weights: Float64Array(frames * channels * 52) }.
+// thresholdFrom: 'own' (the default) forms those thresholds from the unit's spectrum under its own block modes; 'long' (needs
+// masking) from the frame's all-long spectrum, the one threshold per unit of encodeMeasuredModesMasked under which units coded in
+// different modes compare (c1_measure_units_shared_batch).  noise and signal are the same either way.
 // Arguments that break these rules are a TypeError naming the argument, raised before any native call.
 export function checkMeasuredUnits(channels, units, haloFrames = 0) {
   if (!Array.isArray(channels) || channels.length < 1 || channels.length > 2 || channels.some((c) => !(c instanceof Float32Array))) {
@@ -298,11 +301,16 @@ export function checkMeasuredUnits(channels, units, haloFrames = 0) {
 }
 
 export function measureUnits(channels, units, options = {}, ctx = context()) {
-  if (options === null || typeof options !== 'object') throw new TypeError('options must be an object { masking, haloFrames }')
+  if (options === null || typeof options !== 'object') throw new TypeError('options must be an object { masking, haloFrames, thresholdFrom }')
   const haloFrames = options.haloFrames === undefined ? 0 : options.haloFrames
+  const thresholdFrom = options.thresholdFrom === undefined ? 'own' : options.thresholdFrom
+  if (thresholdFrom !== 'own' && thresholdFrom !== 'long') throw new TypeError(`thresholdFrom must be 'own' or 'long', got ${String(thresholdFrom)}`)
+  const noMasking = options.masking === null || options.masking === undefined
+  if (thresholdFrom === 'long' && noMasking) throw new TypeError("thresholdFrom 'long' needs masking")
   checkMeasuredUnits(channels, units, haloFrames)
-  const tables = options.masking === null || options.masking === undefined ? null : checkMasking(options.masking)
-  return native().measureUnits(ctx, channels, haloFrames, units, tables ? tables.floor : null, tables ? tables.spread : null)
+  const tables = noMasking ? null : checkMasking(options.masking)
+  const call = thresholdFrom === 'long' ? native().measureUnitsShared : native().measureUnits
+  return call(ctx, channels, haloFrames, units, tables ? tables.floor : null, tables ? tables.spread : null)
 }
 
 // c1_measure_pcm_batch on the default context: the error of the decoded PCM of sound units against the PCM they were made from,

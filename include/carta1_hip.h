@@ -710,6 +710,51 @@ int c1_measure_units_batch(c1_ctx *ctx, const float *const *pcm, int channels, i
                            const double *mask_spread /* host, or NULL */, double *noise /* host, or NULL */,
                            double *signal /* host, or NULL */, double *totals /* host, or NULL */, double *weights /* host, or NULL */);
 
+/* ---- the coding error of given sound units under the all-long threshold --------------------------------------------------------
+ * c1_measure_units_* forms P_b from the unit's own-mode spectrum, so units coded in different block modes are scored against
+ * different thresholds.  c1_encode_measured_modes_masked_* judges every candidate of a unit under one threshold, that of the
+ * frame's all-long spectrum; this call scores given units on that scale, from the bytes.  It encodes nothing and changes no state.
+ * Arguments, geometry, fields, mode byte (the host call rejects a byte outside the domain, the device call brings it in),
+ * coefficients and dequantized values are c1_measure_units_*'s.  For unit u:
+ *   noise[52u + b] and signal[52u + b] are exactly c1_measure_units_*'s: the coefficients under the unit's own mode byte, W_b,
+ *     j ascending, binary64, nothing fused.
+ *   weights[52u + b] = P_b is c1_encode_measured_modes_masked_*'s weight:
+ *     x0 are the Float32 MDCT coefficients of the frame under mode byte 0 (all long), the exact kernels';
+ *     E_c = sum_j x0_c[j]^2, j ascending, W = 1;
+ *     M_b = sum_c mask_spread[52 b + c] * E_c, c ascending, each product rounded, then added to a sum that starts at +0.0; a NULL
+ *       mask_spread skips the sum (M_b = +0.0);
+ *     thr_b = M_b > mask_floor[b] ? M_b : mask_floor[b]  (a NaN M_b falls to the floor);   P_b = 1.0 / thr_b.
+ *     P_b does not depend on the unit's bytes at all.
+ *   totals[2u] = sum_b P_b * noise[52u + b]     totals[2u + 1] = sum_b P_b * signal[52u + b]     b ascending, each product
+ *     rounded before it is added.
+ * For the units c1_encode_measured_modes_masked_* writes, under the same PCM, tables, candidates and offsets, totals[2u] is its
+ * distortion[(u * n_cand + choice[u]) * 2 + taken[u]], totals[2u + 1] its energy[u * n_cand + choice[u]] and weights its
+ * weights, bit for bit.  For units whose mode byte is 0 every output equals c1_measure_units_*'s under the same tables.
+ * mask_floor is required: NULL is C1_ERR_ARG.  mask_floor, mask_spread: HOST memory in both calls, validated as for
+ * c1_encode_measured_masked_* (same messages) and copied into the same buffer of the context under the same stream-order
+ * contract.  Every output may be NULL; all four NULL is C1_ERR_ARG, as are mask_spread without mask_floor and a NULL units or pcm
+ * with frames to process.  In both calls everything the arguments alone decide is decided before the context or a device is looked
+ * at, and a rejected call writes nothing.  No output depends on the speculation mode, the run length, C1_CHUNK_FRAMES,
+ * C1_PIPELINE, C1_OVERLAP, the halo (given the same real history) or on which outputs are asked for, and the same inputs give the
+ * same bits.  Non-finite PCM gives non-finite outputs.  No byte pattern of a unit makes any access leave the buffers.
+ * device-resident: pcm[c] (16-byte aligned), units (4-byte aligned) and the outputs are DEVICE pointers; limits on frames,
+ * chunking, asynchrony and the caller's-stream contract are c1_measure_units_device's.  Per chunk the exact analysis runs twice
+ * from one set of band samples, under the units' modes and all long (the second plane is the mode search's workspace), then one
+ * kernel reads bytes and both planes back.  c1_ctx_kernel_ms counts that kernel under "meter" and the analysis under
+ * "analysis". */
+int c1_measure_units_shared_device(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                   const uint8_t *units /* device, frames*channels*212 */,
+                                   const double *mask_floor /* HOST, 52 */, const double *mask_spread /* HOST, 52*52, or NULL */,
+                                   double *noise /* device, frames*channels*52, or NULL */, double *signal /* device, frames*channels*52, or NULL */,
+                                   double *totals /* device, frames*channels*2, or NULL */, double *weights /* device, frames*channels*52, or NULL */);
+/* host-resident, synchronous: every pointer HOST.  The tables, the outputs and every unit's mode byte are validated before the
+ * context is looked at or any device work is done (C1_ERR_ARG, nothing written); without a context and without a device the
+ * call then returns C1_ERR_NO_DEVICE.  One copy in, the device call, one copy out per output.  frames 0 .. 2^22 per channel. */
+int c1_measure_units_shared_batch(c1_ctx *ctx, const float *const *pcm, int channels, int64_t frames, int halo_frames,
+                                  const uint8_t *units /* host */, const double *mask_floor /* host */,
+                                  const double *mask_spread /* host, or NULL */, double *noise /* host, or NULL */,
+                                  double *signal /* host, or NULL */, double *totals /* host, or NULL */, double *weights /* host, or NULL */);
+
 /* ---- the error of the decoded PCM of given sound units against their PCM, per 32 samples ---------------------------------------
  * c1_measure_units_* compares coefficients; this call compares what a listener gets: it decodes the units exactly as
  * c1_decode_device does and reports how far the decoded PCM is from the PCM that went in, per unit and per 32-sample segment, in
